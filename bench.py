@@ -12,7 +12,11 @@ all-reduce of that buffer (236 B/Gaussian).  Per-GPU work is fixed as N grows (w
 Metric numerator: F = sum over pixels of n_contrib, counted per view outside the
 timed region.  Inputs are resident in HBM before the timed region starts.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--mode sh|precomp] [--no-cpu]
+A plain run sets up, warms up, times the K steps and prints the JSON line.  ``--full`` adds everything else the line
+reports: per-kernel times and the roofline of the dominant kernel, the secondary workloads and the CPU baselines.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--mode sh|precomp] [--full [--no-cpu] [--no-secondary]]
+       [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -42,7 +46,7 @@ PROFILE_SET = "r06_f"          # profiles/<set>_{hbm,sq}_counters.json: the PMC 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--views-per-gpu", type=int, default=8, help="frames each GPU renders per step (64-view batch / 8 GPUs)")
     ap.add_argument("--config", type=int, default=3, help="BASELINE.json config index (1-based); 3 = 500k/1080p/SH3")
@@ -56,13 +60,17 @@ def parse():
     ap.add_argument("--per-view-calls", action="store_true", help="drive every view through autograd (SyncFreeBatch.run) instead of the whole-batch path (run_views)")
     ap.add_argument("--sync-per-frame", action="store_true", help="reference protocol: read num_rendered back in every forward")
     ap.add_argument("--no-fused-accumulate", action="store_true", help="let autograd add each view's gradients in a separate pass")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-kernel times and the roofline (an instrumented pass before and after the timed "
+                    "steps), the secondary workloads and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (images, parameter gradients, dL/d means2D) as DIR/<name>.npy, "
+                    "float32; arrays over the budget as a fixed seeded sample")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to smoke-test the N>1 control flow)")
     ap.add_argument("--same-device", action="store_true", help="testing only: every rank uses cuda:0 (needs --backend gloo)")
     ap.add_argument("--cpu-frames", type=int, default=3)
     ap.add_argument("--order", default="random", choices=["random", "morton"], help="index order of the synthetic Gaussians: the generator's random permutation "
                     "(default, the headline) or a 3-D Morton curve (neighbours in index are neighbours in space, like mesh-bound Gaussians); not the headline")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads (drop-in API per frame, the trainers' protocol at 2048x2048, grown splats, "
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary workloads (drop-in API per frame, the trainers' protocol at 2048x2048, grown splats, "
                     "alive-pair count) that are reported beside the headline at N = 1")
     ap.add_argument("--cpu-splat-only", action="store_true", help="internal: run only the PyTorch point-splat CPU baseline of BASELINE config 1 and print its JSON "
                     "(cpu_baseline starts this as a child process with a time limit)")
@@ -70,7 +78,10 @@ def parse():
                     "starts behind its launch (1 = one blocking all-reduce behind the whole pass).  Default 2 since round 4: cutting the pass costs 1 %% "
                     "with two ranges and 4.6 %% with four, a collective 13-42 us at world size 1 (secondary.rccl_world1), and the all-reduce is longer "
                     "than the whole pass -- two ranges expose the least (DESIGN.md section 7)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def launch_ranks(a) -> int:
@@ -175,11 +186,11 @@ def main():
 
     # fragment / instance counts of the views this rank will time (outside the timed region).  F = sum of n_contrib as the
     # REFERENCE's state defines it (positions in the full 3-sigma-rectangle lists), so instance pruning is off
-    # for this count; R_binned is what the timed path really bins.
+    # for this count; R_binned (--full) is what the timed path really bins.
     used = sorted({v for s in range(a.steps) for v in views_of(s)})
     F_view, R_view, Rb_view = {}, {}, {}
     empty = torch.Tensor([])
-    for prune in (False, True):
+    for prune in ((False, True) if a.full else (False,)):
         _C.set_instance_pruning(prune)
         for v in used:
             rs = settings[v]
@@ -194,6 +205,7 @@ def main():
                 R_view[v] = int(R)
                 del nc
             del geom, binning, img, color, radii
+    _C.set_instance_pruning(True)           # (a process-wide setting) the library's default again: the timed path bins the pruned lists
     torch.cuda.synchronize()
 
     flat = FlatGradients(params)            # parameter .grad tensors are views of one buffer: one collective per step
@@ -202,7 +214,8 @@ def main():
     upstream_batch, upstream_view = None, (lambda v, image: dL)
     if a.loss:
         from youreditableavatar_amd.loss import l1_ssim_value_and_grad
-        targets = torch.rand(VPG, 3, H, W, device=dev)         # stand-ins for the ground-truth images of the step's views
+        # stand-ins for the ground-truth images of the step's views, seeded: the same inputs in every run
+        targets = torch.rand(VPG, 3, H, W, device=dev, generator=torch.Generator(device=dev).manual_seed(cfg["seed"] + 2000))
         upstream_view = lambda v, image: l1_ssim_value_and_grad(image[None], targets[v:v + 1])[1][0]
     if a.batch_upstream:
         upstream_view = None
@@ -215,47 +228,56 @@ def main():
         pending.extend(flat.all_reduce_rows(first, count))      # asynchronous, behind the launch that made this range final
 
     def step(s):
+        """one step; returns the images it rendered (the gradients are in the parameters' .grad)"""
         if batch is not None and not a.per_view_calls:
             # three native calls per step (forward of all views, per-pixel backward of all views, one per-Gaussian backward), one Meta read-back;
             # the one per-Gaussian pass of the step STORES the gradients, so the flat buffer needs no zeroing.  N > 1: that pass runs range by
             # range and every range's all-reduce (RCCL, its own stream) runs beside the pass over the next one.
             if chunks > 1:
-                batch.run_views([settings[v] for v in views_of(s)], means3D, opac, shs, scales, rots, upstream_batch, accumulate=False, upstream_view=upstream_view,
-                                grad_chunks=chunks, on_chunk=reduce_range)
+                images = batch.run_views([settings[v] for v in views_of(s)], means3D, opac, shs, scales, rots, upstream_batch, accumulate=False,
+                                         upstream_view=upstream_view, grad_chunks=chunks, on_chunk=reduce_range)
                 for w in pending:
                     w.wait()
                 pending.clear()
             else:
-                batch.run_views([settings[v] for v in views_of(s)], means3D, opac, shs, scales, rots, upstream_batch, accumulate=False, upstream_view=upstream_view)
+                images = batch.run_views([settings[v] for v in views_of(s)], means3D, opac, shs, scales, rots, upstream_batch, accumulate=False,
+                                         upstream_view=upstream_view)
                 flat.all_reduce()
-            return
+            return images
         flat.zero_()
         if batch is not None:       # the same through autograd, view by view
-            batch.run(views_of(s), rasterize, lambda v, img: dL)
+            images = batch.run(views_of(s), rasterize, lambda v, img: dL)
         else:
+            images = []
             for v in views_of(s):
-                rasterize(v)[0].backward(dL)
+                img = rasterize(v)[0]
+                img.backward(dL)
+                images.append(img.detach())
         flat.all_reduce()
+        return images
 
-    # per-stage times FIRST: one untimed pass with events around every stage (each event costs queue time, so the timed region below keeps
-    # only the events of the dominant kernel -- the one the roofline object reports) on ONE stream.  Until round 5 this pass stood between the
-    # warm-up and the timed blocks, and the first block was the slow one in every line (1.86-1.89 ms against 1.72-1.74 for the other two: the
-    # stream pools of the caching allocator and the speculation state had last seen the one-stream pass) -- a second hiccup in one of the other
-    # two blocks then made that block the median (one line in six: 892 Gfrag/s between 946 and 979).  Now the W warm-up steps run directly in
-    # front of the K timed ones, in the configuration that is timed.
+    # the first batch renders its views synchronously and learns the instance bound that sizes the sync-free steps' buffers (SyncFreeBatch)
     step(0)
     torch.cuda.synchronize()
-    _C.profile_begin(max(a.warmup, 2) * VPG * 8 + 64)
-    if batch is not None:
-        batch.streams = 1                                    # one stream: every kernel has the GPU to itself
-    for s in range(max(a.warmup, 2)):
-        step(s)
-    torch.cuda.synchronize()
-    if batch is not None:
-        batch.streams = a.streams
-    prof_all = _C.profile_end()
-    kern = {k: (ms / max(n, 1)) for k, (ms, n) in prof_all.items() if n > 0}
-    dom = max(kern, key=lambda k: prof_all[k][0]) if kern else None          # most time per step (a batched kernel runs once per step)
+    prof_all, kern, dom = {}, {}, None
+    if a.full:
+        # per-stage times FIRST: one untimed pass with events around every stage (each event costs queue time, so the timed region below keeps
+        # only the events of the dominant kernel -- the one the roofline object reports) on ONE stream.  Until round 5 this pass stood between the
+        # warm-up and the timed blocks, and the first block was the slow one in every line (1.86-1.89 ms against 1.72-1.74 for the other two: the
+        # stream pools of the caching allocator and the speculation state had last seen the one-stream pass) -- a second hiccup in one of the other
+        # two blocks then made that block the median (one line in six: 892 Gfrag/s between 946 and 979).  Now the W warm-up steps run directly in
+        # front of the K timed ones, in the configuration that is timed.
+        _C.profile_begin(max(a.warmup, 2) * VPG * 8 + 64)
+        if batch is not None:
+            batch.streams = 1                                    # one stream: every kernel has the GPU to itself
+        for s in range(max(a.warmup, 2)):
+            step(s)
+        torch.cuda.synchronize()
+        if batch is not None:
+            batch.streams = a.streams
+        prof_all = _C.profile_end()
+        kern = {k: (ms / max(n, 1)) for k, (ms, n) in prof_all.items() if n > 0}
+        dom = max(kern, key=lambda k: prof_all[k][0]) if kern else None          # most time per step (a batched kernel runs once per step)
     # The interpreter's full garbage collection walks every object torch and the scene set-up have created -- ~65 ms on the round's boxes, at a
     # step count the allocation counters decide (tools/trainer_protocol.py <deg> 20 8: one 60-70 ms step per ~150, none with the collector off),
     # i.e. 3 ms per step of whichever block it falls into.  Collect now and move what is alive to the permanent generation: the collector stays
@@ -283,12 +305,15 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for s in range(bounds[bi], bounds[bi + 1]):
-            step(s)
+            images = step(s)
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         block_s.append(time.perf_counter() - t0)
+    if a.dump_outputs and rank == 0:            # before anything else runs a step: the images are a buffer the next step reuses
+        dump_outputs(a.dump_outputs, images, {n: t.grad for n, t in zip(("means3D", "opacities", "scales", "rotations", "shs"), params)},
+                     batch.viewspace_grads if (batch is not None and not a.per_view_calls) else None)
     # the dominant kernel as it runs when the streams share the GPU: the same steps again, now with events around that kernel only
     dom_timed = None
     if dom:
@@ -403,7 +428,7 @@ def main():
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"cfg{a.config}: {P} Gaussians, {W}x{H}, SH degree {D}, colour mode {a.mode}, {V}-view orbit, {VPG} frames per GPU per step",
                        "frames_per_step": N * VPG, "views_per_gpu_per_step": VPG, "fragments_per_frame": int(F_rank / frames_rank),
-                       "instances_per_frame": int(Rm), "instances_binned_per_frame": int(sum(Rb_view[v] for s in range(a.steps) for v in views_of(s)) / frames_rank), "ms_per_frame_per_gpu": round(ms_per_step / VPG, 4),
+                       "instances_per_frame": int(Rm), "instances_binned_per_frame": int(sum(Rb_view[v] for s in range(a.steps) for v in views_of(s)) / frames_rank) if Rb_view else None, "ms_per_frame_per_gpu": round(ms_per_step / VPG, 4),
                        "host_sync": "one per step (SyncFreeBatch)" if batch is not None else "one per frame (reference protocol)",
                        "upstream": "fused L1+SSIM loss against target images (tgs_l1_ssim)" if a.loss else "fixed dL/d image",
                        "native_calls": ("3 per step (run_views)" if not a.per_view_calls else "per view, through autograd") if batch is not None else "per view",
@@ -428,7 +453,7 @@ def main():
             "other_rates": {"Minstances/s": round(R_tot / elapsed / 1e6, 2), "Mpixels/s": round(Npix * frames_rank * N / elapsed / 1e6, 2),
                             "MGaussians/s": round(P * frames_rank * N / elapsed / 1e6, 2), "frames/s": round(frames_rank * N / elapsed, 1)},
         }
-        if N == 1 and not a.no_secondary and a.mode == "sh" and batch is not None and not a.per_view_calls:
+        if a.full and N == 1 and not a.no_secondary and a.mode == "sh" and batch is not None and not a.per_view_calls:
             del batch                                        # (its pooled state: ~2 GB)
             torch.cuda.empty_cache()
             out["secondary"] = secondary_workloads(a, cloud, dev, D, W, H, out["config"]["ms_per_frame_per_gpu"])
@@ -436,11 +461,38 @@ def main():
             # the honest single-frame figure: SURVEY.md 8d's B_alg over the frame time of the path the reference's trainers call
             out["secondary"]["dropin_api"]["frame_hbm_frac"] = round(B_alg / (out["secondary"]["dropin_api"]["ms_per_frame"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
             out["dropin_frame_hbm_frac"] = out["secondary"]["dropin_api"]["frame_hbm_frac"]
-        if N == 1 and not a.no_cpu:
+        if a.full and N == 1 and not a.no_cpu:
             out["cpu_baseline"] = cpu_baseline(cloud, cams[0], dL_np, a)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, images, grads, viewspace):
+    """--dump-outputs: what the last timed step handed its caller -- the rendered images, the parameter gradients and (whole-batch path) dL/d means2D
+    per view -- as float32 ``<name>.npy`` files, so that two builds can be compared output for output.  An array over its budget is a sample at
+    fixed seeded positions: the same pixels of every view and channel, the same Gaussians of every per-Gaussian array (at most 56 MB in all)."""
+    if isinstance(images, (list, tuple)):
+        images = torch.stack(images)
+    V, _, H, W = images.shape
+    grads = {n: g for n, g in grads.items() if g is not None}
+    P = next(iter(grads.values())).shape[0]
+
+    def pick(n, k, seed):
+        idx = np.arange(n) if n <= k else np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+        return torch.from_numpy(idx).to(images.device)
+
+    pixels = pick(H * W, (6 << 20) // (V * 3), 1)                                # <= 24 MB of images
+    # room for dL/d means2D whether or not the path returns it: every path of the same workload samples the same Gaussians
+    per_gaussian = sum(g[0].numel() for g in grads.values()) + V * 3
+    rows = pick(P, (8 << 20) // per_gaussian, 2)                                 # <= 32 MB of per-Gaussian arrays
+    arrays = {"images": images.reshape(V, 3, H * W)[:, :, pixels]}
+    arrays.update({"grad_" + n: g[rows] for n, g in grads.items()})
+    if viewspace is not None:
+        arrays["grad_means2D"] = viewspace[:, rows]
+    os.makedirs(out_dir, exist_ok=True)
+    for n, t in arrays.items():
+        np.save(os.path.join(out_dir, n + ".npy"), t.detach().float().cpu().numpy())
 
 
 def secondary_workloads(a, cloud, dev, D, W, H, headline_ms):

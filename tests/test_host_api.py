@@ -223,7 +223,7 @@ def test_bench_contract_is_parseable_without_a_gpu():
     ast.parse(src)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--views-per-gpu", "--streams", "--sync-per-frame", "--no-cpu"):
+    for flag in ("--gpus", "--steps", "--warmup", "--views-per-gpu", "--streams", "--sync-per-frame", "--no-cpu", "--full", "--dump-outputs"):
         assert flag in out.stdout, flag
     for key in ('"metric"', '"value"', '"unit"', '"n_gpus"', '"steps"', '"warmup"', '"ms_per_step"', '"higher_is_better"', '"scaling"', '"vs_baseline"', '"dtype"',
                 '"data"', '"config"', '"workload"', '"roofline"', '"bound"', '"achieved"', '"peak"', '"frac"', '"traffic"', '"cpu_baseline"', '"cores"', '"kind"',

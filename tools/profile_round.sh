@@ -8,9 +8,9 @@ O=$R/gpurun_out/${1:-r06_f}
 mkdir -p $O
 python3 -c "import sys; sys.path.insert(0, '$R'); from youreditableavatar_amd.build import source_hash; print(source_hash())" > $O/csrc_sha16.txt   # the sources these counters belong to
 cd /tmp && export TMPDIR=/tmp
-timeout 420 python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
-timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp4 -o rp -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu --no-secondary > $O/bench_under_rocprof.json 2> $O/rp4.err
-timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp1 -o rp -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu --no-secondary --streams 1 > $O/bench_under_rocprof_one_stream.json 2> $O/rp1.err
+timeout 420 python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp4 -o rp -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu --no-secondary > $O/bench_under_rocprof.json 2> $O/rp4.err
+timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp1 -o rp -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu --no-secondary --streams 1 > $O/bench_under_rocprof_one_stream.json 2> $O/rp1.err
 timeout 420 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o pmc -- python3 $R/tools/pmc_workload.py 4 > $O/pmc_fetch.log 2>&1
 timeout 420 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o pmc -- python3 $R/tools/pmc_workload.py 4 > $O/pmc_write.log 2>&1
 timeout 420 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES --output-format csv -d $O/pmc_sq -o pmc -- python3 $R/tools/pmc_workload.py 4 > $O/pmc_sq.log 2>&1
@@ -37,9 +37,9 @@ timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_dropin -o pmc -- python3 $R/tools/dropin_loop.py 8 > $O/pmc_write_dropin.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES --output-format csv -d $O/pmc_sq_dropin -o pmc -- python3 $R/tools/dropin_loop.py 8 > $O/pmc_sq_dropin.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_UNALIGNED_STALL SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $O/pmc_lds_dropin -o pmc -- python3 $R/tools/dropin_loop.py 8 > $O/pmc_lds_dropin.log 2>&1
-timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_batch -o pmc -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu --no-secondary --streams 1 > $O/pmc_fetch_batch.log 2>&1
-timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_batch -o pmc -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu --no-secondary --streams 1 > $O/pmc_write_batch.log 2>&1
-timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES --output-format csv -d $O/pmc_sq_batch -o pmc -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu --no-secondary --streams 1 > $O/pmc_sq_batch.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_batch -o pmc -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu --no-secondary --streams 1 > $O/pmc_fetch_batch.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_batch -o pmc -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu --no-secondary --streams 1 > $O/pmc_write_batch.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES --output-format csv -d $O/pmc_sq_batch -o pmc -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu --no-secondary --streams 1 > $O/pmc_sq_batch.log 2>&1
 timeout 300 python3 $R/tools/batch_stage_times.py 1 0 > $O/batch_stage_times.txt 2>/dev/null
 timeout 300 python3 $R/tools/batch_stage_times.py 1 1 >> $O/batch_stage_times.txt 2>/dev/null
 timeout 300 python3 $R/tools/batch_stage_times.py 4 0 >> $O/batch_stage_times.txt 2>/dev/null
@@ -50,9 +50,9 @@ find $O -name "*kernel_trace.csv" -path "*rp*" -delete 2>/dev/null
 ls -R $O | head -60
 tail -c 600 $O/bench_default.json
 # other configurations and the trainers' protocol (rocprof summaries only)
-timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_cfg2 -o rp -- python3 $R/bench.py --config 2 --steps 6 --warmup 2 --no-cpu --no-secondary > $O/bench_cfg2_under_rocprof.json 2> $O/rp_cfg2.err
-timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_cfg5 -o rp -- python3 $R/bench.py --config 5 --views-per-gpu 4 --steps 4 --warmup 2 --no-cpu --no-secondary > $O/bench_cfg5_under_rocprof.json 2> $O/rp_cfg5.err
+timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_cfg2 -o rp -- python3 $R/bench.py --full --config 2 --steps 6 --warmup 2 --no-cpu --no-secondary > $O/bench_cfg2_under_rocprof.json 2> $O/rp_cfg2.err
+timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_cfg5 -o rp -- python3 $R/bench.py --full --config 5 --views-per-gpu 4 --steps 4 --warmup 2 --no-cpu --no-secondary > $O/bench_cfg5_under_rocprof.json 2> $O/rp_cfg5.err
 timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_trainer -o rp -- python3 $R/tools/trainer_protocol.py 0 40 > $O/trainer_protocol.json 2> $O/rp_trainer.err
-timeout 420 python3 $R/bench.py --config 2 --no-cpu --no-secondary > $O/bench_cfg2.json 2>/dev/null
-timeout 420 python3 $R/bench.py --config 5 --views-per-gpu 4 --no-cpu --no-secondary > $O/bench_cfg5.json 2>/dev/null
+timeout 420 python3 $R/bench.py --full --config 2 --no-cpu --no-secondary > $O/bench_cfg2.json 2>/dev/null
+timeout 420 python3 $R/bench.py --full --config 5 --views-per-gpu 4 --no-cpu --no-secondary > $O/bench_cfg5.json 2>/dev/null
 du -sh $O; find $O -size +8M | head
