@@ -430,7 +430,8 @@ __device__ __forceinline__ void bwd_light_group(const ImgState& s, const BinStat
         const PixIn cur = nxt;
         if (bi < 3) nxt = load_block(bi + 1);
         asm volatile("" ::: "memory");                      // (the next block's loads stay here, in front of this block's passes)
-        const float T_final = select_loaded(cur.in, cur.Tf), dpx0 = select_loaded(cur.in, cur.d0), dpx1 = select_loaded(cur.in, cur.d1), dpx2 = select_loaded(cur.in, cur.d2);
+        const unsigned long long keep = keep_mask(cur.in);
+        const float T_final = select_loaded(keep, cur.Tf), dpx0 = select_loaded(keep, cur.d0), dpx1 = select_loaded(keep, cur.d1), dpx2 = select_loaded(keep, cur.d2);
         const uint32_t last_contributor = cur.lc;
         float T = T_final;
         float bg_dot_dpixel = 0.f;                          // backward.cu:533-535
@@ -534,8 +535,9 @@ __global__ __launch_bounds__(BWD_THREADS, 8) void k_render_bwd(const ImgState s,
     if (ht < qmax) fetch(rg.x + qmax - 1 - ht);
     asm volatile("" ::: "memory");
     // (the selects behind the loads' issue: an asm statement waits for its operand where it stands)
-    const float T_final = select_loaded(inside, T_raw);
-    float dpx0 = select_loaded(inside, d_raw0), dpx1 = select_loaded(inside, d_raw1), dpx2 = select_loaded(inside, d_raw2);
+    const unsigned long long keep = keep_mask(inside);
+    const float T_final = select_loaded(keep, T_raw);
+    float dpx0 = select_loaded(keep, d_raw0), dpx1 = select_loaded(keep, d_raw1), dpx2 = select_loaded(keep, d_raw2);
     float T = T_final;
     float bg_dot_dpixel = 0.f;                              // backward.cu:533-535
     bg_dot_dpixel += bg[0] * dpx0; bg_dot_dpixel += bg[1] * dpx1; bg_dot_dpixel += bg[2] * dpx2;

@@ -276,6 +276,11 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(
 //   * gfx940 family: a VALU write of an SGPR / VCC needs 2 wait states before a VALU instruction reads it as a constant.  v_cmp writes vcc, and
 //     v_mbcnt_lo reads vcc_lo: the TWO scalar instructions between them (s_and_saveexec, s_bcnt1) are those wait states -- with no margin.
 //     Whoever removes or moves one of them must put an s_nop in its place.  (The scalar unit's own read of vcc is interlocked.)
+//   * the guard: tests/test_isa_hazards.py compiles every source to gfx950 assembly with the build's flags (this default and the
+//     -DTGS_QL_APPEND_C=1 variant below) and fails on any pair of its rule table -- VALU SGPR / VCC write -> VALU read, VALU VGPR write ->
+//     DPP or permlane-swap read, v_rcp / v_exp result -> use, and more -- with a producer or consumer in inline asm and too few wait states
+//     between them, across labels and branches.  It checks the schedule hipcc emitted: an s_nop that today's schedule does not need still
+//     covers a write hipcc may move next to the block tomorrow; keep them.
 //   * the 16-byte null fill of ql_fill_null and the b16 appends go to the same LDS words: a wave's LDS operations execute in order (one
 //     in-order queue per wave, lgkmcnt counts them in order), so the appends land behind the fill without a wait between them.
 // -DTGS_QL_APPEND_C=1 builds the same three functions from ballot / mbcnt builtins (the compiler's 9-11 instructions per list): the A/B partner
@@ -597,10 +602,20 @@ __device__ __forceinline__ void row_stride4_sum9_banked(float (&v)[9], float& s0
 // Neither `keep ? x : 0` (turned back into a load under a branch of its own: one memory round trip per value) nor `x * (keep ? 1 : 0)` (round 5;
 // 0 * NaN = NaN: a non-finite dL_dpixel at the clamped element -- pixel (0, 0) -- reached every padding lane of the right / bottom edge tiles
 // and from there every splat on those tiles; ADVICE of round 5).  Not volatile: the compiler places it like any vector instruction.
-__device__ __forceinline__ float select_loaded(bool keep, float x)
+// The mask comes from keep_mask, formed on the scalar unit: the ballot itself is a v_cmp, a VALU write of an SGPR pair, and a VALU read of it
+// needs 2 wait states that hipcc does not put in front of an asm statement (round 6: five selects of k_render_bwd sat 1 wait state behind
+// their v_cmp; tests/test_isa_hazards.py).  An SALU write read by a VALU needs none.
+__device__ __forceinline__ unsigned long long keep_mask(bool keep)
+{
+    unsigned long long m;
+    // (=&: a pair of its own -- in the ballot's pair, the v_cmp would still be the last VALU write in front of the selects)
+    asm("s_and_b64 %0, %1, exec" : "=&s"(m) : "s"(__builtin_amdgcn_ballot_w64(keep)) : "scc");
+    return m;
+}
+__device__ __forceinline__ float select_loaded(unsigned long long keep, float x)
 {
     float r;
-    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(x), "s"(__builtin_amdgcn_ballot_w64(keep)));
+    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(x), "s"(keep));
     return r;
 }
 
