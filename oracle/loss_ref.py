@@ -21,6 +21,13 @@ def gaussian_window(window_size: int = 11, sigma: float = 1.5, dtype=torch.float
 def ssim_map(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11) -> torch.Tensor:
     """loss_utils.py:27-58 for [C,H,W] or [B,C,H,W] images: zero-padded depthwise 11x11 Gaussian statistics."""
     C = img1.size(-3)
+    if C == 1:
+        # One channel goes through the depthwise convolution as the first of two channels: the same function (groups = C keeps the
+        # channels apart), computed by the kernel the three-channel cases use.  With groups = 1 the CPU backend picks another kernel whose
+        # fp32 backward depends on the CPU (fixture case c: 0, 7e-8 and 7e-3 rel-L2 on three x86 machines); the depthwise route reproduces
+        # all four fixture cases bit for bit.
+        z1, z2 = torch.zeros_like(img1), torch.zeros_like(img2)
+        return ssim_map(torch.cat([img1, z1], -3), torch.cat([img2, z2], -3), window_size)[..., :1, :, :]
     w1 = gaussian_window(window_size, 1.5, torch.float32).unsqueeze(1)
     w2 = w1.mm(w1.t()).float().to(img1.dtype)                 # the reference forms the 2-D window in fp32 (:29)
     window = w2.unsqueeze(0).unsqueeze(0).expand(C, 1, window_size, window_size).contiguous().to(img1.device)

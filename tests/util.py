@@ -45,7 +45,8 @@ def tolerance(key: str, golden_out: Optional[dict]) -> float:
     return tol
 
 
-def oracle_run(inp: dict, dL: Optional[np.ndarray] = None):
+def oracle_run(inp: dict, dL: Optional[np.ndarray] = None, variant: str = "f32"):
+    """The CPU oracle on one view (``variant``: a build of oracle/tgs_oracle.c, e.g. "f64" for the reference's function in double)."""
     from oracle import oracle
     kw = dict(bg=inp["bg"], means3D=inp["means3D"], viewmatrix=inp["viewmatrix"], projmatrix=inp["projmatrix"],
               campos=inp["campos"], tanfovx=float(inp["tanfovx"]), tanfovy=float(inp["tanfovy"]),
@@ -53,7 +54,7 @@ def oracle_run(inp: dict, dL: Optional[np.ndarray] = None):
     for k in ("shs", "colors_precomp", "scales", "rotations", "cov3D_precomp"):
         kw[k] = inp.get(k)
     color, radii, st = oracle.forward(opacities=inp["opacities"], image_height=int(inp["image_height"]),
-                                      image_width=int(inp["image_width"]), sh_degree=int(inp["sh_degree"]), **kw)
+                                      image_width=int(inp["image_width"]), sh_degree=int(inp["sh_degree"]), variant=variant, **kw)
     H, W = int(inp["image_height"]), int(inp["image_width"])
     out = dict(color=color, radii=radii, num_rendered=st.num_rendered, n_contrib=st.field("n_contrib").reshape(H, W),
                final_T=st.field("final_T").reshape(H, W), point_list=st.field("point_list"),
