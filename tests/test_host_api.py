@@ -150,6 +150,21 @@ def test_sync_free_batch_capacity_policy():
     assert b.capacity() is None
     b._cooldown = 0
     assert b.capacity() == 1 << 16
+    assert SyncFreeBatch(deterministic=True, forward_group=4).options is not None     # explicit options of the whole-batch entry points
+
+
+@pytest.mark.parametrize("field,value", [("image_width", 16), ("sh_degree", 2), ("scale_modifier", 0.5), ("prefiltered", True)])
+def test_run_views_rejects_mixed_views_before_anything_else(field, value):
+    """SyncFreeBatch.run_views checks that the views of a batch share image size, SH degree, scale modifier and the prefiltered flag
+    before it looks at anything else -- so the first batch, which renders its views synchronously, rejects mixed views too."""
+    from youreditableavatar_amd.diff_gaussian_rasterization import GaussianRasterizationSettings
+    from youreditableavatar_amd.multiview import SyncFreeBatch
+    z = torch.zeros
+    rs = GaussianRasterizationSettings(image_height=8, image_width=8, tanfovx=1.0, tanfovy=1.0, bg=z(3), scale_modifier=1.0, viewmatrix=z(4, 4),
+                                       projmatrix=z(4, 4), sh_degree=3, campos=z(3), prefiltered=False, debug=False)
+    leaf = lambda *shape: z(*shape, requires_grad=True)
+    with pytest.raises(RuntimeError, match="share image size"):
+        SyncFreeBatch().run_views([rs, rs._replace(**{field: value})], leaf(4, 3), leaf(4, 1), leaf(4, 16, 3), leaf(4, 3), leaf(4, 4), lambda images: images)
 
 
 def test_tile_bound_policy(monkeypatch):

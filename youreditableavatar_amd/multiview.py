@@ -7,18 +7,22 @@ per-Gaussian gradients of every view into ONE flat fp32 buffer (parameter ``.gra
 into it), and the step ends with ONE all-reduce(sum) of that buffer -- RCCL over xGMI on GPUs
 (backend "nccl"), gloo in the CPU tests.  There is no other data-path collective.
 
-Host logic only: nothing here touches the HIP library, so it runs on CPU with any per-view render
-function (the tests inject the CPU oracle).
+``FlatGradients`` and ``render_batch_sharded`` are host logic only: they run on CPU with any per-view
+render function (the tests inject the CPU oracle).
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Callable, Iterable, List, Optional, Sequence
 
 import ctypes as C
 import os
+import threading
 
 import torch
 import torch.distributed as dist
+
+from .diff_gaussian_rasterization import _C
 
 
 def shard_views(num_views: int, rank: int, world_size: int) -> range:
@@ -285,7 +289,6 @@ class DeferredBackward:
                                means2D=means2D))
 
     def finish(self) -> None:
-        from .diff_gaussian_rasterization import _C
         if not self.views:
             return
         L = self.leaves
@@ -310,7 +313,7 @@ class DeferredBackward:
         self.views = []
 
 
-_collector: Optional[DeferredBackward] = None       # set by SyncFreeBatch.run while it renders its views
+_collector = threading.local()      # .batch: the DeferredBackward of the SyncFreeBatch.run that renders views on this thread
 
 
 class _RasterizeAccumulate(torch.autograd.Function):
@@ -321,7 +324,6 @@ class _RasterizeAccumulate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, r_capacity):
-        from .diff_gaussian_rasterization import _C
         rs = raster_settings
         from . import diff_gaussian_rasterization as dgr
         key = (int(means3D.shape[0]), int(rs.image_height), int(rs.image_width), means3D.device)
@@ -334,7 +336,7 @@ class _RasterizeAccumulate(torch.autograd.Function):
         if dgr._SPECULATE and r_capacity is None:
             dgr._speculation.update(key, out[6] if guess is not None else num_rendered, guess)     # (out[6]: the true count, out[7]: tiles with instances)
         ctx.rs, ctx.num_rendered = rs, num_rendered         # sync-free: the binning capacity (what the buffers are carved for)
-        ctx.collector = _collector if (r_capacity is not None and colors_precomp.numel() == 0) else None
+        ctx.collector = getattr(_collector, "batch", None) if (r_capacity is not None and colors_precomp.numel() == 0) else None
         ctx.means2D = means2D
         ctx.leaves = dict(means3D=means3D, sh=sh, colors_precomp=colors_precomp, opacities=opacities, scales=scales, rotations=rotations,
                           cov3D_precomp=cov3Ds_precomp)
@@ -345,7 +347,6 @@ class _RasterizeAccumulate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, _grad_meta=None):
-        from .diff_gaussian_rasterization import _C
         rs, L = ctx.rs, ctx.leaves
         radii, geom, binning, img = ctx.saved_tensors
         if ctx.collector is not None:
@@ -381,7 +382,108 @@ def rasterize_accumulate(raster_settings, means3D, means2D, opacities, shs=None,
     return (color, radii, meta) if (return_meta or r_capacity is not None) else (color, radii)
 
 
-_SIDE_STREAMS: dict = {}      # device -> [torch.cuda.Stream]: the side streams of all SyncFreeBatch objects (see __init__)
+_SIDE_STREAMS: dict = {}      # device -> [torch.cuda.Stream]: the side streams of all SyncFreeBatch objects (see _lanes)
+_SIDE_LOCK = threading.Lock()
+
+
+def _lanes(main: torch.cuda.Stream, n: int) -> list:
+    """The ``n`` streams a batch spreads its views over: ``main`` and the first n - 1 side streams of its device."""
+    # Side streams are shared by every SyncFreeBatch of the process (round 6): HIP multiplexes streams onto a few hardware queues, and a process that
+    # had created a dozen of them -- bench.py's secondary workloads each built a batch object of their own -- ran its later batches up to 10 % slower
+    # than a fresh process did (streams aliasing onto one queue: less overlap between the views).  A trainer has one batch object; this keeps it so.
+    with _SIDE_LOCK:
+        side = _SIDE_STREAMS.setdefault(main.device, [])
+        while len(side) < n - 1:
+            side.append(torch.cuda.Stream(device=main.device))
+        return [main] + side[:n - 1]
+
+
+def _fork(lanes: list) -> None:
+    """The side lanes wait for what the first lane (the calling stream) holds."""
+    ev = torch.cuda.Event()
+    ev.record(lanes[0])
+    for st in lanes[1:]:
+        st.wait_event(ev)
+
+
+def _join(lanes: list) -> None:
+    """The first lane waits for what the side lanes hold."""
+    for st in lanes[1:]:
+        ev = torch.cuda.Event()
+        ev.record(st)
+        lanes[0].wait_event(ev)
+
+
+def _read_verdicts(ready: Sequence[torch.cuda.Event], host: torch.Tensor) -> list:
+    """The one host wait of a batch -- for the events ``ready``, behind which its Meta records are in the pinned rows ``host`` [V, 64] --
+    and the records decoded: per view (R, rejected, (tiles with instances, tiles with >= 1024, tiles with >= 128 of them))."""
+    for ev in ready:
+        ev.synchronize()
+    rows = []
+    for meta in host:
+        R, flags, _longest, _n_overflow = _C.decode_meta_full(meta)
+        # (a tile list longer than the LDS sort is no reason to reject a frame any more: k_tile_sort's overflow workers sort it on the device)
+        if flags & _C.FRAME_PREFILTERED:
+            raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
+        rows.append((R, bool(flags & _C.FRAME_REJECTED), _C.decode_meta_tiles(meta)))
+    return rows
+
+
+# A checked SyncFreeBatch.run_views call.  M: SH coefficients per Gaussian (0: per-view colours); precomp: per-view colours instead of SH;
+# dsh_plane > 0: shs.grad is level-major, its coefficient planes this many floats apart; params: the leaves whose .grad the batch writes
+# (means3D, opacities, scales, rotations, + sh); colors: colors_precomp [V,P,3], detached; ranges: (first, count) of the per-Gaussian
+# launches, multiples of 256 Gaussians, the same on every rank.
+_Call = namedtuple("_Call", "settings V P H W D M precomp dsh_plane params colors ranges")
+
+
+def _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_batch, upstream_view, colors_precomp, grad_chunks) -> _Call:
+    """Checks the arguments of ``SyncFreeBatch.run_views``, the consistency of the views' settings first."""
+    rs0 = settings[0]
+    V, P, H, W, D = len(settings), int(means3D.size(0)), int(rs0.image_height), int(rs0.image_width), int(rs0.sh_degree)
+    for rs in settings:
+        if (int(rs.image_height), int(rs.image_width), int(rs.sh_degree)) != (H, W, D) or rs.scale_modifier != rs0.scale_modifier or \
+                bool(rs.prefiltered) != bool(rs0.prefiltered):
+            raise RuntimeError("run_views: all views of a batch share image size, SH degree, scale modifier and the prefiltered flag")
+    precomp = colors_precomp is not None
+    if (upstream_batch is None) == (upstream_view is None):
+        raise RuntimeError("run_views: provide exactly one of upstream_batch / upstream_view")
+    if precomp == (shs is not None):
+        raise RuntimeError("run_views: provide exactly one of shs / colors_precomp")
+    params = dict(means3D=means3D, opacities=opacities, scales=scales, rotations=rotations)
+    if precomp:
+        colors_precomp = colors_precomp.detach()
+        if not (colors_precomp.is_cuda and colors_precomp.dtype == torch.float32 and colors_precomp.is_contiguous()
+                and tuple(colors_precomp.shape) == (V, P, 3)):
+            raise RuntimeError("run_views: colors_precomp must be a contiguous float32 GPU tensor [V,P,3]")
+    else:
+        params["sh"] = shs
+    M = 0 if precomp else int(shs.size(1))
+    # dL_dsh level-major (FlatGradients(level_major=True)): .grad is the [P, M, 3] view of M planes, strides (3, plane, 1)
+    dsh_plane = 0
+    if not precomp and shs.grad is not None and not shs.grad.is_contiguous():
+        st = shs.grad.stride()
+        if not (M == 16 and st[0] == 3 and st[2] == 1 and st[1] >= 3 * P and st[1] % 4 == 0 and shs.grad.data_ptr() % 16 == 0):
+            raise RuntimeError("run_views: shs.grad must be contiguous, or the level-major view FlatGradients(level_major=True) makes of a [P,16,3] parameter")
+        dsh_plane = int(st[1])
+    for name, t in params.items():
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.is_leaf and t.grad is not None and
+                (t.grad.is_contiguous() or (name == "sh" and dsh_plane))):
+            raise RuntimeError(f"run_views: {name} must be a contiguous float32 leaf parameter on the GPU with an allocated .grad (see FlatGradients)")
+    n_chunks = max(1, min(int(grad_chunks), (P + 255) // 256))
+    per = ((P + n_chunks - 1) // n_chunks + 255) // 256 * 256
+    ranges = [(first, min(per, P - first)) for first in range(0, P, per)]
+    return _Call(settings, V, P, H, W, D, M, precomp, dsh_plane, params, colors_precomp, ranges)
+
+
+def _upstream_checked(dL: torch.Tensor, c: _Call) -> torch.Tensor:
+    if dL.dtype != torch.float32 or not dL.is_cuda or tuple(dL.shape[-3:]) != (3, c.H, c.W):
+        raise RuntimeError("upstream must return a float32 GPU tensor [V,3,H,W] or [3,H,W]")
+    return dL.contiguous()
+
+
+def _of_view(dL: torch.Tensor, v: int) -> torch.Tensor:
+    """View v's part of an upstream gradient ([3,H,W]: the same for every view)."""
+    return dL if dL.dim() == 3 else dL[v]
 
 
 class SyncFreeBatch:
@@ -417,10 +519,6 @@ class SyncFreeBatch:
         # (k_render_fwd, the loss, k_render_bwd): kernels bound by the L2 atomics / by latency next to kernels bound by VALU issue
         self.split = bool(split)
         self._host: Optional[torch.Tensor] = None
-        # Side streams are shared by every SyncFreeBatch of the process (round 6): HIP multiplexes streams onto a few hardware queues, and a process that
-        # had created a dozen of them -- bench.py's secondary workloads each built a batch object of their own -- ran its later batches up to 10 % slower
-        # than a fresh process did (streams aliasing onto one queue: less overlap between the views).  A trainer has one batch object; this keeps it so.
-        self._side = _SIDE_STREAMS
         self._cooldown = 0                      # batches left to render synchronously (unused since overflow lists are sorted on the device; kept for callers that set it)
         self._pool = None
         self.viewspace_grads: Optional[torch.Tensor] = None
@@ -437,6 +535,16 @@ class SyncFreeBatch:
             return None
         c = int(self.bound * self.headroom) + 1
         return min(0x7fffffff, (c + self.granule - 1) // self.granule * self.granule)
+
+    def _learn(self, seen: int, tiles: Optional[Sequence[int]] = None) -> None:
+        """What a batch saw: the largest instance count of its views, and (sync-free frames) of tiles with instances, with >= 1024, with >= 128."""
+        decayed = lambda bound, new: new if bound is None else max(new, int(bound * 0.95))
+        self.bound = decayed(self.bound, seen)
+        if tiles is not None:
+            self.tile_bound = decayed(self.tile_bound, tiles[0])
+            self.class_bound = [decayed(self.class_bound[0], tiles[1]), decayed(self.class_bound[1], tiles[2])]
+        if self._cooldown > 0:
+            self._cooldown -= 1
 
     # ------------------------------------------------------------------------------------------------------------------
     # Whole-batch path: three trips into the native library per batch (tgs_forward_views, tgs_backward_render_views,
@@ -469,177 +577,53 @@ class SyncFreeBatch:
         ranges of Gaussians, and ``on_chunk`` is called right behind each launch (on the calling stream) -- the parameter gradients of
         Gaussians [first, first + count) are final once that launch is: a data-parallel step starts their all-reduce there
         (``FlatGradients.all_reduce_rows``) while the next range is still being computed."""
-        from .diff_gaussian_rasterization import _C
-        V = len(settings)
-        rs0 = settings[0]
-        P, H, W, D = int(means3D.size(0)), int(rs0.image_height), int(rs0.image_width), int(rs0.sh_degree)
-        precomp = colors_precomp is not None
-        if (upstream_batch is None) == (upstream_view is None):
-            raise RuntimeError("run_views: provide exactly one of upstream_batch / upstream_view")
-        if upstream_batch is None:
-            upstream_batch = lambda images: torch.stack([upstream_view(v, images[v]) for v in range(images.size(0))])   # the synchronous paths
-        if precomp == (shs is not None):
-            raise RuntimeError("run_views: provide exactly one of shs / colors_precomp")
-        params = dict(means3D=means3D, opacities=opacities, scales=scales, rotations=rotations)
-        if precomp:
-            colors_precomp = colors_precomp.detach()
-            if not (colors_precomp.is_cuda and colors_precomp.dtype == torch.float32 and colors_precomp.is_contiguous()
-                    and tuple(colors_precomp.shape) == (V, int(means3D.size(0)), 3)):
-                raise RuntimeError("run_views: colors_precomp must be a contiguous float32 GPU tensor [V,P,3]")
-        else:
-            params["sh"] = shs
-        M = 0 if precomp else int(shs.size(1))
-        # dL_dsh level-major (FlatGradients(level_major=True)): .grad is the [P, M, 3] view of M planes, strides (3, plane, 1)
-        dsh_plane = 0
-        if not precomp and shs.grad is not None and not shs.grad.is_contiguous():
-            st = shs.grad.stride()
-            if not (M == 16 and st[0] == 3 and st[2] == 1 and st[1] >= 3 * int(shs.size(0)) and st[1] % 4 == 0 and shs.grad.data_ptr() % 16 == 0):
-                raise RuntimeError("run_views: shs.grad must be contiguous, or the level-major view FlatGradients(level_major=True) makes of a [P,16,3] parameter")
-            dsh_plane = int(st[1])
-        for name, t in params.items():
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.is_leaf and t.grad is not None and
-                    (t.grad.is_contiguous() or (name == "sh" and dsh_plane))):
-                raise RuntimeError(f"run_views: {name} must be a contiguous float32 leaf parameter on the GPU with an allocated .grad (see FlatGradients)")
-        cap = self.capacity()
-        tcap = self.tile_capacity()
+        c = _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_batch, upstream_view, colors_precomp, grad_chunks)
+        V, P, D, M, precomp = c.V, c.P, c.D, c.M, c.precomp
         dev = means3D.device
-        n_chunks = max(1, min(int(grad_chunks), (P + 255) // 256))
-        per = ((P + n_chunks - 1) // n_chunks + 255) // 256 * 256
-        ranges = [(first, min(per, P - first)) for first in range(0, P, per)]      # the same on every rank: multiples of 256 Gaussians
-
-        def per_view_fallback(idx: Sequence[int], dL):
-            # synchronous forward + in-place backward through the general path (first batch, rejected views, cooldown)
-            e = torch.Tensor([])
-            out = {}
-            for v in idx:
-                rs = settings[v]
-                R, color, radii, geom, binning, img = _C.rasterize_gaussians(rs.bg, means3D.detach(), colors_precomp[v] if precomp else e, opacities.detach(),
-                                                                           scales.detach(), rotations.detach(), rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix,
-                                                                           rs.tanfovx, rs.tanfovy, H, W, e if precomp else shs.detach(), D, rs.campos,
-                                                                           rs.prefiltered, rs.debug, pruning=self._pruning)
-                out[v] = (R, color, radii, geom, binning, img)
-            return out
-
-        def per_view_backward(v, state, g):
-            rs = settings[v]
-            e = torch.Tensor([])
-            R, color, radii, geom, binning, img = state
-            into = dict(means3D=means3D.grad, opacities=opacities.grad, scales=scales.grad, rotations=rotations.grad)
-            if precomp:
-                gcol[v].zero_()
-                into["colors_precomp"] = gcol[v]             # per-view colours: their gradient is this view's alone
-            else:
-                # (the one-view kernel writes rows: with a level-major .grad this rare path -- first batch, a view rendered again -- goes through a row-major temporary)
-                into["sh"] = torch.zeros_like(shs) if dsh_plane else shs.grad
-            g2 = _C.rasterize_gaussians_backward_accumulate(rs.bg, means3D.detach(), radii, colors_precomp[v] if precomp else e, scales.detach(),
-                                                            rotations.detach(), rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, g,
-                                                            e if precomp else shs.detach(), D, rs.campos, geom, R, binning, img, rs.debug, into,
-                                                            deterministic=self._deterministic)
-            if dsh_plane and not precomp:
-                shs.grad.add_(into["sh"])
-            return g2
-
-        def grad_of(dL, v):
-            return dL if dL.dim() == 3 else dL[v]
-
-        gcol = torch.empty((V, P, 3), dtype=torch.float32, device=dev) if (precomp and cap is None) else None
+        cap = self.capacity()
         if cap is None:                                     # no bound yet (or cooling down after an LDS-sort overflow): synchronous frames
             if not accumulate:
-                for t in params.values():
+                for t in c.params.values():
                     t.grad.zero_()
-            states = per_view_fallback(range(V), None)
-            images = torch.stack([states[v][1] for v in range(V)])
-            dL = upstream_batch(images)
-            g2d = [per_view_backward(v, states[v], grad_of(dL, v)) for v in range(V)]
-            self.viewspace_grads = torch.stack(g2d)
+            states = [self._render_view(c, v) for v in range(V)]
+            images = torch.stack([s[1] for s in states])
+            dL = upstream_batch(images) if upstream_batch is not None else torch.stack([upstream_view(v, images[v]) for v in range(V)])
+            gcol = torch.empty((V, P, 3), dtype=torch.float32, device=dev) if precomp else None
+            scratch = torch.empty_like(shs) if c.dsh_plane else None
+            self.viewspace_grads = torch.stack([self._backward_view(c, v, states[v], _of_view(dL, v), gcol, scratch) for v in range(V)])
             self.color_grads = gcol
-            seen = max(states[v][0] for v in range(V))
-            if self._cooldown > 0:
-                self._cooldown -= 1
-            self.bound = seen if self.bound is None else max(seen, int(self.bound * 0.95))
-            for first, count in (ranges if on_chunk is not None else []):
+            self._learn(max(s[0] for s in states))
+            for first, count in (c.ranges if on_chunk is not None else []):
                 on_chunk(first, count)
             return images
 
-        # ---- pooled state: one tensor per kind for all views, reused from step to step
-        key = (P, H, W, V, M, cap, dev, precomp)
-        if self._pool is None or self._pool["key"] != key:
-            gb, bb, ib = _C.state_sizes(P, W, H, not precomp, True, cap)
-            al = lambda n: (n + 255) // 256 * 256
-            z = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
-            self._pool = dict(key=key, images=z(V, 3, H, W), radii=z(V, P, dt=torch.int32), g2d=z(V, P, 3), geom=z(V, al(gb), dt=torch.uint8),
-                              binning=z(V, al(bb), dt=torch.uint8), img=z(V, al(ib), dt=torch.uint8), sizes=(gb, bb, ib), arr=_C.ViewArray(V),
-                              gcol=z(V, P, 3) if precomp else None,
-                              host=torch.empty((V, _C.META_BYTES), dtype=torch.uint8, pin_memory=True))
-        pool = self._pool
-        gcol = pool["gcol"]
-        arr = pool["arr"]
-        gb, bb, ib = pool["sizes"]
-        for v, rs in enumerate(settings):
-            if (int(rs.image_height), int(rs.image_width), int(rs.sh_degree)) != (H, W, D) or rs.scale_modifier != rs0.scale_modifier or \
-                    bool(rs.prefiltered) != bool(rs0.prefiltered):
-                raise RuntimeError("run_views: all views of a batch share image size, SH degree, scale modifier and the prefiltered flag")
-            a = arr[v]
-            a.width, a.height, a.tan_fovx, a.tan_fovy = W, H, float(rs.tanfovx), float(rs.tanfovy)
-            a.viewmatrix, a.projmatrix, a.campos, a.background = rs.viewmatrix.data_ptr(), rs.projmatrix.data_ptr(), rs.campos.data_ptr(), rs.bg.data_ptr()
-            a.radii = a.radii_out = pool["radii"][v].data_ptr()
-            a.geom_buffer, a.binning_buffer, a.img_buffer = pool["geom"][v].data_ptr(), pool["binning"][v].data_ptr(), pool["img"][v].data_ptr()
-            a.geom_bytes, a.binning_bytes, a.img_bytes = gb, bb, ib
-            a.out_color, a.dL_dmean2D, a.dL_dpix = pool["images"][v].data_ptr(), pool["g2d"][v].data_ptr(), None
-            a.dL_dcolor = gcol[v].data_ptr() if precomp else None
-            a.colors_precomp = colors_precomp[v].data_ptr() if precomp else None
-            a.host_meta = pool["host"][v].data_ptr()        # k_scan writes the frame's Meta record here itself: no device-to-host copy in the stream
-            a.tile_bound = tcap
-            # (generous: the class counts move more from view to view than the number of tiles with instances does, and a miss costs a frame)
-            a.heavy_bound, a.mid_bound = ((int(self.class_bound[0] * 1.5) + 64) // 32 * 32, (int(self.class_bound[1] * 1.3) + 128) // 64 * 64) if tcap else (0, 0)
+        pool = self._pooled(c, cap)
+        self._fill_views(c, pool)
+        arr, images, gcol = pool["arr"], pool["images"], pool["gcol"]
         main = torch.cuda.current_stream(dev)
-        side = self._side.setdefault(dev, [])
-        n_lanes = max(1, min(self.streams, V))
-        while len(side) < n_lanes - 1:
-            side.append(torch.cuda.Stream(device=dev))
-        lanes = [main] + side[:n_lanes - 1]
-        handles = [st.cuda_stream for st in lanes]
-
-        def fork():
-            ev = torch.cuda.Event()
-            ev.record(main)
-            for st in lanes[1:]:
-                st.wait_event(ev)
-
-        def join():
-            for st in lanes[1:]:
-                ev = torch.cuda.Event()
-                ev.record(st)
-                main.wait_event(ev)
-
-        def check(dL):
-            if dL.dtype != torch.float32 or not dL.is_cuda or dL.shape[-3:] != pool["images"].shape[-3:]:
-                raise RuntimeError("upstream must return a float32 GPU tensor [V,3,H,W] or [3,H,W]")
-            return dL.contiguous()
-
+        lanes = _lanes(main, min(self.streams, V))
         with torch.cuda.device(dev):
-            split = self.split and upstream_view is not None and n_lanes >= 4
-            bin_lanes, ren_lanes = (lanes[:n_lanes // 2], lanes[n_lanes // 2:]) if split else (lanes, lanes)
-            fork()
+            split = self.split and upstream_view is not None and len(lanes) >= 4
+            bin_lanes, ren_lanes = (lanes[:len(lanes) // 2], lanes[len(lanes) // 2:]) if split else (lanes, lanes)
+            _fork(lanes)
             _C.set_render_streams([st.cuda_stream for st in ren_lanes] if split else [])
             try:
                 _C.forward_views([st.cuda_stream for st in bin_lanes], cap, P, D, M, means3D.data_ptr(), None if precomp else shs.data_ptr(), opacities.data_ptr(),
-                                 scales.data_ptr(), rs0.scale_modifier, rotations.data_ptr(), arr, V, prefiltered=rs0.prefiltered, opt=self.options)
+                                 scales.data_ptr(), settings[0].scale_modifier, rotations.data_ptr(), arr, V, prefiltered=settings[0].prefiltered, opt=self.options)
             finally:
                 _C.set_render_streams([])
-            images = pool["images"]
             if upstream_view is None:
-                join()
+                _join(lanes)
                 ready = [torch.cuda.Event()]                # (the verdicts are in pinned memory once the scans have run: tgs_view_t.host_meta)
                 ready[0].record(main)
-                dL = check(upstream_batch(images))
+                dL = _upstream_checked(upstream_batch(images), c)
                 for v in range(V):
-                    arr[v].dL_dpix = grad_of(dL, v).data_ptr()
-                fork()
+                    arr[v].dL_dpix = _of_view(dL, v).data_ptr()
+                _fork(lanes)
             else:
                 # every lane: the verdicts of its views leave for the host, then loss and backward of each view follow on the same stream
                 ready, dLs = [], []
-                for l, st in enumerate(bin_lanes):
+                for st in bin_lanes:
                     with torch.cuda.stream(st):
                         ev = torch.cuda.Event()             # behind the lane's forwards: their scans have written the verdicts to pinned memory
                         ev.record(st)
@@ -647,67 +631,113 @@ class SyncFreeBatch:
                 for l, st in enumerate(ren_lanes):
                     with torch.cuda.stream(st):
                         for v in range(l, V, len(ren_lanes)):
-                            g = check(upstream_view(v, images[v]))
+                            g = _upstream_checked(upstream_view(v, images[v]), c)
                             if g.dim() != 3:
                                 raise RuntimeError("upstream_view must return [3,H,W]")
                             g.record_stream(st)
                             dLs.append((v, g))
-                dL = torch.empty(0)
                 for v, g in dLs:
                     arr[v].dL_dpix = g.data_ptr()
                 self._keep = dLs                                 # (alive until the next batch)
-            bw_handles = [st.cuda_stream for st in ren_lanes] if upstream_view is not None else handles
-            _C.backward_render_views(bw_handles, P, arr, V, opt=self.options)
-            join()
-            def verdict():
-                """waits for the Meta records (the one host wait of the batch: they left right behind the forwards) -> (views to render again, largest count)"""
-                for ev in ready:
-                    ev.synchronize()
-                seen, redo, tiles, heavy_seen, mid_seen = 0, [], 0, 0, 0
-                for v in range(V):
-                    R, flags, _longest, n_overflow = _C.decode_meta_full(pool["host"][v])
-                    if flags & _C.FRAME_PREFILTERED:
-                        raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-                    if flags & _C.FRAME_REJECTED:
-                        redo.append(v)
-                    seen = max(seen, R)
-                    n_t, n_heavy, n_mid = _C.decode_meta_tiles(pool["host"][v])
-                    tiles, heavy_seen, mid_seen = max(tiles, n_t), max(heavy_seen, n_heavy), max(mid_seen, n_mid)
-                self.tile_bound = tiles if self.tile_bound is None else max(tiles, int(self.tile_bound * 0.95))
-                self.class_bound = [max(heavy_seen, int(self.class_bound[0] * 0.95)), max(mid_seen, int(self.class_bound[1] * 0.95))]
-                return redo, seen
-
+            _C.backward_render_views([st.cuda_stream for st in (lanes if upstream_view is None else ren_lanes)], P, arr, V, opt=self.options)
+            _join(lanes)
             # With on_chunk the verdict is read BEFORE the per-Gaussian pass is enqueued (the GPU still has the per-pixel backwards in its
             # queues): a range may only be handed out as final when no view has to be rendered again.
-            known = verdict() if on_chunk is not None else None
-            eager = known is not None and not known[0]
+            rows = _read_verdicts(ready, pool["host"]) if on_chunk is not None else None
+            eager = rows is not None and not any(rejected for _R, rejected, _tiles in rows)
             # the one per-Gaussian pass of the step, range by range: a range's gradients are final behind its launch
-            for g0, gcount in ranges:
+            for g0, gcount in c.ranges:
                 _C.backward_batch_raw(main.cuda_stream, P, D, M, arr, V, means3D.data_ptr(), None if precomp else shs.data_ptr(), scales.data_ptr(),
-                                      rs0.scale_modifier, rotations.data_ptr(), opacities.grad.data_ptr(), means3D.grad.data_ptr(),
+                                      settings[0].scale_modifier, rotations.data_ptr(), opacities.grad.data_ptr(), means3D.grad.data_ptr(),
                                       None if precomp else shs.grad.data_ptr(), scales.grad.data_ptr(), rotations.grad.data_ptr(), accumulate, g0, gcount,
-                                      dsh_plane_stride=dsh_plane)
+                                      dsh_plane_stride=c.dsh_plane)
                 if eager:
                     on_chunk(g0, gcount)
         self.viewspace_grads = pool["g2d"]
         self.color_grads = gcol
-        if self._cooldown > 0:
-            self._cooldown -= 1
-        redo, seen = known if known is not None else verdict()
+        if rows is None:
+            rows = _read_verdicts(ready, pool["host"])
+        seen = max(R for R, _rejected, _tiles in rows)
+        redo = [v for v, (_R, rejected, _tiles) in enumerate(rows) if rejected]
         if redo:
             self.rejected += len(redo)
-            states = per_view_fallback(redo, dL)
+            states = {v: self._render_view(c, v) for v in redo}
             for v in redo:
                 images[v].copy_(states[v][1])
             dL2 = upstream_batch(images).contiguous() if upstream_view is None else None    # the gradient images depend on the re-rendered frames
+            scratch = torch.empty_like(shs) if c.dsh_plane else None
             for v in redo:
-                pool["g2d"][v].copy_(per_view_backward(v, states[v], grad_of(dL2, v) if dL2 is not None else check(upstream_view(v, images[v]))))
+                g = _of_view(dL2, v) if dL2 is not None else _upstream_checked(upstream_view(v, images[v]), c)
+                pool["g2d"][v].copy_(self._backward_view(c, v, states[v], g, gcol, scratch))
                 seen = max(seen, states[v][0])
         if on_chunk is not None and not eager:
-            for first, count in ranges:     # the same calls in the same order as on a rank that had nothing to render again (collectives must pair up)
+            for first, count in c.ranges:     # the same calls in the same order as on a rank that had nothing to render again (collectives must pair up)
                 on_chunk(first, count)
-        self.bound = max(seen, int(self.bound * 0.95))
+        self._learn(seen, [max(counts) for counts in zip(*(tiles for _R, _rejected, tiles in rows))])
         return images
+
+    def _pooled(self, c: _Call, cap: int) -> dict:
+        """The batch's buffers, one tensor per kind for all views, and its tgs_view_t array: kept while the shapes and the capacity stay."""
+        dev = c.params["means3D"].device
+        key = (c.P, c.H, c.W, c.V, c.M, cap, dev, c.precomp)
+        if self._pool is None or self._pool["key"] != key:
+            V, P = c.V, c.P
+            gb, bb, ib = _C.state_sizes(P, c.W, c.H, not c.precomp, True, cap)
+            al = lambda n: (n + 255) // 256 * 256
+            z = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
+            self._pool = dict(key=key, images=z(V, 3, c.H, c.W), radii=z(V, P, dt=torch.int32), g2d=z(V, P, 3), geom=z(V, al(gb), dt=torch.uint8),
+                              binning=z(V, al(bb), dt=torch.uint8), img=z(V, al(ib), dt=torch.uint8), sizes=(gb, bb, ib), arr=_C.ViewArray(V),
+                              gcol=z(V, P, 3) if c.precomp else None,
+                              host=torch.empty((V, _C.META_BYTES), dtype=torch.uint8, pin_memory=True))
+        return self._pool
+
+    def _fill_views(self, c: _Call, pool: dict) -> None:
+        """The pooled tgs_view_t array: each view's camera, its slices of the pooled buffers and its grid bounds (dL_dpix comes later)."""
+        gb, bb, ib = pool["sizes"]
+        tcap = self.tile_capacity()
+        # (generous: the class counts move more from view to view than the number of tiles with instances does, and a miss costs a frame)
+        heavy, mid = ((int(self.class_bound[0] * 1.5) + 64) // 32 * 32, (int(self.class_bound[1] * 1.3) + 128) // 64 * 64) if tcap else (0, 0)
+        for v, rs in enumerate(c.settings):
+            a = pool["arr"][v]
+            a.width, a.height, a.tan_fovx, a.tan_fovy = c.W, c.H, float(rs.tanfovx), float(rs.tanfovy)
+            a.viewmatrix, a.projmatrix, a.campos, a.background = rs.viewmatrix.data_ptr(), rs.projmatrix.data_ptr(), rs.campos.data_ptr(), rs.bg.data_ptr()
+            a.radii = a.radii_out = pool["radii"][v].data_ptr()
+            a.geom_buffer, a.binning_buffer, a.img_buffer = pool["geom"][v].data_ptr(), pool["binning"][v].data_ptr(), pool["img"][v].data_ptr()
+            a.geom_bytes, a.binning_bytes, a.img_bytes = gb, bb, ib
+            a.out_color, a.dL_dmean2D, a.dL_dpix = pool["images"][v].data_ptr(), pool["g2d"][v].data_ptr(), None
+            a.dL_dcolor = pool["gcol"][v].data_ptr() if c.precomp else None
+            a.colors_precomp = c.colors[v].data_ptr() if c.precomp else None
+            a.host_meta = pool["host"][v].data_ptr()        # k_scan writes the frame's Meta record here itself: no device-to-host copy in the stream
+            a.tile_bound = tcap
+            a.heavy_bound, a.mid_bound = heavy, mid
+
+    def _render_view(self, c: _Call, v: int) -> tuple:
+        """View v through the synchronous forward, buffers sized from the true count: (R, color, radii, geom, binning, img)."""
+        rs, p, e = c.settings[v], c.params, torch.Tensor([])
+        return _C.rasterize_gaussians(rs.bg, p["means3D"].detach(), c.colors[v] if c.precomp else e, p["opacities"].detach(), p["scales"].detach(),
+                                      p["rotations"].detach(), rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, c.H, c.W,
+                                      e if c.precomp else p["sh"].detach(), c.D, rs.campos, rs.prefiltered, rs.debug, pruning=self._pruning)
+
+    def _backward_view(self, c: _Call, v: int, state: tuple, dL: torch.Tensor, gcol: Optional[torch.Tensor],
+                       scratch: Optional[torch.Tensor]) -> torch.Tensor:
+        """The backward of a view from _render_view, in place: adds into the parameters' .grad (per-view colours: this view's alone, in gcol[v])
+        and returns dL/d means2D.  The one-view kernel writes dL_dsh by rows: a level-major .grad gets it through the row-major ``scratch``."""
+        rs, p, e = c.settings[v], c.params, torch.Tensor([])
+        R, _color, radii, geom, binning, img = state
+        into = {name: t.grad for name, t in p.items()}
+        if c.precomp:
+            gcol[v].zero_()
+            into["colors_precomp"] = gcol[v]
+        elif scratch is not None:
+            scratch.zero_()
+            into["sh"] = scratch
+        g2 = _C.rasterize_gaussians_backward_accumulate(rs.bg, p["means3D"].detach(), radii, c.colors[v] if c.precomp else e, p["scales"].detach(),
+                                                        p["rotations"].detach(), rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
+                                                        dL, e if c.precomp else p["sh"].detach(), c.D, rs.campos, geom, R, binning, img, rs.debug, into,
+                                                        deterministic=self._deterministic)
+        if scratch is not None:
+            p["sh"].grad.add_(scratch)
+        return g2
 
     def run(self, views: Iterable[int], rasterize: Callable, upstream: Callable[[int, torch.Tensor], torch.Tensor]) -> List[torch.Tensor]:
         """Renders and back-propagates ``views``; returns their images.
@@ -718,7 +748,6 @@ class SyncFreeBatch:
         pass at the end (``DeferredBackward``), so the streams never wait for each other.  Without it the backwards are
         chained by events, because each adds into the same gradient buffers.  The calling stream waits for everything
         before ``run`` returns."""
-        from .diff_gaussian_rasterization import _C
         views = list(views)
         images: List[torch.Tensor] = []
         metas: List[torch.Tensor] = []
@@ -726,31 +755,22 @@ class SyncFreeBatch:
         if not views:
             return images
         main = torch.cuda.current_stream()
-        lanes = [main]
-        if self.streams > 1 and cap is not None and len(views) > 1:
-            key = main.device
-            side = self._side.setdefault(key, [])
-            while len(side) < min(self.streams, len(views)) - 1:
-                side.append(torch.cuda.Stream(device=key))
-            lanes += side[:min(self.streams, len(views)) - 1]
-            start = torch.cuda.Event()
-            start.record(main)
-            for st in lanes[1:]:
-                st.wait_event(start)                        # whatever the caller enqueued before (e.g. zeroing the gradients)
+        lanes = _lanes(main, min(self.streams, len(views)) if cap is not None else 1)
+        if len(lanes) > 1:
+            _fork(lanes)                                    # whatever the caller enqueued before (e.g. zeroing the gradients)
         ready = None
         fwd_done = [None] * len(lanes)
         prev_bwd = None
-        global _collector
         collector = DeferredBackward() if (self.deferred and cap is not None) else None
         last_on_lane = [None] * len(lanes)
         for k, v in enumerate(views):
             st = lanes[k % len(lanes)]
             with torch.cuda.stream(st):
-                _collector = collector                      # picked up by rasterize_accumulate's forward
+                _collector.batch = collector                # picked up by rasterize_accumulate's forward
                 try:
                     img, _radii, meta = rasterize(v, cap)
                 finally:
-                    _collector = None
+                    _collector.batch = None
                 metas.append(meta)
                 if len(lanes) > 1:
                     fwd_done[k % len(lanes)] = torch.cuda.Event()
@@ -786,22 +806,15 @@ class SyncFreeBatch:
                     main.wait_event(ev)                     # chained backwards: the last one is behind every other kernel of the batch
         if collector is not None:
             collector.finish()                              # the per-Gaussian half of every view, one pass, on the calling stream
-        ready.synchronize()                                 # the one host wait of the batch
-        host = self._host
+        rows = _read_verdicts([ready], self._host)          # the one host wait of the batch
         seen = 0
-        if self._cooldown > 0:
-            self._cooldown -= 1
-        for i, v in enumerate(views):
-            R, flags, _longest, n_overflow = _C.decode_meta_full(host[i])
-            # (a tile list longer than the LDS sort is no reason to reject a frame any more: k_tile_sort's overflow workers sort it on the device)
-            if flags & _C.FRAME_PREFILTERED:
-                raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-            if flags & _C.FRAME_REJECTED:
+        for i, (v, (R, rejected, _tiles)) in enumerate(zip(views, rows)):
+            if rejected:
                 self.rejected += 1
                 img, _radii, meta = rasterize(v, None)      # synchronous forward: sizes its buffers from the true count
                 img.backward(upstream(v, img.detach()))
                 images[i] = img.detach()
                 R, _ = _C.decode_meta(meta)
             seen = max(seen, R)
-        self.bound = seen if self.bound is None else max(seen, int(self.bound * 0.95))
+        self._learn(seen)
         return images
