@@ -206,3 +206,413 @@ def test_compiled_extension_rejects_cpu_tensors_loudly():
         _C.rasterize_gaussians(z, torch.zeros(5, 3), z, z, z, z, 1.0, z, z, z, 1.0, 1.0, 4, 4, z, 0, z, False, False)
     with pytest.raises(RuntimeError, match="no CPU path"):
         _C.mark_visible(torch.zeros(5, 3), torch.eye(4), torch.eye(4))
+
+
+# ---- rejection table: every error the host layer (csrc/tgs_api.hip) returns BEFORE its first HIP call -- code, message text and which
+# error wins when several apply.  Fake non-NULL pointers (nothing is dereferenced on these paths), a recording allocation callback that
+# returns NULL.  No case goes on past a check: what needs a device to be told apart (e.g. that tgs_backward_opt ACCEPTS a NULL dL_dconic,
+# or that tgs_backward checks neither background nor the camera pointers) is left to the GPU suite.
+X = 4096                                    # a fake device pointer
+INVALID, ALLOC = -1, -3
+MSG_COLOR = "provide exactly one of shs / colors_precomp"
+MSG_SR = "provide exactly one of (scales, rotations) / cov3D_precomp"
+MSG_NULL = "NULL required pointer"
+MSG_VIEW = "view %d: bad sizes or NULL required pointer"
+BIG = 16 * 65536                            # 65536 tiles across: one more than a launch grid takes
+_vp, _it, _i64, _fl, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
+_ALLOC = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t)
+
+
+class _View(ctypes.Structure):              # tgs_view_t
+    _fields_ = [("width", _it), ("height", _it), ("tan_fovx", _fl), ("tan_fovy", _fl), ("viewmatrix", _vp), ("projmatrix", _vp), ("campos", _vp),
+                ("radii", _vp), ("geom_buffer", _vp), ("binning_buffer", _vp), ("img_buffer", _vp), ("R", _i64), ("dL_dmean2D", _vp), ("dL_dcolor", _vp),
+                ("background", _vp), ("out_color", _vp), ("radii_out", _vp), ("dL_dpix", _vp), ("geom_bytes", _sz), ("binning_bytes", _sz),
+                ("img_bytes", _sz), ("colors_precomp", _vp), ("tile_bound", _i64), ("heavy_bound", _i64), ("mid_bound", _i64), ("host_meta", _vp)]
+
+
+class _Options(ctypes.Structure):           # tgs_options_t
+    _fields_ = [("struct_size", ctypes.c_uint32), ("instance_pruning", ctypes.c_int32), ("deterministic", ctypes.c_int32), ("forward_group", ctypes.c_int32),
+                ("sort_lds_cap", ctypes.c_uint32), ("tile_bound", _i64), ("heavy_bound", _i64), ("mid_bound", _i64), ("light_tiles", ctypes.c_int32)]
+
+
+class _FrameInfo(ctypes.Structure):         # tgs_frame_info_t
+    _fields_ = [("num_rendered", _i64), ("nonempty_tiles", _i64), ("flags", ctypes.c_int32), ("mid_tiles", ctypes.c_int32)]
+
+
+FWD = dict(alloc=None, alloc_ctx=None, stream=None, P=10, D=0, M=0, background=X, width=64, height=64, means3D=X, shs=None, colors_precomp=X, opacities=X,
+           scales=X, scale_modifier=1.0, rotations=X, cov3D_precomp=None, viewmatrix=X, projmatrix=X, cam_pos=X, tan_fovx=1.0, tan_fovy=1.0, prefiltered=0,
+           out_color=X, radii=X, debug=0)
+FWD_TYPES = [_vp, _vp, _vp, _it, _it, _it, _vp, _it, _it, _vp, _vp, _vp, _vp, _vp, _fl, _vp, _vp, _vp, _vp, _vp, _fl, _fl, _it, _vp, _vp, _it]
+BWD = dict(stream=None, P=10, D=0, M=0, R=5, background=X, width=64, height=64, means3D=X, shs=None, colors_precomp=X, scales=X, scale_modifier=1.0,
+           rotations=X, cov3D_precomp=None, viewmatrix=X, projmatrix=X, campos=X, tan_fovx=1.0, tan_fovy=1.0, radii=X, geom_buffer=X, binning_buffer=X,
+           img_buffer=X, dL_dpix=X, dL_dmean2D=X, dL_dconic=X, dL_dopacity=X, dL_dcolor=X, dL_dmean3D=X, dL_dcov3D=X, dL_dsh=X, dL_dscale=X, dL_drot=X, debug=0)
+BWD_TYPES = [_vp, _it, _it, _it, _i64, _vp, _it, _it, _vp, _vp, _vp, _vp, _fl, _vp, _vp, _vp, _vp, _vp, _fl, _fl] + [_vp] * 14 + [_it]
+FVIEWS = dict(streams=None, n_streams=1, r_capacity=100, P=10, D=0, M=0, means3D=X, shs=None, colors_precomp=X, opacities=X, scales=X, scale_modifier=1.0,
+              rotations=X, cov3D_precomp=None, prefiltered=0, n_views=0, views=None)
+FVIEWS_TYPES = [_vp, _it, _i64, _it, _it, _it, _vp, _vp, _vp, _vp, _vp, _fl, _vp, _vp, _it, _it, _vp]
+BATCH = dict(stream=None, P=1000, D=0, M=0, n_views=0, views=None, means3D=X, shs=None, scales=X, scale_modifier=1.0, rotations=X, cov3D_precomp=None,
+             dL_dopacity=X, dL_dmean3D=X, dL_dcov3D=None, dL_dsh=None, dL_dscale=X, dL_drot=X, accumulate=0)
+BATCH_TYPES = [_vp, _it, _it, _it, _it, _vp, _vp, _vp, _vp, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _it]
+SH = dict(shs=X, colors_precomp=None, D=3, M=16)        # forward / backward on the SH path
+COV = dict(scales=None, rotations=None, cov3D_precomp=X)
+
+
+def _args(base, over):
+    assert not set(over) - set(base), set(over) - set(base)
+    return tuple({**base, **over}.values())
+
+
+@pytest.fixture(scope="module")
+def abi():
+    os.environ.pop("TGS_FORWARD_GROUP", None)           # (read once by tgs_forward_views_opt; the table passes forward_group explicitly)
+    lib = ctypes.CDLL(lib_path())
+    lib.tgs_last_error.restype = ctypes.c_char_p
+    for name, res, types in (
+            ("tgs_forward", _i64, FWD_TYPES), ("tgs_forward_opt", _i64, [_vp, _it, _i64, _vp] + FWD_TYPES), ("tgs_forward_async", _i64, [_i64] + FWD_TYPES),
+            ("tgs_forward_speculative", _i64, [_i64, _vp] + FWD_TYPES), ("tgs_backward", _it, BWD_TYPES), ("tgs_backward_accumulate", _it, BWD_TYPES),
+            ("tgs_backward_opt", _it, [_vp, _it] + BWD_TYPES), ("tgs_forward_views", _it, FVIEWS_TYPES), ("tgs_forward_views_opt", _it, [_vp] + FVIEWS_TYPES),
+            ("tgs_backward_render", _it, [_vp, _it, _i64, _vp, _it, _it, _vp, _vp, _vp]),
+            ("tgs_backward_render_opt", _it, [_vp, _vp, _it, _i64, _vp, _it, _it, _vp, _vp, _vp]),
+            ("tgs_backward_render_views", _it, [_vp, _it, _it, _it, _vp]), ("tgs_backward_render_views_opt", _it, [_vp, _vp, _it, _it, _it, _vp]),
+            ("tgs_backward_batch", _it, BATCH_TYPES), ("tgs_backward_batch_range", _it, BATCH_TYPES + [_it, _it]),
+            ("tgs_backward_batch_range_planes", _it, BATCH_TYPES + [_it, _it, _i64]), ("tgs_frame_status", _it, [_vp, _vp, _vp, _vp]),
+            ("tgs_mark_visible", _it, [_vp, _it, _vp, _vp, _vp, _vp]),
+            ("tgs_state_field", _i64, [_vp, ctypes.c_char_p, _it, _it, _it, _i64, _it, _it, _vp, _vp, _vp, _vp, _sz]),
+            ("tgs_state_sizes", None, [_it, _it, _it, _it, _it, _i64, ctypes.POINTER(_sz)])):
+        getattr(lib, name).restype, getattr(lib, name).argtypes = res, types
+    return lib
+
+
+def _sizes(lib, P, W, H, has_sh, has_sr, r=0):
+    out = (_sz * 3)()
+    lib.tgs_state_sizes(P, W, H, int(has_sh), int(has_sr), r, out)
+    return out[0], out[1], out[2]
+
+
+def _check(lib, failures, label, got, code, text):
+    """One row: return code and the WHOLE message."""
+    m = (lib.tgs_last_error() or b"").decode()
+    if got != code or (text is not None and m != text):
+        failures.append(f"{label}: got {got} {m!r}, expected {code} {text!r}")
+
+
+# (label, overrides of FWD, code, message, allocations seen: None = none, "state" = geometry then image with tgs_state_sizes' bytes)
+FORWARD_TABLE = [
+    ("alloc NULL", dict(alloc=None), INVALID, "alloc callback is NULL", None),
+    ("alloc NULL wins over every model error", dict(alloc=None, P=-1, colors_precomp=None, means3D=None), INVALID, "alloc callback is NULL", None),
+    ("P < 0", dict(P=-1), INVALID, "bad sizes P=-1 W=64 H=64", None),
+    ("W == 0", dict(width=0), INVALID, "bad sizes P=10 W=0 H=64", None),
+    ("H < 0", dict(height=-2), INVALID, "bad sizes P=10 W=64 H=-2", None),
+    ("sizes win over colours", dict(width=0, colors_precomp=None), INVALID, "bad sizes P=10 W=0 H=64", None),
+    ("P == 0 needs out_color only", dict(P=0, out_color=None, means3D=None, colors_precomp=None, scales=None), INVALID, MSG_NULL, None),
+    ("no colours", dict(colors_precomp=None), INVALID, MSG_COLOR, None),
+    ("both colours", dict(shs=X, D=0, M=1), INVALID, MSG_COLOR, None),
+    ("colours win over scales", dict(colors_precomp=None, scales=None), INVALID, MSG_COLOR, None),
+    ("scales, rotations and cov3D", dict(cov3D_precomp=X), INVALID, MSG_SR, None),
+    ("none of scales, rotations, cov3D", dict(scales=None, rotations=None), INVALID, MSG_SR, None),
+    ("scales without rotations", dict(rotations=None), INVALID, MSG_SR, None),
+    ("rotations without scales", dict(scales=None), INVALID, MSG_SR, None),
+    ("scales without rotations, with cov3D", dict(rotations=None, cov3D_precomp=X), INVALID, MSG_SR, None),
+    ("rotations without scales, with cov3D", dict(scales=None, cov3D_precomp=X), INVALID, MSG_SR, None),
+    ("scales win over SH degree", dict(SH, D=4, cov3D_precomp=X), INVALID, MSG_SR, None),
+    ("D > 3", dict(SH, D=4, M=25), INVALID, "SH degree 4 needs M >= 25 (M=25)", None),
+    ("D < 0", dict(SH, D=-1), INVALID, "SH degree -1 needs M >= 0 (M=16)", None),
+    ("M too small", dict(SH, M=9), INVALID, "SH degree 3 needs M >= 16 (M=9)", None),
+    ("M too small, D = 1", dict(SH, D=1, M=3), INVALID, "SH degree 1 needs M >= 4 (M=3)", None),
+    ("SH degree wins over NULL pointers", dict(SH, M=9, means3D=None), INVALID, "SH degree 3 needs M >= 16 (M=9)", None),
+] + [(f"{p} NULL", {p: None}, INVALID, MSG_NULL, None) for p in ("background", "means3D", "opacities", "viewmatrix", "projmatrix", "cam_pos", "out_color")] + [
+    ("NULL pointer wins over image size", dict(width=BIG, opacities=None), INVALID, MSG_NULL, None),
+    ("image too wide", dict(width=BIG, height=16), INVALID, "image too large", None),
+    ("image too high", dict(width=16, height=BIG), INVALID, "image too large", None),
+    ("allocation fails", dict(), ALLOC, "state buffer allocation failed", "state"),
+    ("allocation fails, SH + cov3D", dict(SH, **COV), ALLOC, "state buffer allocation failed", "state"),
+    ("allocation fails, SH", dict(SH, M=20), ALLOC, "state buffer allocation failed", "state"),
+    ("allocation fails, cov3D, widest image", dict(COV, width=BIG - 16, height=16), ALLOC, "state buffer allocation failed", "state"),
+    ("D and M are only read with shs; radii may be NULL", dict(D=7, M=-1, radii=None), ALLOC, "state buffer allocation failed", "state"),
+]
+
+
+def test_forward_rejections(abi):
+    """tgs_forward, tgs_forward_opt in its three modes, tgs_forward_async, tgs_forward_speculative: the same checks in the same order, and
+    the first two allocations are TGS_BUF_GEOM then TGS_BUF_IMAGE with exactly tgs_state_sizes' bytes."""
+    lib, failures, seen = abi, [], []
+    rec = _ALLOC(lambda _ctx, which, nbytes: seen.append((which, nbytes)))          # (returns None: NULL)
+    nr, info = _i64(7), _FrameInfo()
+    entries = [("tgs_forward", lambda a: lib.tgs_forward(*a)), ("tgs_forward_async", lambda a: lib.tgs_forward_async(100, *a)),
+               ("tgs_forward_speculative", lambda a: lib.tgs_forward_speculative(100, ctypes.byref(nr), *a)),
+               ("opt sync", lambda a: lib.tgs_forward_opt(None, 0, 1 << 40, ctypes.byref(info), *a)),          # (r is ignored in this mode)
+               ("opt async", lambda a: lib.tgs_forward_opt(None, 1, 100, ctypes.byref(info), *a)),
+               ("opt speculative", lambda a: lib.tgs_forward_opt(None, 2, 0, ctypes.byref(info), *a))]
+    assert _sizes(lib, 10, 64, 64, False, True)[::2] == (2824, 52736)
+    for ename, call in entries:
+        for label, over, code, text, allocs in FORWARD_TABLE:
+            a = {**FWD, "alloc": ctypes.cast(rec, _vp), **over}
+            del seen[:]
+            nr.value, info.num_rendered, info.nonempty_tiles, info.flags, info.mid_tiles = 7, 7, 7, 7, 7
+            _check(lib, failures, f"{ename}: {label}", call(tuple(a.values())), code, text)
+            g, _b, i = _sizes(lib, a["P"], a["width"], a["height"], a["shs"] is not None, a["scales"] is not None)
+            want = [] if allocs is None else [(0, g), (2, i)]
+            if seen != want:
+                failures.append(f"{ename}: {label}: allocations {seen}, expected {want}")
+            if ename.startswith("opt") and (info.num_rendered, info.nonempty_tiles, info.flags, info.mid_tiles) != (-1, -1, 0, -1):
+                failures.append(f"{ename}: {label}: frame info not reset")
+            if ename == "tgs_forward_speculative" and nr.value != 0:
+                failures.append(f"{ename}: {label}: *num_rendered not cleared")
+    # what the wrappers check themselves, before anything above
+    good, bad = _args(FWD, dict(alloc=ctypes.cast(rec, _vp))), _args(FWD, dict(alloc=None, P=-1))
+    del seen[:]
+    _check(lib, failures, "async r < 0", lib.tgs_forward_async(-5, *bad), INVALID, "r_capacity must be >= 0")
+    _check(lib, failures, "speculative r < 0", lib.tgs_forward_speculative(-1, ctypes.byref(nr), *bad), INVALID, "r_guess must be >= 0 and num_rendered non-NULL")
+    _check(lib, failures, "speculative num_rendered NULL", lib.tgs_forward_speculative(5, None, *bad), INVALID, "r_guess must be >= 0 and num_rendered non-NULL")
+    _check(lib, failures, "opt unknown mode", lib.tgs_forward_opt(None, 3, 5, None, *bad), INVALID, "tgs_forward_opt: unknown mode 3")
+    _check(lib, failures, "opt unknown mode < 0", lib.tgs_forward_opt(None, -1, -5, None, *bad), INVALID, "tgs_forward_opt: unknown mode -1")
+    _check(lib, failures, "opt async r < 0", lib.tgs_forward_opt(None, 1, -3, None, *bad), INVALID, "r_capacity / r_guess must be >= 0")
+    _check(lib, failures, "opt speculative r < 0", lib.tgs_forward_opt(None, 2, -1, None, *bad), INVALID, "r_capacity / r_guess must be >= 0")
+    _check(lib, failures, "opt sync ignores r < 0", lib.tgs_forward_opt(None, 0, -3, None, *bad), INVALID, "alloc callback is NULL")
+    for ename, call in (("async", lambda a: lib.tgs_forward_async(1 << 31, *a)), ("speculative", lambda a: lib.tgs_forward_speculative(1 << 31, ctypes.byref(nr), *a)),
+                        ("opt async", lambda a: lib.tgs_forward_opt(None, 1, 1 << 31, None, *a)), ("opt speculative", lambda a: lib.tgs_forward_opt(None, 2, 1 << 40, None, *a))):
+        _check(lib, failures, f"{ename}: r > 2^31-1 wins over alloc NULL", call(bad), INVALID, "r_capacity exceeds 2^31-1")
+        _check(lib, failures, f"{ename}: r > 2^31-1", call(good), INVALID, "r_capacity exceeds 2^31-1")
+    _check(lib, failures, "async: r == 2^31-1 is accepted", lib.tgs_forward_async((1 << 31) - 1, *good), ALLOC, "state buffer allocation failed")
+    if seen != [(0, 2824), (2, 52736)]:
+        failures.append(f"wrapper checks: allocations {seen}")
+    assert not failures, "\n".join(failures)
+
+
+# rows of (label, overrides of BWD, strict-only?, accumulate: None = either way / 0 / 1): every one is TGS_ERR_INVALID
+BACKWARD_TABLE = [(f"{k} = {v}", {k: v}, False, None, "bad sizes") for k, v in (("P", -1), ("R", -1), ("width", 0), ("height", -3))] + [
+    ("sizes win over colours", dict(R=-1, colors_precomp=None), False, None, "bad sizes"),
+    ("no colours", dict(colors_precomp=None), False, None, MSG_COLOR),
+    ("both colours", dict(shs=X, M=16), False, None, MSG_COLOR),
+    ("colours win over scales", dict(colors_precomp=None, cov3D_precomp=X), False, None, MSG_COLOR),
+    ("scales, rotations and cov3D", dict(cov3D_precomp=X), False, None, MSG_SR),
+    ("none of scales, rotations, cov3D", dict(scales=None, rotations=None), False, None, MSG_SR),
+    ("scales without rotations", dict(rotations=None), False, None, MSG_SR),
+    ("rotations without scales", dict(scales=None), False, None, MSG_SR),
+    ("scales win over NULL pointers", dict(cov3D_precomp=X, radii=None), False, None, MSG_SR),
+    # today's behaviour, unlike the forward's: half a (scales, rotations) pair next to cov3D_precomp counts as the cov3D path, and D / M are not looked at
+    ("scales without rotations, with cov3D: the cov3D path", dict(rotations=None, cov3D_precomp=X, dL_dcov3D=None), False, None, MSG_NULL),
+    ("D and M are not checked", dict(SH, D=9, M=0, dL_dsh=None), False, None, MSG_NULL),
+] + [(f"{p} NULL", {p: None}, False, None, MSG_NULL) for p in ("geom_buffer", "binning_buffer", "img_buffer", "radii", "dL_dpix", "dL_dmean2D", "dL_dopacity", "dL_dmean3D")] + [
+    ("dL_dcolor NULL with colors_precomp", dict(dL_dcolor=None), False, None, MSG_NULL),
+    ("dL_dsh NULL with shs", dict(SH, dL_dsh=None), False, None, MSG_NULL),
+    ("dL_dcov3D NULL with cov3D_precomp", dict(COV, dL_dcov3D=None), False, None, MSG_NULL),
+    # the reference's contract (tgs_backward, tgs_backward_accumulate): the outputs tgs_backward_opt lets its caller drop
+    ("dL_dconic NULL", dict(dL_dconic=None), True, None, MSG_NULL),
+    ("dL_dcolor NULL with shs", dict(SH, dL_dcolor=None), True, 0, MSG_NULL),
+    ("dL_dcov3D NULL with scales and rotations", dict(dL_dcov3D=None), True, 0, MSG_NULL),
+]
+
+
+def test_backward_rejections(abi):
+    """tgs_backward, tgs_backward_accumulate, tgs_backward_opt: one set of checks; `strict` rows are rejected by the first two only (and the
+    last two of them only without accumulation) -- that the others ACCEPT them needs a device to see."""
+    lib, failures = abi, []
+    entries = [("tgs_backward", True, 0, lambda a: lib.tgs_backward(*a)), ("tgs_backward_accumulate", True, 1, lambda a: lib.tgs_backward_accumulate(*a)),
+               ("opt", False, 0, lambda a: lib.tgs_backward_opt(None, 0, *a)), ("opt accumulate", False, 1, lambda a: lib.tgs_backward_opt(None, 1, *a))]
+    for ename, strict, acc, call in entries:
+        for label, over, strict_only, only_acc, text in BACKWARD_TABLE:
+            if (strict_only and not strict) or (only_acc is not None and only_acc != acc):
+                continue
+            _check(lib, failures, f"{ename}: {label}", call(_args(BWD, over)), INVALID, text)
+        _check(lib, failures, f"{ename}: P == 0", call(_args(BWD, dict(P=0, R=-1, width=0, colors_precomp=None, radii=None))), 0, "")
+    assert not failures, "\n".join(failures)
+
+
+def _views(n, **over):
+    arr = (_View * n)()
+    for v in arr:
+        v.width, v.height, v.tan_fovx, v.tan_fovy, v.R = 64, 64, 1.0, 1.0, 5
+        for f in ("viewmatrix", "projmatrix", "campos", "radii", "geom_buffer", "binning_buffer", "img_buffer", "dL_dmean2D", "dL_dcolor", "background", "out_color",
+                  "radii_out", "dL_dpix"):
+            setattr(v, f, X)
+        v.geom_bytes = v.binning_bytes = v.img_bytes = 1 << 30
+        for k, val in over.items():
+            setattr(v, k, val)
+    return arr
+
+
+def _options(**kw):
+    o = _Options(ctypes.sizeof(_Options), -1, -1, 0, 0, 0, 0, 0, -1)
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def test_forward_views_rejections(abi):
+    lib, failures = abi, []
+    streams = (_vp * 2)(None, None)
+    group4 = _options(forward_group=4)
+
+    def run(label, code, text, arr=None, opt=None, **over):
+        a = {**FVIEWS, "streams": ctypes.cast(streams, _vp), "n_streams": 2, "n_views": len(arr) if arr is not None else 0,
+             "views": ctypes.cast(arr, _vp) if arr is not None else None, **over}
+        assert not set(a) - set(FVIEWS)
+        if opt is None:
+            _check(lib, failures, f"tgs_forward_views: {label}", lib.tgs_forward_views(*a.values()), code, text)
+        _check(lib, failures, f"tgs_forward_views_opt: {label}", lib.tgs_forward_views_opt(ctypes.byref(opt) if opt is not None else None, *a.values()), code, text)
+
+    run("no views", 0, None, n_views=0, streams=None, views=None, P=-1)
+    for label, over in (("streams NULL", dict(streams=None)), ("no streams", dict(n_streams=0)), ("n_views < 0", dict(n_views=-1)), ("views NULL", dict(views=None, n_views=2)),
+                        ("r_capacity < 0", dict(r_capacity=-1))):
+        run(label, INVALID, "bad arguments", arr=_views(2), **over)
+    run("bad arguments win over a bad view", INVALID, "bad arguments", arr=_views(2, width=0), r_capacity=-1)
+    v = _views(3); v[2].colors_precomp = X
+    run("per-view colours with shs", INVALID, MSG_COLOR, arr=v, **dict(SH), opt=group4)
+    v = _views(3, width=0); v[2].colors_precomp = X
+    run("per-view colours with shs win over a bad view", INVALID, MSG_COLOR, arr=v, **dict(SH), opt=group4)
+    for f, bad in [(p, None) for p in ("geom_buffer", "binning_buffer", "img_buffer", "out_color", "background", "viewmatrix", "projmatrix", "campos")] + [("width", 0), ("height", -1)]:
+        v = _views(2); setattr(v[1], f, bad)
+        run(f"view 1: {f}", INVALID, MSG_VIEW % 1, arr=v)
+        run(f"view 1: {f} wins over a model error", INVALID, MSG_VIEW % 1, arr=v, colors_precomp=None)
+        v = _views(4); setattr(v[3], f, bad)
+        run(f"view 3 of a group of four: {f}", INVALID, MSG_VIEW % 3, arr=v, opt=group4)
+    v = _views(1, width=0)
+    run("a single bad view", INVALID, MSG_VIEW % 0, arr=v)
+    # a group that shares the per-Gaussian stage checks its views' images and buffers itself
+    g, _b, i = _sizes(lib, 10, 64, 64, False, True)
+    for f, n in (("geom_bytes", g - 1), ("img_bytes", i - 1)):
+        v = _views(2, geom_bytes=g, img_bytes=i, binning_bytes=0); setattr(v[1], f, n)
+        run(f"batched: view 1 {f} one short", ALLOC, "view 1: state buffers smaller than tgs_state_sizes()", arr=v)
+        v = _views(1, geom_bytes=g, img_bytes=i, binning_bytes=0); setattr(v[0], f, n)
+        run(f"single view: {f} one short", ALLOC, "state buffer allocation failed", arr=v)
+        v = _views(2, geom_bytes=g, img_bytes=i, binning_bytes=0); setattr(v[0], f, n)
+        run(f"groups of one: {f} one short", ALLOC, "state buffer allocation failed", arr=v, opt=_options(forward_group=1))
+    gs, _b, _i = _sizes(lib, 10, 64, 64, True, False)
+    v = _views(2, geom_bytes=gs - 1)
+    run("batched: geometry sized for SH + cov3D", ALLOC, "view 0: state buffers smaller than tgs_state_sizes()", arr=v, **dict(SH, **COV))
+    v = _views(2); v[1].width = BIG; v[1].height = 16
+    run("batched: image too large", INVALID, "image too large", arr=v)
+    v = _views(3, geom_bytes=0); v[2].height = BIG
+    run("batched: the views of a group in order (view 0's buffers before view 2's image)", ALLOC, "view 0: state buffers smaller than tgs_state_sizes()", arr=v, opt=group4)
+    run("single view: image too large", INVALID, "image too large", arr=_views(1, width=BIG, height=16))
+    # a model the shared stage cannot take goes view by view through the single-view forward, which names the error
+    for label, over, text in [
+            ("no colours", dict(colors_precomp=None), MSG_COLOR), ("both colours", dict(shs=X, M=16), MSG_COLOR),
+            ("scales, rotations and cov3D", dict(cov3D_precomp=X), MSG_SR), ("none of scales, rotations, cov3D", dict(scales=None, rotations=None), MSG_SR),
+            ("scales without rotations", dict(rotations=None), MSG_SR), ("rotations without scales, with cov3D", dict(scales=None, cov3D_precomp=X), MSG_SR),
+            ("scales without rotations, with cov3D", dict(rotations=None, cov3D_precomp=X), MSG_SR),
+            ("D > 3", dict(SH, D=4, M=25), "SH degree 4 needs M >= 25 (M=25)"), ("D < 0", dict(SH, D=-1), "SH degree -1 needs M >= 0 (M=16)"),
+            ("M too small", dict(SH, M=15), "SH degree 3 needs M >= 16 (M=15)"), ("means3D NULL", dict(means3D=None), MSG_NULL), ("opacities NULL", dict(opacities=None), MSG_NULL),
+            ("P < 0", dict(P=-1), "bad sizes P=-1 W=64 H=64"), ("colours win over scales", dict(colors_precomp=None, scales=None), MSG_COLOR)]:
+        run(f"model, single view: {label}", INVALID, text, arr=_views(1), **over)
+        run(f"model, groups of one: {label}", INVALID, text, arr=_views(2), opt=_options(forward_group=1), **over)
+        if "with cov3D" in label:           # (half a pair next to cov3D_precomp: what a GROUP does with it before the single-view forward
+            continue                        # rejects it is not decided before the first launch -- not a case for this table)
+        run(f"model: {label}", INVALID, text, arr=_views(2), **over)
+        run(f"model, group of four: {label}", INVALID, text, arr=_views(4), opt=group4, **over)
+    v = _views(2, geom_bytes=0); v[0].colors_precomp = v[1].colors_precomp = X
+    run("per-view colours: view by view", ALLOC, "state buffer allocation failed", arr=v, colors_precomp=None)
+    run("single view: r_capacity > 2^31-1", INVALID, "r_capacity exceeds 2^31-1", arr=_views(1), r_capacity=1 << 31)
+    run("model error behind r_capacity > 2^31-1", INVALID, "r_capacity exceeds 2^31-1", arr=_views(2), r_capacity=1 << 31, colors_precomp=None)
+    assert not failures, "\n".join(failures)
+
+
+def test_backward_render_rejections(abi):
+    lib, failures = abi, []
+    base = dict(stream=None, P=10, R=5, background=X, width=64, height=64, binning_buffer=X, img_buffer=X, dL_dpix=X)
+    rows = [(f"{k} = {v}", {k: v}, INVALID, "bad sizes") for k, v in (("P", -1), ("R", -1), ("width", 0), ("height", -1))] + \
+           [(f"{p} NULL", {p: None}, INVALID, MSG_NULL) for p in ("background", "binning_buffer", "img_buffer", "dL_dpix")] + \
+           [("sizes win over NULL pointers", dict(R=-2, dL_dpix=None), INVALID, "bad sizes"), ("P == 0", dict(P=0, R=-1, dL_dpix=None), 0, ""),
+            ("R == 0: nothing to launch", dict(R=0), 0, "")]
+    for label, over, code, text in rows:
+        a = _args(base, over)
+        _check(lib, failures, f"tgs_backward_render: {label}", lib.tgs_backward_render(*a), code, text)
+        _check(lib, failures, f"tgs_backward_render_opt: {label}", lib.tgs_backward_render_opt(None, *a), code, text)
+        _check(lib, failures, f"tgs_backward_render_opt, options: {label}", lib.tgs_backward_render_opt(ctypes.byref(_options(tile_bound=3)), *a), code, text)
+    streams = (_vp * 2)(None, None)
+    sp = ctypes.cast(streams, _vp)
+    for ename, call in (("tgs_backward_render_views", lambda *a: lib.tgs_backward_render_views(*a)), ("tgs_backward_render_views_opt", lambda *a: lib.tgs_backward_render_views_opt(None, *a))):
+        vs = _views(3, R=0)                 # (R == 0: a view without instances launches nothing, so later views are reached)
+        vp_ = ctypes.cast(vs, _vp)
+        _check(lib, failures, f"{ename}: no views", call(None, 0, 10, 0, None), 0, None)
+        for label, a in (("streams NULL", (None, 2, 10, 3, vp_)), ("no streams", (sp, 0, 10, 3, vp_)), ("n_views < 0", (sp, 2, 10, -1, vp_)), ("views NULL", (sp, 2, 10, 3, None))):
+            _check(lib, failures, f"{ename}: {label}", call(*a), INVALID, "bad arguments")
+        _check(lib, failures, f"{ename}: P == 0", call(sp, 2, 0, 3, vp_), 0, None)
+        _check(lib, failures, f"{ename}: views without instances", call(sp, 2, 10, 3, vp_), 0, "")
+        _check(lib, failures, f"{ename}: P < 0", call(sp, 2, -1, 3, vp_), INVALID, "bad sizes")
+        for f, bad, text in [("R", -1, "bad sizes"), ("width", 0, "bad sizes"), ("height", 0, "bad sizes")] + [(p, None, MSG_NULL) for p in ("background", "binning_buffer", "img_buffer", "dL_dpix")]:
+            for k in (0, 2):                # (the message does not carry the view's index)
+                vs = _views(3, R=0); setattr(vs[k], f, bad)
+                _check(lib, failures, f"{ename}: view {k}: {f}", call(sp, 2, 10, 3, ctypes.cast(vs, _vp)), INVALID, text)
+    assert not failures, "\n".join(failures)
+
+
+MSG_RANGE = "Gaussian range [%d, %d + %d) must start and end on multiples of 256 (or end at P = %d)"
+MSG_PLANES = "level-major dL_dsh needs SH colours with M = 16, a plane stride >= 3 P that is a multiple of 4 floats, and a 16-byte aligned dL_dsh"
+BATCH_SH = dict(shs=X, D=3, M=16, dL_dsh=X)
+BATCH_COV = dict(scales=None, rotations=None, cov3D_precomp=X, dL_dcov3D=X, dL_dscale=None, dL_drot=None)
+
+
+def test_backward_batch_rejections(abi):
+    """tgs_backward_batch, _range, _range_planes: sizes, then the range, then the model, then the level-major conditions, then the views."""
+    lib, failures = abi, []
+
+    def run(label, code, text, arr=8, first=0, count=None, stride=0, **over):
+        vs = _views(arr) if isinstance(arr, int) else arr
+        a = {**BATCH, "n_views": len(vs), "views": ctypes.cast(vs, _vp), **over}
+        assert not set(a) - set(BATCH)
+        count = a["P"] - first if count is None else count
+        if stride == 0 and first == 0 and count == a["P"]:
+            _check(lib, failures, f"tgs_backward_batch: {label}", lib.tgs_backward_batch(*a.values()), code, text)
+        if stride == 0:
+            _check(lib, failures, f"tgs_backward_batch_range: {label}", lib.tgs_backward_batch_range(*a.values(), first, count), code, text)
+        _check(lib, failures, f"tgs_backward_batch_range_planes: {label}", lib.tgs_backward_batch_range_planes(*a.values(), first, count, stride), code, text)
+
+    run("P == 0", 0, "", P=0, means3D=None)
+    run("no views", 0, "", n_views=0, means3D=None)
+    run("empty range", 0, "", first=3, count=0, means3D=None)
+    run("P < 0", INVALID, "bad sizes", P=-1)
+    run("n_views < 0", INVALID, "bad sizes", n_views=-1)
+    run("views NULL", INVALID, "bad sizes", views=None, n_views=2)
+    run("sizes win over the range", INVALID, "bad sizes", P=-1, first=3)
+    for first, count in ((-256, 256), (0, -1), (100, 900), (256, 1000), (0, 300), (512, 300), (768, 233), (0, 1001)):
+        run(f"range {first} + {count}", INVALID, MSG_RANGE % (first, first, count, 1000), first=first, count=count)
+    run("range wins over the model", INVALID, MSG_RANGE % (0, 0, 300, 1000), first=0, count=300, cov3D_precomp=X)
+    run("scales, rotations and cov3D", INVALID, MSG_SR, cov3D_precomp=X)
+    run("none of scales, rotations, cov3D", INVALID, MSG_SR, scales=None, rotations=None)
+    run("scales without rotations", INVALID, MSG_SR, rotations=None)
+    run("rotations without scales", INVALID, MSG_SR, scales=None)
+    run("scales win over SH degree", INVALID, MSG_SR, **dict(BATCH_SH, D=4, cov3D_precomp=X))
+    run("D > 3", INVALID, "SH degree 4 needs M >= 25 (M=16)", **dict(BATCH_SH, D=4))
+    run("D < 0", INVALID, "SH degree -1 needs M >= 0 (M=16)", **dict(BATCH_SH, D=-1))
+    run("M too small", INVALID, "SH degree 2 needs M >= 9 (M=8)", **dict(BATCH_SH, D=2, M=8))
+    run("SH degree wins over NULL pointers", INVALID, "SH degree 2 needs M >= 9 (M=8)", **dict(BATCH_SH, D=2, M=8, means3D=None))
+    run("scales without rotations, with cov3D: the cov3D path", INVALID, MSG_NULL, rotations=None, cov3D_precomp=X, dL_dcov3D=None)
+    for p in ("means3D", "dL_dopacity", "dL_dmean3D", "dL_dscale", "dL_drot"):
+        run(f"{p} NULL", INVALID, MSG_NULL, **{p: None})
+    run("dL_dsh NULL with shs", INVALID, MSG_NULL, **dict(BATCH_SH, dL_dsh=None))
+    run("dL_dcov3D NULL with cov3D_precomp", INVALID, MSG_NULL, **dict(BATCH_COV, dL_dcov3D=None))
+    run("NULL pointers win over level-major", INVALID, MSG_NULL, stride=3008, means3D=None)
+    run("level-major without shs", INVALID, MSG_PLANES, stride=3008)
+    run("level-major, M = 9", INVALID, MSG_PLANES, stride=3008, **dict(BATCH_SH, D=2, M=9))
+    run("level-major, stride < 3 P", INVALID, MSG_PLANES, stride=2996, **BATCH_SH)
+    run("level-major, stride not a multiple of 4", INVALID, MSG_PLANES, stride=3002, **BATCH_SH)
+    run("level-major, dL_dsh misaligned", INVALID, MSG_PLANES, stride=3008, **dict(BATCH_SH, dL_dsh=X + 4))
+    run("level-major wins over a bad view", INVALID, MSG_PLANES, arr=_views(2, width=0), stride=3002, **BATCH_SH)
+    for f, bad in [("width", 0), ("height", -1), ("R", -1)] + [(p, None) for p in ("viewmatrix", "projmatrix", "campos", "radii", "geom_buffer", "binning_buffer", "img_buffer", "dL_dmean2D", "dL_dcolor")]:
+        for k in (0, 5):
+            vs = _views(8); setattr(vs[k], f, bad)
+            run(f"view {k}: {f}", INVALID, MSG_VIEW % k, arr=vs)
+    vs = _views(8); vs[7].dL_dmean2D = None; vs[6].dL_dcolor = None
+    run("view 7 (dL_dcolor is not needed with shs)", INVALID, MSG_VIEW % 7, arr=vs, **BATCH_SH)
+    vs = _views(3); vs[1].R = -1
+    run("view 1 of a range", INVALID, MSG_VIEW % 1, arr=vs, first=256, count=744)
+    assert not failures, "\n".join(failures)
+
+
+def test_small_entry_point_rejections(abi):
+    lib, failures = abi, []
+    a, b = _i64(0), _it(0)
+    for args in ((None, None, ctypes.byref(a), ctypes.byref(b)), (None, X, None, ctypes.byref(b)), (None, X, ctypes.byref(a), None)):
+        _check(lib, failures, "tgs_frame_status", lib.tgs_frame_status(*args), INVALID, MSG_NULL)
+    for args in ((None, -1, X, X, X, X), (None, 5, None, X, X, X), (None, 5, X, None, X, X), (None, 5, X, X, None, None)):
+        _check(lib, failures, "tgs_mark_visible", lib.tgs_mark_visible(*args), INVALID, "bad arguments")
+    _check(lib, failures, "tgs_mark_visible: P == 0", lib.tgs_mark_visible(None, 0, None, None, None, None), 0, "")
+    field = lambda name, P, R, nbytes: lib.tgs_state_field(None, name, P, 64, 64, R, 0, 1, X, X, X, X, nbytes)
+    _check(lib, failures, "tgs_state_field: unknown", field(b"foo", 10, 5, 1 << 20), INVALID, "unknown field foo")
+    _check(lib, failures, "tgs_state_field: dst too small", field(b"depths", 10, 5, 39), INVALID, "dst too small for depths")
+    _check(lib, failures, "tgs_state_field: dst too small", field(b"ranges", 10, 5, 16 * 8 - 1), INVALID, "dst too small for ranges")
+    _check(lib, failures, "tgs_state_field: dst too small", field(b"means2D", 10, 5, 79), INVALID, "dst too small for means2D")
+    _check(lib, failures, "tgs_state_field: nothing to copy", field(b"point_list", 10, 0, 0), 0, "")
+    assert not failures, "\n".join(failures)

@@ -150,29 +150,425 @@ static int fail(int code, const char* fmt, ...)
         if (e_ != hipSuccess) return fail(TGS_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-// the reference's CHECK_CUDA (auxiliary.h:166-173): in debug mode synchronise after every stage
-#define STAGE_BEGIN(id) prof_begin_stage(st, id)
-#define STAGE_CHECK(name, id)                                                                             \
-    do {                                                                                                  \
-        prof_end_stage(st, id);                                                                                                  \
-        hipError_t e_ = hipGetLastError();                                                                \
-        if (e_ == hipSuccess && debug) e_ = hipStreamSynchronize(st);                                     \
-        if (e_ != hipSuccess) return fail(TGS_ERR_HIP, "stage %s: %s", name, hipGetErrorString(e_));       \
-    } while (0)
-
-static CamParams make_cam(const float* view, const float* proj, const float* campos, float tan_fovx, float tan_fovy, float scale_modifier,
-                          int W, int H)
+// One pipeline stage: profile events around `launch` on `st`, then the reference's CHECK_CUDA (auxiliary.h:166-173): in debug mode
+// synchronise after every stage
+template <class Launch>
+static int stage(hipStream_t st, int id, const char* name, int debug, Launch&& launch)
 {
-    CamParams c;
-    c.view = view; c.proj = proj; c.campos = campos;
-    c.tan_fovx = tan_fovx; c.tan_fovy = tan_fovy;
-    c.focal_y = H / (2.0f * tan_fovy);            // rasterizer_impl.cu:222-223
-    c.focal_x = W / (2.0f * tan_fovx);
-    c.scale_modifier = scale_modifier;
-    c.W = W; c.H = H;
-    c.gx = (uint32_t)((W + TILE - 1) / TILE);
-    c.gy = (uint32_t)((H + TILE - 1) / TILE);
-    return c;
+    prof_begin_stage(st, id);
+    launch();
+    prof_end_stage(st, id);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && debug) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(TGS_ERR_HIP, "stage %s: %s", name, hipGetErrorString(e));
+    return TGS_OK;
+}
+
+// ---- argument records: every extern "C" entry point packs its arguments into these ONCE (fields in the order of the C signatures);
+// nothing below the entry points takes the long lists ----
+struct GeomShape { size_t P; bool has_sh, has_sr; };      // what sizes the geometry buffer
+struct Model {                  // the Gaussians: what every view of a call shares
+    int P, D, M;
+    const float *means3D, *shs, *colors_precomp, *opacities, *scales;
+    float scale_modifier;
+    const float *rotations, *cov3D_precomp;
+    bool has_sh() const { return shs != nullptr; }
+    bool has_sr() const { return scales != nullptr && rotations != nullptr; }
+    GeomShape shape() const { return GeomShape{(size_t)P, has_sh(), has_sr()}; }
+};
+
+struct ViewArgs {               // one camera and its image; the one place that knows the tile grid
+    const float* background;
+    int width, height;
+    const float *viewmatrix, *projmatrix, *campos;
+    float tan_fovx, tan_fovy;
+    uint32_t gx() const { return (uint32_t)((width + TILE - 1) / TILE); }
+    uint32_t gy() const { return (uint32_t)((height + TILE - 1) / TILE); }
+    size_t N() const { return (size_t)width * height; }
+    size_t T() const { return (size_t)gx() * gy(); }
+    CamParams cam(float scale_modifier) const
+    {
+        CamParams c;
+        c.view = viewmatrix; c.proj = projmatrix; c.campos = campos;
+        c.tan_fovx = tan_fovx; c.tan_fovy = tan_fovy;
+        c.focal_y = height / (2.0f * tan_fovy);       // rasterizer_impl.cu:222-223
+        c.focal_x = width / (2.0f * tan_fovx);
+        c.scale_modifier = scale_modifier;
+        c.W = width; c.H = height;
+        c.gx = gx(); c.gy = gy();
+        return c;
+    }
+};
+static ViewArgs view_args(const tgs_view_t& v) { return ViewArgs{v.background, v.width, v.height, v.viewmatrix, v.projmatrix, v.campos, v.tan_fovx, v.tan_fovy}; }
+
+static int frame_cam(CamParams& cam, const ViewArgs& v, float scale_modifier)
+{
+    cam = v.cam(scale_modifier);
+    if (cam.gx > 65535u || cam.gy > 65535u) return fail(TGS_ERR_INVALID, "image too large");
+    return TGS_OK;
+}
+
+struct FrameBuffers { GeomState g; ImgState s; BinState b; };      // the three state buffers of a frame, carved
+
+// a frame whose buffers exist (backward, batch backward, tgs_state_field); a buffer the caller does not use may be NULL
+static FrameBuffers carve_frame(const GeomShape& m, const ViewArgs& v, int64_t R, const void* geom, const void* binning, const void* img)
+{
+    FrameBuffers fb;
+    geom_carve(fb.g, (char*)geom, m.P, m.has_sh, m.has_sr);
+    img_carve(fb.s, (char*)img, v.N(), v.T());
+    bin_carve(fb.b, (char*)binning, (size_t)R);
+    return fb;
+}
+
+struct Alloc { tgs_alloc_fn fn; void* ctx; };
+
+// the forward's frame: geometry and image are sized and requested first (in this order), the binning buffer once its size is known
+static int alloc_geom_image(FrameBuffers& fb, const Alloc& a, const GeomShape& m, const ViewArgs& v)
+{
+    char* geom = (char*)a.fn(a.ctx, TGS_BUF_GEOM, geom_carve(fb.g, nullptr, m.P, m.has_sh, m.has_sr));
+    char* img = (char*)a.fn(a.ctx, TGS_BUF_IMAGE, img_carve(fb.s, nullptr, v.N(), v.T()));
+    if (!geom || !img) return fail(TGS_ERR_ALLOC, "state buffer allocation failed");
+    fb = carve_frame(m, v, 0, geom, nullptr, img);
+    return TGS_OK;
+}
+static int alloc_binning(FrameBuffers& fb, const Alloc& a, uint64_t R)
+{
+    char* bin = (char*)a.fn(a.ctx, TGS_BUF_BINNING, bin_carve(fb.b, nullptr, (size_t)R));
+    if (!bin) return fail(TGS_ERR_ALLOC, "binning buffer allocation failed");
+    bin_carve(fb.b, bin, (size_t)R);
+    return TGS_OK;
+}
+
+// ---- the one model check and the one per-view check ----
+// What the entry points ask of a model differs (and stays as it is): the single-view backward looks at neither D / M nor the model's
+// pointers; only the forward refuses half a (scales, rotations) pair next to cov3D_precomp; the batch backward has no shared
+// colors_precomp (shs == NULL there means per-view colours).
+enum ModelUse { MODEL_FORWARD, MODEL_BACKWARD, MODEL_BATCH_BACKWARD };
+static int check_model(const Model& m, ModelUse use)
+{
+    if (use != MODEL_BATCH_BACKWARD && m.has_sh() == (m.colors_precomp != nullptr)) return fail(TGS_ERR_INVALID, "provide exactly one of shs / colors_precomp");
+    const bool half_pair = (m.scales == nullptr) != (m.rotations == nullptr);
+    if (m.has_sr() == (m.cov3D_precomp != nullptr) || (use == MODEL_FORWARD && half_pair))
+        return fail(TGS_ERR_INVALID, "provide exactly one of (scales, rotations) / cov3D_precomp");
+    if (use == MODEL_BACKWARD) return TGS_OK;
+    if (m.has_sh() && (m.D < 0 || m.D > 3 || m.M < (m.D + 1) * (m.D + 1)))
+        return fail(TGS_ERR_INVALID, "SH degree %d needs M >= %d (M=%d)", m.D, (m.D + 1) * (m.D + 1), m.M);
+    if (!m.means3D || (use == MODEL_FORWARD && !m.opacities)) return fail(TGS_ERR_INVALID, "NULL required pointer");
+    return TGS_OK;
+}
+
+// A tgs_view_t carries the fields of three uses; each needs its own.  The per-pixel backward also serves tgs_backward_render, which has
+// no view index to name: its two messages stay as they are.
+enum ViewUse { VIEW_FORWARD, VIEW_RENDER_BWD, VIEW_BATCH_BWD };
+static int check_view(const tgs_view_t& v, int k, ViewUse use, bool has_sh)
+{
+    const bool sizes = v.width > 0 && v.height > 0 && (use == VIEW_FORWARD || v.R >= 0);
+    bool ptrs = v.binning_buffer && v.img_buffer;
+    if (use == VIEW_RENDER_BWD) ptrs = ptrs && v.background && v.dL_dpix;
+    else ptrs = ptrs && v.geom_buffer && v.viewmatrix && v.projmatrix && v.campos;
+    if (use == VIEW_FORWARD) ptrs = ptrs && v.out_color && v.background;
+    if (use == VIEW_BATCH_BWD) ptrs = ptrs && v.radii && v.dL_dmean2D && (has_sh || v.dL_dcolor);
+    if (use == VIEW_RENDER_BWD) {
+        if (!sizes) return fail(TGS_ERR_INVALID, "bad sizes");
+        return ptrs ? TGS_OK : fail(TGS_ERR_INVALID, "NULL required pointer");
+    }
+    return sizes && ptrs ? TGS_OK : fail(TGS_ERR_INVALID, "view %d: bad sizes or NULL required pointer", k);
+}
+
+// ---- the bound rule, for both directions ----
+// Sync-free grids cover `tiles` tiles (the caller's bound on the tiles with instances, or all T of them); k_scan rejects a frame with
+// more.  The class bounds (tiles with >= 1024 / >= LIGHT_MAX instances) come with a tile bound below T only: only then does k_scan
+// enforce them, and without that neither the forward nor the backward may size a grid by them.
+struct Bounds { uint32_t tiles, heavy, mid; };
+static Bounds all_tiles(size_t T) { return Bounds{(uint32_t)T, (uint32_t)T, (uint32_t)T}; }
+static Bounds resolve_bounds(const Opts& o, size_t T)
+{
+    Bounds b = all_tiles(T);
+    if (o.tile_bound > 0 && (uint64_t)o.tile_bound < (uint64_t)T) b.tiles = (uint32_t)o.tile_bound;
+    const bool classes = b.tiles < T;
+    b.heavy = (classes && o.heavy_bound > 0 && (uint64_t)o.heavy_bound < b.tiles) ? (uint32_t)o.heavy_bound : b.tiles;
+    b.mid = (classes && o.mid_bound > 0 && (uint64_t)o.mid_bound < b.tiles) ? (uint32_t)o.mid_bound : b.tiles;
+    return b;
+}
+// the bounds of a view of the *_views entry points travel in its tgs_view_t
+static Opts view_options(Opts opt, const tgs_view_t& v)
+{
+    opt.tile_bound = v.tile_bound > 0 ? v.tile_bound : 0;
+    opt.heavy_bound = v.heavy_bound > 0 ? v.heavy_bound : 0;
+    opt.mid_bound = v.mid_bound > 0 ? v.mid_bound : 0;
+    return opt;
+}
+
+// pinned Meta staging + event of the speculative forward: one per host thread AND device (an event belongs to the device that was
+// current when it was created; a thread that renders on cuda:0 and then on cuda:1 gets a slot for each)
+struct SpecSlot { Meta* meta; hipEvent_t ready; };
+static SpecSlot* spec_slot()
+{
+    thread_local std::vector<SpecSlot> slots;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return nullptr;
+    if ((size_t)dev >= slots.size()) slots.resize((size_t)dev + 1, SpecSlot{nullptr, nullptr});
+    SpecSlot& slot = slots[(size_t)dev];
+    if (!slot.meta) {
+        if (hipHostMalloc((void**)&slot.meta, sizeof(Meta), hipHostMallocDefault) != hipSuccess) { slot.meta = nullptr; return nullptr; }
+        if (hipEventCreateWithFlags(&slot.ready, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(slot.meta); slot.meta = nullptr; return nullptr; }
+    }
+    return &slot;
+}
+
+// tgs_set_render_streams: k_render_fwd of view k goes to render stream k mod n (behind an event on the view's own stream)
+static thread_local std::vector<hipStream_t> t_render_streams;
+static thread_local int64_t t_last_nonempty = -1;           // tgs_last_nonempty_tiles (legacy read-out; tgs_frame_info_t carries it explicitly)
+
+// ---- the forward ----
+// How one forward runs, beside the model and the view.  mode TGS_FWD_SYNC: the reference's protocol (read R back, then size the binning
+// buffer).  TGS_FWD_ASYNC: sync-free -- the binning buffer is sized for r instances before anything runs and nothing is read back.
+// TGS_FWD_SPECULATIVE: enqueued like the sync-free one against the guess r, then the host reads the frame's Meta and repeats the stages
+// behind the scan if the guess was too small.
+struct FwdCall {
+    int mode; int64_t r; tgs_frame_info_t* info;
+    Alloc alloc; hipStream_t st;
+    int prefiltered; float* out_color; int* radii; int debug;
+    // tgs_forward_views only: the pinned record k_scan writes the frame's Meta to as well; where k_render_fwd goes (nullptr: the frame's own
+    // stream); whether the per-Gaussian stage of this view already ran with its group's
+    Meta* host_meta; hipStream_t render_stream; bool preprocessed;
+};
+struct Forward {                // one forward in flight: what its phases share
+    const Opts& opt; const FwdCall& c; const Model& m; const ViewArgs& v;
+    CamParams cam; FrameBuffers fb; FwdIn in;
+    uint32_t T() const { return (uint32_t)v.T(); }
+};
+
+static FwdIn fwd_in(const Model& m, const Opts& opt, int prefiltered)
+{
+    FwdIn in;
+    memset(&in, 0, sizeof(in));
+    in.P = m.P; in.D = m.D; in.M = m.M; in.means3D = m.means3D; in.shs = m.shs; in.colors_precomp = m.colors_precomp; in.opacities = m.opacities;
+    in.scales = m.scales; in.rotations = m.rotations; in.cov3D_precomp = m.cov3D_precomp; in.prefiltered = prefiltered; in.prune = opt.prune;
+    return in;
+}
+
+// rasterize_points.cu:81: nothing runs, the image keeps its zero fill (empty inputs have no pointers to check)
+static int64_t forward_empty(const FwdCall& c, const ViewArgs& v)
+{
+    if (!c.out_color) return fail(TGS_ERR_INVALID, "NULL required pointer");
+    HIP_TRY(hipMemsetAsync(c.out_color, 0, 3 * v.N() * sizeof(float), c.st));
+    if (c.host_meta) memset(c.host_meta, 0, sizeof(Meta));   // (pinned host memory: no kernel of this frame writes it)
+    if (c.info && c.mode != TGS_FWD_ASYNC) { c.info->num_rendered = 0; c.info->nonempty_tiles = 0; c.info->mid_tiles = 0; }
+    if (c.mode != TGS_FWD_SYNC) {   // the caller still gets a (zeroed) Meta to query
+        ImgState s0;
+        char* ip = (char*)c.alloc.fn(c.alloc.ctx, TGS_BUF_IMAGE, img_carve(s0, nullptr, v.N(), v.T()));
+        if (!ip) return fail(TGS_ERR_ALLOC, "state buffer allocation failed");
+        HIP_TRY(hipMemsetAsync(ip, 0, 256, c.st));
+    }
+    return 0;
+}
+
+// validate, size and allocate geometry and image, fill the kernels' arguments.  Meta sits at the head of the image buffer;
+// k_preprocess_fwd* clears it itself (block_sum_tiles: nothing else writes Meta before k_scan), everything else is written before it is
+// read -- no memset launch in front of a frame
+static int plan(Forward& f)
+{
+    if (int r = check_model(f.m, MODEL_FORWARD)) return r;
+    if (!f.v.background || !f.v.viewmatrix || !f.v.projmatrix || !f.v.campos || !f.c.out_color) return fail(TGS_ERR_INVALID, "NULL required pointer");
+    if (int r = frame_cam(f.cam, f.v, f.m.scale_modifier)) return r;
+    if (int r = alloc_geom_image(f.fb, f.c.alloc, f.m.shape(), f.v)) return r;
+    f.in = fwd_in(f.m, f.opt, f.c.prefiltered);
+    f.in.background = f.v.background; f.in.out_color = f.c.out_color; f.in.radii = f.c.radii;
+    return TGS_OK;
+}
+
+static int enqueue_preprocess(Forward& f)
+{
+    return stage(f.c.st, TGS_STAGE_PREPROCESS_FWD, "preprocess", f.c.debug, [&] { launch_preprocess_fwd(f.c.st, f.in, f.cam, f.fb.g, f.fb.s); });
+}
+
+// count and scan the tile instances; k_scan rejects a frame with more than `capacity` of them or more tiles than `b` allows, and writes
+// the frame's Meta to `host_meta` as well when there is one
+static int enqueue_scan(Forward& f, const Bounds& b, unsigned long long capacity, Meta* host_meta)
+{
+    return stage(f.c.st, TGS_STAGE_SCAN, "scan", f.c.debug, [&] {
+        launch_bin_count(f.c.st, f.m.P, f.fb.g, f.fb.s, f.cam.gx, f.T());
+        launch_scan(f.c.st, f.fb.g, f.fb.s, (uint32_t)n_blocks((size_t)f.m.P), f.T(), f.opt.sort_cap, capacity, b.tiles, b.heavy, b.mid, host_meta, f.opt.light);
+    });
+}
+
+// what the host learns from a frame's Meta, once it has it; `flags`: the bits of Meta::error the caller is told about
+static int read_meta(const FwdCall& c, const Meta& meta, uint32_t flags)
+{
+    if (meta.error & 1u) return fail(TGS_ERR_PREFILTERED, "Point is filtered although prefiltered is set. This shouldn't happen!");
+    if (meta.R > 0x7fffffffull) return fail(TGS_ERR_TOO_MANY, "%llu tile instances exceed 2^31-1", (unsigned long long)meta.R);
+    t_last_nonempty = (int64_t)meta.n_nonempty;
+    if (c.info) { c.info->num_rendered = (int64_t)meta.R; c.info->nonempty_tiles = (int64_t)meta.n_nonempty; c.info->flags = (int32_t)(meta.error & flags); c.info->mid_tiles = (int32_t)meta.n_mid; }
+    return TGS_OK;
+}
+
+// request the binning buffer for R instances, then scatter, tile sort and render.  `known`: the frame's Meta where the host has it (the
+// kernels then size themselves by it).  render_stream: binning and compositing on different streams (tgs_set_render_streams)
+static int enqueue_binning_and_render(Forward& f, uint64_t R, const Bounds& b, const Meta* known, hipStream_t render_stream)
+{
+    hipStream_t st = f.c.st;
+    const int debug = f.c.debug;
+    if (int r = alloc_binning(f.fb, f.c.alloc, R)) return r;
+    if (R > 0) {
+        if (int r = stage(st, TGS_STAGE_SCATTER, "scatter", debug, [&] { launch_scatter(st, f.m.P, f.fb.g, f.fb.s, f.fb.b, f.cam.gx, f.T()); })) return r;
+        if (int r = stage(st, TGS_STAGE_TILE_SORT, "tile_sort", debug, [&] {
+                launch_tile_sort(st, f.fb.g, f.fb.s, f.fb.b, f.cam.gx, f.T(), R, known, f.opt.sort_cap, b.tiles, b.heavy, b.mid); })) return r;
+    }
+    hipStream_t rst = st;
+    if (render_stream && render_stream != st) {
+        hipEvent_t binned;
+        HIP_TRY(hipEventCreateWithFlags(&binned, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(binned, st));
+        HIP_TRY(hipStreamWaitEvent(render_stream, binned, 0));
+        (void)hipEventDestroy(binned);
+        rst = render_stream;
+    }
+    // (the stage's events and its debug synchronisation stay on the frame's own stream)
+    return stage(st, TGS_STAGE_RENDER_FWD, "render", debug, [&] {
+        launch_render_fwd(rst, f.fb.s, f.fb.b, f.v.width, f.v.height, f.cam.gx, f.T(), known, f.v.background, f.c.out_color, b.tiles, b.mid, f.opt.light); });
+}
+
+static int64_t forward_impl(const Opts& opt, const FwdCall& c, const Model& m, const ViewArgs& v)
+{
+    const bool sync = c.mode == TGS_FWD_SYNC, spec = c.mode == TGS_FWD_SPECULATIVE;
+    t_last_nonempty = -1;                                   // (known again once this call has read the frame's Meta)
+    if (c.info) { c.info->num_rendered = -1; c.info->nonempty_tiles = -1; c.info->flags = 0; c.info->mid_tiles = -1; }
+    if (!sync && c.r > 0x7fffffffll) return fail(TGS_ERR_INVALID, "r_capacity exceeds 2^31-1");
+    g_err[0] = 0;
+    if (!c.alloc.fn) return fail(TGS_ERR_INVALID, "alloc callback is NULL");
+    if (m.P < 0 || v.width <= 0 || v.height <= 0) return fail(TGS_ERR_INVALID, "bad sizes P=%d W=%d H=%d", m.P, v.width, v.height);
+    if (m.P == 0) return forward_empty(c, v);
+    Forward f{opt, c, m, v};
+    if (int r = plan(f)) return r;
+    if (!c.preprocessed)
+        if (int r = enqueue_preprocess(f)) return r;
+    Meta meta;
+    if (sync) {
+        if (int r = enqueue_scan(f, all_tiles(v.T()), ~0ull, c.host_meta)) return r;
+        // the one host synchronisation of the forward pass (rasterizer_impl.cu:280-281): R sizes the binning buffer
+        HIP_TRY(hipMemcpyAsync(&meta, f.fb.s.meta, sizeof(Meta), hipMemcpyDeviceToHost, c.st));
+        HIP_TRY(hipStreamSynchronize(c.st));
+        if (int r = read_meta(c, meta, ~0u)) return r;
+        if (int r = enqueue_binning_and_render(f, meta.R, all_tiles(v.T()), &meta, c.render_stream)) return r;
+        return (int64_t)meta.R;
+    }
+    const Bounds b = resolve_bounds(opt, v.T());
+    if (!spec) {
+        if (int r = enqueue_scan(f, b, (unsigned long long)c.r, c.host_meta)) return r;
+        if (int r = enqueue_binning_and_render(f, (uint64_t)c.r, b, nullptr, c.render_stream)) return r;
+        return c.r;
+    }
+    // speculative: k_scan itself writes Meta into the pinned host slot; the event marks its end, the remaining stages are enqueued
+    // against the guessed capacity without waiting, and only then the host waits for the event -- the GPU never idles behind the
+    // read-back, and no copy sits in the stream
+    SpecSlot* slot = spec_slot();
+    if (!slot) return fail(TGS_ERR_HIP, "pinned staging for the speculative forward could not be allocated");
+    if (int r = enqueue_scan(f, b, (unsigned long long)c.r, slot->meta)) return r;
+    HIP_TRY(hipEventRecord(slot->ready, c.st));
+    if (int r = enqueue_binning_and_render(f, (uint64_t)c.r, b, nullptr, nullptr)) return r;
+    HIP_TRY(hipEventSynchronize(slot->ready));
+    meta = *slot->meta;
+    if (int r = read_meta(c, meta, ~META_ERR_CAPACITY)) return r;
+    if (!(meta.error & META_ERR_CAPACITY) && meta.pad[0] == 0u) return c.r;      // (pad[0]: more tiles with instances than the caller's bound, k_scan)
+    // the guess was too small: every kernel behind the scan returned at once; clear the flag and run those stages again with the exact
+    // sizes, as the synchronous forward does
+    HIP_TRY(hipMemsetAsync(&f.fb.s.meta->error, 0, sizeof(uint32_t), c.st));
+    if (int r = enqueue_binning_and_render(f, meta.R, all_tiles(v.T()), &meta, nullptr)) return r;
+    return (int64_t)meta.R;
+}
+
+// ---- the backward ----
+// the frame a backward differentiates and where its gradients go
+struct BwdArgs {
+    int64_t R; const int* radii; const void *geom_buffer, *binning_buffer, *img_buffer; const float* dL_dpix;
+    float *dL_dmean2D, *dL_dconic, *dL_dopacity, *dL_dcolor, *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot;
+};
+
+static BwdIn bwd_in(const Model& m)
+{
+    BwdIn in;
+    memset(&in, 0, sizeof(in));
+    in.P = m.P; in.D = m.D; in.M = m.M; in.means3D = m.means3D; in.shs = m.shs; in.colors_precomp = m.colors_precomp; in.scales = m.scales;
+    in.rotations = m.rotations; in.cov3D_precomp = m.cov3D_precomp;
+    return in;
+}
+
+// the per-pixel half of a frame's backward; the tile partials stay in the binning buffer
+static int enqueue_render_bwd(const Opts& opt, hipStream_t st, int debug, const FrameBuffers& fb, const ViewArgs& v, int64_t R, const float* dL_dpix)
+{
+    if (R <= 0) return TGS_OK;
+    const Bounds b = resolve_bounds(opt, v.T());
+    return stage(st, TGS_STAGE_RENDER_BWD, "render_bwd", debug, [&] {
+        launch_render_bwd(st, fb.s, fb.b, v.width, v.height, v.gx(), b.tiles, v.background, dL_dpix, opt.deterministic, b.mid, opt.light, (uint32_t)v.T()); });
+}
+
+// strict: tgs_backward / tgs_backward_accumulate as the reference's Rasterizer::backward declares them (every output required);
+// tgs_backward_opt: the outputs its caller discards may be NULL (dL_dconic; dL_dcolor with shs; dL_dcov3D with scales + rotations)
+static int backward_impl(bool strict, const Opts& opt, int accumulate, hipStream_t st, int debug, const Model& m, const ViewArgs& v, const BwdArgs& a)
+{
+    g_err[0] = 0;
+    if (m.P == 0) return TGS_OK;
+    if (m.P < 0 || a.R < 0 || v.width <= 0 || v.height <= 0) return fail(TGS_ERR_INVALID, "bad sizes");
+    if (int r = check_model(m, MODEL_BACKWARD)) return r;
+    if (!a.geom_buffer || !a.binning_buffer || !a.img_buffer || !a.radii || !a.dL_dpix || !a.dL_dmean2D || !a.dL_dopacity || !a.dL_dmean3D ||
+        (m.has_sh() && !a.dL_dsh) || (!m.has_sh() && !a.dL_dcolor) || (!m.has_sr() && !a.dL_dcov3D) ||
+        (strict && (!a.dL_dconic || (!accumulate && (!a.dL_dcolor || !a.dL_dcov3D)))))
+        return fail(TGS_ERR_INVALID, "NULL required pointer");
+    const CamParams cam = v.cam(m.scale_modifier);
+    const FrameBuffers fb = carve_frame(m.shape(), v, a.R, a.geom_buffer, a.binning_buffer, a.img_buffer);
+
+    BwdIn in = bwd_in(m);
+    in.background = v.background; in.radii = a.radii; in.dL_dpix = a.dL_dpix;
+    in.dL_dmean2D = a.dL_dmean2D; in.dL_dconic = a.dL_dconic; in.dL_dopacity = a.dL_dopacity; in.dL_dcolor = a.dL_dcolor;
+    in.dL_dmean3D = a.dL_dmean3D; in.dL_dcov3D = a.dL_dcov3D; in.dL_dsh = a.dL_dsh; in.dL_dscale = a.dL_dscale; in.dL_drot = a.dL_drot;
+    in.accumulate = accumulate;
+    in.meta = fb.s.meta;
+
+    if (int r = enqueue_render_bwd(opt, st, debug, fb, v, a.R, a.dL_dpix)) return r;
+    return stage(st, TGS_STAGE_PREPROCESS_BWD, "preprocess_bwd", debug, [&] { launch_preprocess_bwd(st, in, cam, fb.g, fb.b); });
+}
+
+// tgs_backward_render[_views]: the view's own fields (tgs_backward_render packs its arguments into one)
+static int backward_render_impl(const Opts& opt, hipStream_t st, int P, const tgs_view_t& w)
+{
+    g_err[0] = 0;
+    if (P == 0) return TGS_OK;
+    if (P < 0) return fail(TGS_ERR_INVALID, "bad sizes");
+    if (int r = check_view(w, 0, VIEW_RENDER_BWD, false)) return r;
+    const ViewArgs v = view_args(w);
+    return enqueue_render_bwd(opt, st, 0, carve_frame(GeomShape{(size_t)P, false, false}, v, w.R, nullptr, w.binning_buffer, w.img_buffer), v, w.R, w.dL_dpix);
+}
+
+// the shared per-Gaussian stage of a group of views of tgs_forward_views: one launch on the group's first stream
+static int enqueue_group_preprocess(const Opts& opt, hipStream_t st, const Model& m, int prefiltered, const tgs_view_t* views, int v0, int nv)
+{
+    const FwdIn in = fwd_in(m, opt, prefiltered);
+    FwdViews fv;
+    memset(&fv, 0, sizeof(fv));
+    fv.n = nv;
+    for (int k = 0; k < nv; k++) {
+        const tgs_view_t& w = views[v0 + k];
+        const ViewArgs v = view_args(w);
+        FwdView& o = fv.v[k];
+        if (int r = frame_cam(o.cam, v, m.scale_modifier)) return r;
+        if (geom_carve(o.g, nullptr, (size_t)m.P, m.has_sh(), m.has_sr()) > w.geom_bytes || img_carve(o.s, nullptr, v.N(), v.T()) > w.img_bytes)
+            return fail(TGS_ERR_ALLOC, "view %d: state buffers smaller than tgs_state_sizes()", v0 + k);
+        const FrameBuffers fb = carve_frame(m.shape(), v, 0, w.geom_buffer, nullptr, w.img_buffer);
+        o.g = fb.g; o.s = fb.s;
+        o.radii = w.radii_out;
+    }
+    return stage(st, TGS_STAGE_PREPROCESS_FWD, "preprocess_batch", 0, [&] { launch_preprocess_fwd_batch(st, in, fv); });
+}
+
+// allocation "callback" of the *_views entry points: hands out the caller's preset buffers
+static void* alloc_preset(void* ctx, int which, size_t bytes)
+{
+    const tgs_view_t* v = (const tgs_view_t*)ctx;
+    if (which == TGS_BUF_GEOM) return bytes <= v->geom_bytes ? const_cast<void*>(v->geom_buffer) : nullptr;
+    if (which == TGS_BUF_BINNING) return bytes <= v->binning_bytes ? const_cast<void*>(v->binning_buffer) : nullptr;
+    if (which == TGS_BUF_IMAGE) return bytes <= v->img_bytes ? const_cast<void*>(v->img_buffer) : nullptr;
+    return nullptr;
 }
 
 extern "C" {
@@ -236,193 +632,6 @@ int tgs_profile_end(double* ms_sum, int64_t* counts)
 }
 const char* tgs_last_error(void) { return g_err; }
 
-// pinned Meta staging + event of the speculative forward: one per host thread AND device (an event belongs to the device that was
-// current when it was created; a thread that renders on cuda:0 and then on cuda:1 gets a slot for each)
-struct SpecSlot { Meta* meta; hipEvent_t ready; };
-static SpecSlot* spec_slot()
-{
-    thread_local std::vector<SpecSlot> slots;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return nullptr;
-    if ((size_t)dev >= slots.size()) slots.resize((size_t)dev + 1, SpecSlot{nullptr, nullptr});
-    SpecSlot& slot = slots[(size_t)dev];
-    if (!slot.meta) {
-        if (hipHostMalloc((void**)&slot.meta, sizeof(Meta), hipHostMallocDefault) != hipSuccess) { slot.meta = nullptr; return nullptr; }
-        if (hipEventCreateWithFlags(&slot.ready, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(slot.meta); slot.meta = nullptr; return nullptr; }
-    }
-    return &slot;
-}
-
-// r_capacity < 0: the reference's protocol (read R back, then size the binning buffer).  r_capacity >= 0: sync-free --
-// the binning buffer is sized for r_capacity instances before anything runs and nothing is read back.
-// tgs_set_render_streams: k_render_fwd of view k goes to render stream k mod n (behind an event on the view's own stream)
-static thread_local std::vector<hipStream_t> t_render_streams;
-static thread_local int64_t t_last_nonempty = -1;           // tgs_last_nonempty_tiles (legacy read-out; tgs_frame_info_t carries it explicitly)
-static uint32_t bounded_tiles(const Opts& o, size_t T) { return (o.tile_bound > 0 && (uint64_t)o.tile_bound < (uint64_t)T) ? (uint32_t)o.tile_bound : (uint32_t)T; }
-// bound on the tiles with >= LIGHT_MAX instances (the 1024-thread render kernel's grid): the caller's mid_bound, else the tile bound
-static uint32_t bounded_mid(const Opts& o, size_t T)
-{
-    const uint32_t tb = bounded_tiles(o, T);
-    // the SAME predicate as the forward's (forward_impl: `classes`): a mid bound is only enforced -- by k_scan, which rejects a frame with more
-    // such tiles -- together with a tile bound below the tile count; without that enforcement the backward must not size its grid by it
-    return (tb < (uint32_t)T && o.mid_bound > 0 && (uint64_t)o.mid_bound < tb) ? (uint32_t)o.mid_bound : tb;
-}
-
-static int64_t forward_impl(const Opts& opt, Meta* host_meta, hipStream_t render_stream, tgs_frame_info_t* info, int preprocessed, int64_t r_capacity, int64_t* speculative_true_R, tgs_alloc_fn alloc, void* alloc_ctx, void* stream, int P, int D, int M, const float* background, int width,
-                    int height, const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-                    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                    const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
-                    int prefiltered, float* out_color, int* radii, int debug)
-{
-    const bool async = r_capacity >= 0;
-    t_last_nonempty = -1;                                   // (known again once this call has read the frame's Meta)
-    if (info) { info->num_rendered = -1; info->nonempty_tiles = -1; info->flags = 0; info->mid_tiles = -1; }
-    if (r_capacity > 0x7fffffffll) return fail(TGS_ERR_INVALID, "r_capacity exceeds 2^31-1");
-    hipStream_t st = (hipStream_t)stream;
-    g_err[0] = 0;
-    if (!alloc) return fail(TGS_ERR_INVALID, "alloc callback is NULL");
-    if (P < 0 || width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "bad sizes P=%d W=%d H=%d", P, width, height);
-    if (P == 0) {   // rasterize_points.cu:81: nothing runs, the image keeps its zero fill (empty inputs have no pointers to check)
-        if (!out_color) return fail(TGS_ERR_INVALID, "NULL required pointer");
-        HIP_TRY(hipMemsetAsync(out_color, 0, 3 * (size_t)width * height * sizeof(float), st));
-        if (host_meta) memset(host_meta, 0, sizeof(Meta));   // (pinned host memory: no kernel of this frame writes it)
-        if (info && !(async && !speculative_true_R)) { info->num_rendered = 0; info->nonempty_tiles = 0; info->mid_tiles = 0; }
-        if (async) {   // the caller still gets a (zeroed) Meta to query
-            ImgState s0;
-            const size_t bytes = img_carve(s0, nullptr, (size_t)width * height, (size_t)((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE));
-            char* ip = (char*)alloc(alloc_ctx, TGS_BUF_IMAGE, bytes);
-            if (!ip) return fail(TGS_ERR_ALLOC, "state buffer allocation failed");
-            HIP_TRY(hipMemsetAsync(ip, 0, 256, st));
-        }
-        return 0;
-    }
-    if ((shs == nullptr) == (colors_precomp == nullptr)) return fail(TGS_ERR_INVALID, "provide exactly one of shs / colors_precomp");
-    const bool has_sr = scales != nullptr && rotations != nullptr;
-    if (has_sr == (cov3D_precomp != nullptr) || (scales == nullptr) != (rotations == nullptr))
-        return fail(TGS_ERR_INVALID, "provide exactly one of (scales, rotations) / cov3D_precomp");
-    if (shs && (D < 0 || D > 3 || M < (D + 1) * (D + 1))) return fail(TGS_ERR_INVALID, "SH degree %d needs M >= %d (M=%d)", D, (D + 1) * (D + 1), M);
-    if (!background || !means3D || !opacities || !viewmatrix || !projmatrix || !cam_pos || !out_color)
-        return fail(TGS_ERR_INVALID, "NULL required pointer");
-    const CamParams cam = make_cam(viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, scale_modifier, width, height);
-    if (cam.gx > 65535u || cam.gy > 65535u) return fail(TGS_ERR_INVALID, "image too large");
-    const size_t N = (size_t)width * height, T = (size_t)cam.gx * cam.gy;
-    const bool has_sh = shs != nullptr;
-
-    const uint32_t sort_cap = opt.sort_cap;
-    GeomState g; ImgState s; BinState b;
-    const size_t geom_bytes = geom_carve(g, nullptr, (size_t)P, has_sh, has_sr);
-    const size_t img_bytes = img_carve(s, nullptr, N, T);
-    char* geom_ptr = (char*)alloc(alloc_ctx, TGS_BUF_GEOM, geom_bytes);
-    char* img_ptr = (char*)alloc(alloc_ctx, TGS_BUF_IMAGE, img_bytes);
-    if (!geom_ptr || !img_ptr) return fail(TGS_ERR_ALLOC, "state buffer allocation failed");
-    geom_carve(g, geom_ptr, (size_t)P, has_sh, has_sr);
-    img_carve(s, img_ptr, N, T);
-
-    // Meta sits at the head of the image buffer; k_preprocess_fwd* clears it itself (block_sum_tiles: nothing else writes Meta before
-    // k_scan), everything else is written before it is read -- no memset launch in front of a frame
-
-    FwdIn in;
-    in.P = P; in.D = D; in.M = M; in.means3D = means3D; in.shs = shs; in.colors_precomp = colors_precomp; in.opacities = opacities;
-    in.scales = scales; in.rotations = rotations; in.cov3D_precomp = cov3D_precomp; in.background = background;
-    in.prefiltered = prefiltered; in.out_color = out_color; in.radii = radii; in.prune = opt.prune;
-
-    uint64_t R = 0;
-    Meta meta;
-    memset(&meta, 0, sizeof(meta));
-    if (!preprocessed) {
-        STAGE_BEGIN(TGS_STAGE_PREPROCESS_FWD);
-        launch_preprocess_fwd(st, in, cam, g, s);
-        STAGE_CHECK("preprocess", TGS_STAGE_PREPROCESS_FWD);
-    }
-    SpecSlot* spec = nullptr;
-    if (async && speculative_true_R) {
-        spec = spec_slot();
-        if (!spec) return fail(TGS_ERR_HIP, "pinned staging for the speculative forward could not be allocated");
-    }
-    // sync-free grids cover `tb` tiles (the caller's bound on the tiles with instances, or all of them); k_scan rejects a frame with more
-    const uint32_t tb = async ? bounded_tiles(opt, T) : (uint32_t)T;
-    const bool classes = async && tb < T;                   // class bounds come with a tile bound only
-    const uint32_t hb = (classes && opt.heavy_bound > 0 && (uint64_t)opt.heavy_bound < tb) ? (uint32_t)opt.heavy_bound : tb;
-    const uint32_t mb = (classes && opt.mid_bound > 0 && (uint64_t)opt.mid_bound < tb) ? (uint32_t)opt.mid_bound : tb;
-    STAGE_BEGIN(TGS_STAGE_SCAN);
-    launch_bin_count(st, P, g, s, cam.gx, (uint32_t)T);
-    launch_scan(st, g, s, (uint32_t)n_blocks((size_t)P), (uint32_t)T, sort_cap, async ? (unsigned long long)r_capacity : ~0ull, tb, hb, mb,
-                spec ? spec->meta : host_meta, opt.light);
-    STAGE_CHECK("scan", TGS_STAGE_SCAN);
-    if (spec) {
-        // speculative synchronous forward: k_scan itself has written Meta into the pinned host slot; the event marks its end, the remaining
-        // stages are enqueued against the guessed capacity without waiting, and only then the host waits for the event -- the GPU never
-        // idles behind the read-back, and no copy sits in the stream
-        HIP_TRY(hipEventRecord(spec->ready, st));
-    }
-    if (!async) {
-        // the one host synchronisation of the forward pass (rasterizer_impl.cu:280-281): R sizes the binning buffer
-        HIP_TRY(hipMemcpyAsync(&meta, s.meta, sizeof(Meta), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (meta.error & 1u) return fail(TGS_ERR_PREFILTERED, "Point is filtered although prefiltered is set. This shouldn't happen!");
-        R = meta.R;
-        if (R > 0x7fffffffull) return fail(TGS_ERR_TOO_MANY, "%llu tile instances exceed 2^31-1", (unsigned long long)R);
-        t_last_nonempty = (int64_t)meta.n_nonempty;
-        if (info) { info->num_rendered = (int64_t)meta.R; info->nonempty_tiles = (int64_t)meta.n_nonempty; info->flags = (int32_t)meta.error; info->mid_tiles = (int32_t)meta.n_mid; }
-    } else {
-        R = (uint64_t)r_capacity;
-    }
-    const size_t bin_bytes = bin_carve(b, nullptr, (size_t)R);
-    char* bin_ptr = (char*)alloc(alloc_ctx, TGS_BUF_BINNING, bin_bytes);
-    if (!bin_ptr) return fail(TGS_ERR_ALLOC, "binning buffer allocation failed");
-    bin_carve(b, bin_ptr, (size_t)R);
-    const Meta* known = async ? nullptr : &meta;
-
-    if (R > 0) {
-        STAGE_BEGIN(TGS_STAGE_SCATTER);
-        launch_scatter(st, P, g, s, b, cam.gx, (uint32_t)T);
-        STAGE_CHECK("scatter", TGS_STAGE_SCATTER);
-    }
-    if (R > 0) {
-        STAGE_BEGIN(TGS_STAGE_TILE_SORT);
-        launch_tile_sort(st, g, s, b, cam.gx, (uint32_t)T, R, known, sort_cap, tb, hb, mb);
-        STAGE_CHECK("tile_sort", TGS_STAGE_TILE_SORT);
-    }
-    hipStream_t rst = st;
-    if (render_stream && render_stream != st && !spec) {     // binning and compositing on different streams (tgs_set_render_streams)
-        hipEvent_t binned;
-        HIP_TRY(hipEventCreateWithFlags(&binned, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(binned, st));
-        HIP_TRY(hipStreamWaitEvent(render_stream, binned, 0));
-        (void)hipEventDestroy(binned);
-        rst = render_stream;
-    }
-    STAGE_BEGIN(TGS_STAGE_RENDER_FWD);
-    launch_render_fwd(rst, s, b, width, height, cam.gx, (uint32_t)T, known, background, out_color, tb, mb, opt.light);
-    STAGE_CHECK("render", TGS_STAGE_RENDER_FWD);
-    if (spec) {
-        HIP_TRY(hipEventSynchronize(spec->ready));
-        meta = *spec->meta;
-        if (meta.error & 1u) return fail(TGS_ERR_PREFILTERED, "Point is filtered although prefiltered is set. This shouldn't happen!");
-        if (meta.R > 0x7fffffffull) return fail(TGS_ERR_TOO_MANY, "%llu tile instances exceed 2^31-1", (unsigned long long)meta.R);
-        *speculative_true_R = (int64_t)meta.R;
-        t_last_nonempty = (int64_t)meta.n_nonempty;
-        if (info) { info->num_rendered = (int64_t)meta.R; info->nonempty_tiles = (int64_t)meta.n_nonempty; info->flags = (int32_t)(meta.error & ~META_ERR_CAPACITY); info->mid_tiles = (int32_t)meta.n_mid; }
-        if ((meta.error & META_ERR_CAPACITY) || meta.pad[0] != 0u) {     // (pad[0]: more tiles with instances than the caller's bound, k_scan)
-            // the guess was too small: every kernel behind the scan returned at
-            // once; clear the flag and run those stages again with the exact sizes, as tgs_forward does
-            HIP_TRY(hipMemsetAsync(&s.meta->error, 0, sizeof(uint32_t), st));
-            R = meta.R;
-            const size_t exact_bytes = bin_carve(b, nullptr, (size_t)R);
-            char* exact_ptr = (char*)alloc(alloc_ctx, TGS_BUF_BINNING, exact_bytes);
-            if (!exact_ptr) return fail(TGS_ERR_ALLOC, "binning buffer allocation failed");
-            bin_carve(b, exact_ptr, (size_t)R);
-            if (R > 0) {
-                launch_scatter(st, P, g, s, b, cam.gx, (uint32_t)T);
-                launch_tile_sort(st, g, s, b, cam.gx, (uint32_t)T, R, &meta, sort_cap, (uint32_t)T, (uint32_t)T, (uint32_t)T);
-            }
-            launch_render_fwd(st, s, b, width, height, cam.gx, (uint32_t)T, &meta, background, out_color, (uint32_t)T, (uint32_t)T, opt.light);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return (int64_t)R;
-}
-
 int64_t tgs_forward(tgs_alloc_fn alloc, void* alloc_ctx, void* stream, int P, int D, int M, const float* background, int width,
                     int height, const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
                     const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
@@ -440,13 +649,11 @@ int64_t tgs_forward_opt(const tgs_options_t* o, int mode, int64_t r, tgs_frame_i
                         float* out_color, int* radii, int debug)
 {
     const Opts opt = resolve_options(o);
-    int64_t true_R = 0;
-    if (mode == TGS_FWD_SYNC) r = -1;
-    else if (mode != TGS_FWD_ASYNC && mode != TGS_FWD_SPECULATIVE) return fail(TGS_ERR_INVALID, "tgs_forward_opt: unknown mode %d", mode);
-    else if (r < 0) return fail(TGS_ERR_INVALID, "r_capacity / r_guess must be >= 0");
-    return forward_impl(opt, nullptr, nullptr, info, 0, r, mode == TGS_FWD_SPECULATIVE ? &true_R : nullptr, alloc, alloc_ctx, stream, P, D, M, background, width, height,
-                        means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
-                        prefiltered, out_color, radii, debug);
+    if (mode != TGS_FWD_SYNC && mode != TGS_FWD_ASYNC && mode != TGS_FWD_SPECULATIVE) return fail(TGS_ERR_INVALID, "tgs_forward_opt: unknown mode %d", mode);
+    if (mode != TGS_FWD_SYNC && r < 0) return fail(TGS_ERR_INVALID, "r_capacity / r_guess must be >= 0");
+    const FwdCall c{mode, r, info, {alloc, alloc_ctx}, (hipStream_t)stream, prefiltered, out_color, radii, debug, nullptr, nullptr, false};
+    return forward_impl(opt, c, Model{P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp},
+                        ViewArgs{background, width, height, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy});
 }
 
 int64_t tgs_forward_async(int64_t r_capacity, tgs_alloc_fn alloc, void* alloc_ctx, void* stream, int P, int D, int M, const float* background,
@@ -492,53 +699,6 @@ int tgs_frame_status(void* stream, const void* img_buffer, int64_t* num_rendered
     return TGS_OK;
 }
 
-// strict: tgs_backward / tgs_backward_accumulate as the reference's Rasterizer::backward declares them (every output required);
-// tgs_backward_opt: the outputs its caller discards may be NULL (dL_dconic; dL_dcolor with shs; dL_dcov3D with scales + rotations)
-static int backward_impl(bool strict, const Opts& opt, int accumulate, void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height, const float* means3D,
-                 const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                 const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                 float tan_fovy, const int* radii, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
-                 const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-                 float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug)
-{
-    hipStream_t st = (hipStream_t)stream;
-    g_err[0] = 0;
-    if (P == 0) return TGS_OK;
-    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "bad sizes");
-    const bool has_sh = shs != nullptr, has_sr = scales != nullptr && rotations != nullptr;
-    if (has_sh == (colors_precomp != nullptr)) return fail(TGS_ERR_INVALID, "provide exactly one of shs / colors_precomp");
-    if (has_sr == (cov3D_precomp != nullptr)) return fail(TGS_ERR_INVALID, "provide exactly one of (scales, rotations) / cov3D_precomp");
-    if (!geom_buffer || !binning_buffer || !img_buffer || !radii || !dL_dpix || !dL_dmean2D || !dL_dopacity || !dL_dmean3D ||
-        (has_sh && !dL_dsh) || (!has_sh && !dL_dcolor) || (!has_sr && !dL_dcov3D) ||
-        (strict && (!dL_dconic || (!accumulate && (!dL_dcolor || !dL_dcov3D)))))
-        return fail(TGS_ERR_INVALID, "NULL required pointer");
-    const CamParams cam = make_cam(viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier, width, height);
-    const size_t N = (size_t)width * height, T = (size_t)cam.gx * cam.gy;
-    GeomState g; ImgState s; BinState b;
-    geom_carve(g, (char*)geom_buffer, (size_t)P, has_sh, has_sr);
-    img_carve(s, (char*)img_buffer, N, T);
-    bin_carve(b, (char*)binning_buffer, (size_t)R);
-
-    BwdIn in;
-    in.P = P; in.D = D; in.M = M; in.means3D = means3D; in.shs = shs; in.colors_precomp = colors_precomp; in.scales = scales;
-    in.rotations = rotations; in.cov3D_precomp = cov3D_precomp; in.background = background; in.radii = radii; in.dL_dpix = dL_dpix;
-    in.dL_dmean2D = dL_dmean2D; in.dL_dconic = dL_dconic; in.dL_dopacity = dL_dopacity; in.dL_dcolor = dL_dcolor;
-    in.dL_dmean3D = dL_dmean3D; in.dL_dcov3D = dL_dcov3D; in.dL_dsh = dL_dsh; in.dL_dscale = dL_dscale; in.dL_drot = dL_drot;
-    in.accumulate = accumulate;
-    in.meta = s.meta;
-    in.block0 = 0; in.nblocks = 0;
-
-    if (R > 0) {
-        STAGE_BEGIN(TGS_STAGE_RENDER_BWD);
-        launch_render_bwd(st, s, b, width, height, cam.gx, bounded_tiles(opt, T), background, dL_dpix, opt.deterministic, bounded_mid(opt, T), opt.light, (uint32_t)T);
-        STAGE_CHECK("render_bwd", TGS_STAGE_RENDER_BWD);
-    }
-    STAGE_BEGIN(TGS_STAGE_PREPROCESS_BWD);
-    launch_preprocess_bwd(st, in, cam, g, b);
-    STAGE_CHECK("preprocess_bwd", TGS_STAGE_PREPROCESS_BWD);
-    return TGS_OK;
-}
-
 int tgs_backward(void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height, const float* means3D,
                  const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
@@ -546,9 +706,10 @@ int tgs_backward(void* stream, int P, int D, int M, int64_t R, const float* back
                  const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
                  float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug)
 {
-    return backward_impl(true, resolve_options(nullptr), 0, stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                         viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D,
-                         dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug);
+    return backward_impl(true, resolve_options(nullptr), 0, (hipStream_t)stream, debug,
+                         Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
+                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy},
+                         BwdArgs{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot});
 }
 
 int tgs_backward_opt(const tgs_options_t* o, int accumulate, void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height,
@@ -558,9 +719,10 @@ int tgs_backward_opt(const tgs_options_t* o, int accumulate, void* stream, int P
                      float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                      int debug)
 {
-    return backward_impl(false, resolve_options(o), accumulate ? 1 : 0, stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
-                         cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D,
-                         dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug);
+    return backward_impl(false, resolve_options(o), accumulate ? 1 : 0, (hipStream_t)stream, debug,
+                         Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
+                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy},
+                         BwdArgs{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot});
 }
 
 int tgs_backward_accumulate(void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height, const float* means3D,
@@ -570,28 +732,19 @@ int tgs_backward_accumulate(void* stream, int P, int D, int M, int64_t R, const 
                             const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
                             float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug)
 {
-    return backward_impl(true, resolve_options(nullptr), 1, stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                         viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D,
-                         dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug);
+    return backward_impl(true, resolve_options(nullptr), 1, (hipStream_t)stream, debug,
+                         Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
+                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy},
+                         BwdArgs{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot});
 }
 
 void tgs_state_sizes(int P, int width, int height, int has_sh, int has_scale_rot, int64_t r_capacity, size_t sizes3[3])
 {
-    GeomState g; ImgState s; BinState b;
-    const size_t gx = (size_t)((width + TILE - 1) / TILE), gy = (size_t)((height + TILE - 1) / TILE);
-    sizes3[TGS_BUF_GEOM] = geom_carve(g, nullptr, (size_t)(P > 0 ? P : 0), has_sh != 0, has_scale_rot != 0);
-    sizes3[TGS_BUF_BINNING] = bin_carve(b, nullptr, (size_t)(r_capacity > 0 ? r_capacity : 0));
-    sizes3[TGS_BUF_IMAGE] = img_carve(s, nullptr, (size_t)width * height, gx * gy);
-}
-
-// allocation "callback" of the *_views entry points: hands out the caller's preset buffers
-static void* alloc_preset(void* ctx, int which, size_t bytes)
-{
-    const tgs_view_t* v = (const tgs_view_t*)ctx;
-    if (which == TGS_BUF_GEOM) return bytes <= v->geom_bytes ? const_cast<void*>(v->geom_buffer) : nullptr;
-    if (which == TGS_BUF_BINNING) return bytes <= v->binning_bytes ? const_cast<void*>(v->binning_buffer) : nullptr;
-    if (which == TGS_BUF_IMAGE) return bytes <= v->img_bytes ? const_cast<void*>(v->img_buffer) : nullptr;
-    return nullptr;
+    FrameBuffers fb;
+    const ViewArgs v{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
+    sizes3[TGS_BUF_GEOM] = geom_carve(fb.g, nullptr, (size_t)(P > 0 ? P : 0), has_sh != 0, has_scale_rot != 0);
+    sizes3[TGS_BUF_BINNING] = bin_carve(fb.b, nullptr, (size_t)(r_capacity > 0 ? r_capacity : 0));
+    sizes3[TGS_BUF_IMAGE] = img_carve(fb.s, nullptr, v.N(), v.T());
 }
 
 void tgs_set_tile_bound(int64_t n) { t_tile_bound = n > 0 ? n : 0; }
@@ -623,10 +776,7 @@ int tgs_forward_views_opt(const tgs_options_t* o, void* const* streams, int n_st
     g_err[0] = 0;
     if (n_views == 0) return TGS_OK;
     if (!streams || n_streams <= 0 || n_views < 0 || !views || r_capacity < 0) return fail(TGS_ERR_INVALID, "bad arguments");
-    const int debug = 0;
-    const bool has_sh = shs != nullptr, has_sr = scales != nullptr && rotations != nullptr;
-    // views that can share the per-Gaussian stage: same model, the usual case (P > 0, all pointers there; the rest is
-    // validated by forward_impl below)
+    const Model m{P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp};
     // Views per launch of the shared per-Gaussian stage (tgs_set_forward_group, TGS_FORWARD_GROUP; default 2).  More views per launch
     // read the SH rows -- more than half of what the stage reads -- fewer times: 51 us for one view, 78 / 125 / 218 us for 2 / 4 / 8.
     // But the views of a group start their remaining stages together, and with four streams that costs more than the bytes save
@@ -638,45 +788,17 @@ int tgs_forward_views_opt(const tgs_options_t* o, void* const* streams, int n_st
     bool per_view_colors = false;
     for (int k = 0; k < n_views; k++) per_view_colors = per_view_colors || views[k].colors_precomp != nullptr;
     if (per_view_colors && shs) return fail(TGS_ERR_INVALID, "provide exactly one of shs / colors_precomp");
-    const bool batched = !per_view_colors && group > 1 && n_views > 1 && P > 0 && means3D && opacities && ((shs == nullptr) != (colors_precomp == nullptr)) && (has_sr != (cov3D_precomp != nullptr)) &&
-                         (!has_sh || (D >= 0 && D <= 3 && M >= (D + 1) * (D + 1)));
+    // views that share the per-Gaussian stage: same colours, a model the forward accepts (any other takes the single-view route, whose
+    // forward names the error)
+    const bool batched = !per_view_colors && group > 1 && n_views > 1 && P > 0 && check_model(m, MODEL_FORWARD) == TGS_OK;
     for (int v0 = 0; v0 < n_views; v0 += group) {
         const int nv = n_views - v0 < group ? n_views - v0 : group;
         hipStream_t st0 = (hipStream_t)streams[v0 % n_streams];
         hipEvent_t pre_done = nullptr;
-        for (int k = 0; k < nv; k++) {
-            const tgs_view_t& v = views[v0 + k];
-            if (!v.geom_buffer || !v.binning_buffer || !v.img_buffer || !v.out_color || !v.background || !v.viewmatrix || !v.projmatrix || !v.campos ||
-                v.width <= 0 || v.height <= 0)
-                return fail(TGS_ERR_INVALID, "view %d: bad sizes or NULL required pointer", v0 + k);
-        }
+        for (int k = 0; k < nv; k++)
+            if (int r = check_view(views[v0 + k], v0 + k, VIEW_FORWARD, false)) return r;
         if (batched) {
-            FwdIn in;
-            memset(&in, 0, sizeof(in));
-            in.P = P; in.D = D; in.M = M; in.means3D = means3D; in.shs = shs; in.colors_precomp = colors_precomp; in.opacities = opacities;
-            in.scales = scales; in.rotations = rotations; in.cov3D_precomp = cov3D_precomp; in.prefiltered = prefiltered;
-            in.prune = opt0.prune;
-            FwdViews fv;
-            memset(&fv, 0, sizeof(fv));
-            fv.n = nv;
-            for (int k = 0; k < nv; k++) {
-                const tgs_view_t& v = views[v0 + k];
-                FwdView& o = fv.v[k];
-                o.cam = make_cam(v.viewmatrix, v.projmatrix, v.campos, v.tan_fovx, v.tan_fovy, scale_modifier, v.width, v.height);
-                if (o.cam.gx > 65535u || o.cam.gy > 65535u) return fail(TGS_ERR_INVALID, "image too large");
-                const size_t N = (size_t)v.width * v.height, T = (size_t)o.cam.gx * o.cam.gy;
-                if (geom_carve(o.g, nullptr, (size_t)P, has_sh, has_sr) > v.geom_bytes || img_carve(o.s, nullptr, N, T) > v.img_bytes)
-                    return fail(TGS_ERR_ALLOC, "view %d: state buffers smaller than tgs_state_sizes()", v0 + k);
-                geom_carve(o.g, (char*)v.geom_buffer, (size_t)P, has_sh, has_sr);
-                img_carve(o.s, (char*)v.img_buffer, N, T);
-                o.radii = v.radii_out;
-            }
-            {
-                hipStream_t st = st0;
-                STAGE_BEGIN(TGS_STAGE_PREPROCESS_FWD);
-                launch_preprocess_fwd_batch(st, in, fv);
-                STAGE_CHECK("preprocess_batch", TGS_STAGE_PREPROCESS_FWD);
-            }
+            if (int r = enqueue_group_preprocess(opt0, st0, m, prefiltered, views, v0, nv)) return r;
             if (n_streams > 1) {
                 HIP_TRY(hipEventCreateWithFlags(&pre_done, hipEventDisableTiming));
                 HIP_TRY(hipEventRecord(pre_done, st0));
@@ -687,13 +809,10 @@ int tgs_forward_views_opt(const tgs_options_t* o, void* const* streams, int n_st
             hipStream_t st = (hipStream_t)streams[(v0 + k) % n_streams];
             if (pre_done && st != st0) HIP_TRY(hipStreamWaitEvent(st, pre_done, 0));
             hipStream_t render_stream = t_render_streams.empty() ? nullptr : t_render_streams[(size_t)(v0 + k) % t_render_streams.size()];
-            Opts opt = opt0;                                // the bounds of a view travel in its tgs_view_t
-            opt.tile_bound = v.tile_bound > 0 ? v.tile_bound : 0;
-            opt.heavy_bound = v.heavy_bound > 0 ? v.heavy_bound : 0; opt.mid_bound = v.mid_bound > 0 ? v.mid_bound : 0;
-            const int64_t r = forward_impl(opt, (Meta*)v.host_meta, render_stream, nullptr, batched ? 1 : 0, r_capacity, nullptr, alloc_preset, &v, st, P, D, M, v.background, v.width, v.height, means3D, shs,
-                                           v.colors_precomp ? v.colors_precomp : colors_precomp,
-                                           opacities, scales, scale_modifier, rotations, cov3D_precomp, v.viewmatrix, v.projmatrix, v.campos, v.tan_fovx, v.tan_fovy,
-                                           prefiltered, v.out_color, v.radii_out, 0);
+            Model mv = m;
+            if (v.colors_precomp) mv.colors_precomp = v.colors_precomp;
+            const FwdCall c{TGS_FWD_ASYNC, r_capacity, nullptr, {alloc_preset, &v}, st, prefiltered, v.out_color, v.radii_out, 0, (Meta*)v.host_meta, render_stream, batched};
+            const int64_t r = forward_impl(view_options(opt0, v), c, mv, view_args(v));
             if (r < 0) { if (pre_done) (void)hipEventDestroy(pre_done); return (int)r; }
             v.R = r;
         }
@@ -701,9 +820,6 @@ int tgs_forward_views_opt(const tgs_options_t* o, void* const* streams, int n_st
     }
     return TGS_OK;
 }
-
-static int backward_render_impl(const Opts& opt, void* stream, int P, int64_t R, const float* background, int width, int height, const void* binning_buffer,
-                                const void* img_buffer, const float* dL_dpix);
 
 int tgs_backward_render_views(void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views)
 {
@@ -716,11 +832,7 @@ int tgs_backward_render_views_opt(const tgs_options_t* o, void* const* streams, 
     if (!streams || n_streams <= 0 || n_views < 0 || !views) return fail(TGS_ERR_INVALID, "bad arguments");
     const Opts opt0 = resolve_options(o, true);
     for (int k = 0; k < n_views; k++) {
-        const tgs_view_t& v = views[k];
-        Opts opt = opt0;
-        opt.tile_bound = v.tile_bound > 0 ? v.tile_bound : 0;
-        opt.mid_bound = v.mid_bound > 0 ? v.mid_bound : 0;
-        const int r = backward_render_impl(opt, streams[k % n_streams], P, v.R, v.background, v.width, v.height, v.binning_buffer, v.img_buffer, v.dL_dpix);
+        const int r = backward_render_impl(view_options(opt0, views[k]), (hipStream_t)streams[k % n_streams], P, views[k]);
         if (r < 0) return r;
     }
     return TGS_OK;
@@ -729,34 +841,16 @@ int tgs_backward_render_views_opt(const tgs_options_t* o, void* const* streams, 
 int tgs_backward_render(void* stream, int P, int64_t R, const float* background, int width, int height, const void* binning_buffer,
                         const void* img_buffer, const float* dL_dpix)
 {
-    return backward_render_impl(resolve_options(nullptr), stream, P, R, background, width, height, binning_buffer, img_buffer, dL_dpix);
+    return tgs_backward_render_opt(nullptr, stream, P, R, background, width, height, binning_buffer, img_buffer, dL_dpix);
 }
 
 int tgs_backward_render_opt(const tgs_options_t* o, void* stream, int P, int64_t R, const float* background, int width, int height, const void* binning_buffer,
                             const void* img_buffer, const float* dL_dpix)
 {
-    return backward_render_impl(resolve_options(o), stream, P, R, background, width, height, binning_buffer, img_buffer, dL_dpix);
-}
-
-static int backward_render_impl(const Opts& opt, void* stream, int P, int64_t R, const float* background, int width, int height, const void* binning_buffer,
-                                const void* img_buffer, const float* dL_dpix)
-{
-    hipStream_t st = (hipStream_t)stream;
-    g_err[0] = 0;
-    const int debug = 0;
-    if (P == 0) return TGS_OK;
-    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "bad sizes");
-    if (!background || !binning_buffer || !img_buffer || !dL_dpix) return fail(TGS_ERR_INVALID, "NULL required pointer");
-    const uint32_t gx = (uint32_t)((width + TILE - 1) / TILE), gy = (uint32_t)((height + TILE - 1) / TILE);
-    ImgState s; BinState b;
-    img_carve(s, (char*)img_buffer, (size_t)width * height, (size_t)gx * gy);
-    bin_carve(b, (char*)binning_buffer, (size_t)R);
-    if (R > 0) {
-        STAGE_BEGIN(TGS_STAGE_RENDER_BWD);
-        launch_render_bwd(st, s, b, width, height, gx, bounded_tiles(opt, (size_t)gx * gy), background, dL_dpix, opt.deterministic, bounded_mid(opt, (size_t)gx * gy), opt.light, gx * gy);
-        STAGE_CHECK("render_bwd", TGS_STAGE_RENDER_BWD);
-    }
-    return TGS_OK;
+    tgs_view_t v;
+    memset(&v, 0, sizeof(v));
+    v.width = width; v.height = height; v.R = R; v.background = background; v.binning_buffer = binning_buffer; v.img_buffer = img_buffer; v.dL_dpix = dL_dpix;
+    return backward_render_impl(resolve_options(o), (hipStream_t)stream, P, v);
 }
 
 int tgs_backward_batch(void* stream, int P, int D, int M, int n_views, const tgs_view_t* views, const float* means3D, const float* shs,
@@ -782,21 +876,18 @@ int tgs_backward_batch_range_planes(void* stream, int P, int D, int M, int n_vie
 {
     hipStream_t st = (hipStream_t)stream;
     g_err[0] = 0;
-    const int debug = 0;
     if (P == 0 || n_views == 0 || count == 0) return TGS_OK;
     if (P < 0 || n_views < 0 || !views) return fail(TGS_ERR_INVALID, "bad sizes");
     if (first < 0 || count < 0 || first % PRE_BLOCK != 0 || (long long)first + count > P || ((first + count) % PRE_BLOCK != 0 && first + count != P))
         return fail(TGS_ERR_INVALID, "Gaussian range [%d, %d + %d) must start and end on multiples of %d (or end at P = %d)", first, first, count, PRE_BLOCK, P);
-    const bool has_sh = shs != nullptr, has_sr = scales != nullptr && rotations != nullptr;
-    if (has_sr == (cov3D_precomp != nullptr)) return fail(TGS_ERR_INVALID, "provide exactly one of (scales, rotations) / cov3D_precomp");
-    if (has_sh && (D < 0 || D > 3 || M < (D + 1) * (D + 1))) return fail(TGS_ERR_INVALID, "SH degree %d needs M >= %d (M=%d)", D, (D + 1) * (D + 1), M);
-    if (!means3D || !dL_dopacity || !dL_dmean3D || (has_sh && !dL_dsh) || (has_sr && (!dL_dscale || !dL_drot)) || (!has_sr && !dL_dcov3D))
+    const Model m{P, D, M, means3D, shs, nullptr, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
+    const bool has_sh = m.has_sh(), has_sr = m.has_sr();
+    if (int r = check_model(m, MODEL_BATCH_BACKWARD)) return r;
+    if (!dL_dopacity || !dL_dmean3D || (has_sh && !dL_dsh) || (has_sr && (!dL_dscale || !dL_drot)) || (!has_sr && !dL_dcov3D))
         return fail(TGS_ERR_INVALID, "NULL required pointer");
     if (dsh_plane_stride != 0 && (!has_sh || M != 16 || dsh_plane_stride < 3 * (int64_t)P || dsh_plane_stride % 4 != 0 || ((uintptr_t)dL_dsh & 15u) != 0))
         return fail(TGS_ERR_INVALID, "level-major dL_dsh needs SH colours with M = 16, a plane stride >= 3 P that is a multiple of 4 floats, and a 16-byte aligned dL_dsh");
-    BwdIn in;
-    memset(&in, 0, sizeof(in));
-    in.P = P; in.D = D; in.M = M; in.means3D = means3D; in.shs = shs; in.scales = scales; in.rotations = rotations; in.cov3D_precomp = cov3D_precomp;
+    BwdIn in = bwd_in(m);
     in.dL_dopacity = dL_dopacity; in.dL_dmean3D = dL_dmean3D; in.dL_dcov3D = has_sr ? nullptr : dL_dcov3D; in.dL_dsh = dL_dsh;
     in.dL_dscale = has_sr ? dL_dscale : nullptr; in.dL_drot = has_sr ? dL_drot : nullptr;
     in.block0 = first / PRE_BLOCK; in.nblocks = (int)n_blocks((size_t)count);
@@ -807,21 +898,15 @@ int tgs_backward_batch_range_planes(void* stream, int P, int D, int M, int n_vie
         bv.n = n_views - v0 < BATCH_VIEWS ? n_views - v0 : BATCH_VIEWS;
         for (int k = 0; k < bv.n; k++) {
             const tgs_view_t& w = views[v0 + k];
-            if (w.width <= 0 || w.height <= 0 || w.R < 0 || !w.viewmatrix || !w.projmatrix || !w.campos || !w.radii || !w.geom_buffer ||
-                !w.binning_buffer || !w.img_buffer || !w.dL_dmean2D || (!has_sh && !w.dL_dcolor))
-                return fail(TGS_ERR_INVALID, "view %d: bad sizes or NULL required pointer", v0 + k);
+            if (int r = check_view(w, v0 + k, VIEW_BATCH_BWD, has_sh)) return r;
+            const ViewArgs v = view_args(w);
+            const FrameBuffers fb = carve_frame(m.shape(), v, w.R, w.geom_buffer, w.binning_buffer, w.img_buffer);
             BatchView& o = bv.v[k];
-            o.cam = make_cam(w.viewmatrix, w.projmatrix, w.campos, w.tan_fovx, w.tan_fovy, scale_modifier, w.width, w.height);
-            ImgState s;
-            geom_carve(o.g, (char*)w.geom_buffer, (size_t)P, has_sh, has_sr);
-            img_carve(s, (char*)w.img_buffer, (size_t)w.width * w.height, (size_t)o.cam.gx * o.cam.gy);
-            bin_carve(o.b, (char*)w.binning_buffer, (size_t)w.R);
-            o.meta = s.meta; o.radii = w.radii; o.dL_dmean2D = w.dL_dmean2D; o.dL_dcolor = has_sh ? nullptr : w.dL_dcolor;
+            o.cam = v.cam(scale_modifier); o.g = fb.g; o.b = fb.b;
+            o.meta = fb.s.meta; o.radii = w.radii; o.dL_dmean2D = w.dL_dmean2D; o.dL_dcolor = has_sh ? nullptr : w.dL_dcolor;
         }
         in.accumulate = (accumulate || v0 > 0) ? 1 : 0;       // later chunks add to what the first one stored
-        STAGE_BEGIN(TGS_STAGE_PREPROCESS_BWD);
-        launch_preprocess_bwd_batch(st, in, bv);
-        STAGE_CHECK("preprocess_bwd_batch", TGS_STAGE_PREPROCESS_BWD);
+        if (int r = stage(st, TGS_STAGE_PREPROCESS_BWD, "preprocess_bwd_batch", 0, [&] { launch_preprocess_bwd_batch(st, in, bv); })) return r;
     }
     return TGS_OK;
 }
@@ -844,12 +929,10 @@ int64_t tgs_state_field(void* stream, const char* field, int P, int width, int h
 {
     hipStream_t st = (hipStream_t)stream;
     g_err[0] = 0;
-    const uint32_t gx = (uint32_t)((width + TILE - 1) / TILE), gy = (uint32_t)((height + TILE - 1) / TILE);
-    const size_t N = (size_t)width * height, T = (size_t)gx * gy;
-    GeomState g; ImgState s; BinState b;
-    geom_carve(g, (char*)geom_buffer, (size_t)P, has_sh != 0, has_scale_rot != 0);
-    img_carve(s, (char*)img_buffer, N, T);
-    bin_carve(b, (char*)binning_buffer, (size_t)R);
+    const ViewArgs v{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
+    const size_t N = v.N(), T = v.T();
+    const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, has_sh != 0, has_scale_rot != 0}, v, R, geom_buffer, binning_buffer, img_buffer);
+    const GeomState& g = fb.g; const ImgState& s = fb.s; const BinState& b = fb.b;
     const void* src = nullptr; size_t count = 0, esz = 4, stride = 0, rows = 0;   // stride != 0: `rows` rows of `esz` bytes, `stride` apart
     if (!strcmp(field, "n_contrib")) { src = s.n_contrib; count = N; }
     else if (!strcmp(field, "final_T")) { src = s.final_T; count = N; }

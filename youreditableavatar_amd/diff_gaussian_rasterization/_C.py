@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional, Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -41,39 +41,21 @@ def _load() -> C.CDLL:
     lib.tgs_sizeof_view.restype = C.c_size_t
     lib.tgs_sizeof_options.restype = C.c_size_t
     lib.tgs_last_error.restype = C.c_char_p
-    lib.tgs_forward.restype = C.c_int64
-    lib.tgs_forward.argtypes = [vp, vp, vp, it, it, it, vp, it, it, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, fl, fl, it, vp, vp, it]
-    lib.tgs_forward_async.restype = C.c_int64
-    lib.tgs_forward_async.argtypes = [C.c_int64] + lib.tgs_forward.argtypes
-    lib.tgs_forward_speculative.restype = C.c_int64
-    lib.tgs_forward_speculative.argtypes = [C.c_int64, C.POINTER(C.c_int64)] + lib.tgs_forward.argtypes
     lib.tgs_frame_status.restype = it
     lib.tgs_frame_status.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(it)]
-    lib.tgs_backward.restype = it
-    lib.tgs_backward.argtypes = [vp, it, it, it, C.c_int64, vp, it, it, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, fl, fl, vp,
-                                 vp, vp, vp, vp] + [vp] * 9 + [it]
-    lib.tgs_backward_accumulate.restype = it
-    lib.tgs_backward_accumulate.argtypes = lib.tgs_backward.argtypes
     lib.tgs_state_sizes.restype = None
     lib.tgs_state_sizes.argtypes = [it, it, it, it, it, C.c_int64, C.POINTER(C.c_size_t)]
-    lib.tgs_forward_opt.restype = C.c_int64
-    lib.tgs_forward_opt.argtypes = [vp, it, C.c_int64, vp] + lib.tgs_forward.argtypes
     lib.tgs_backward_opt.restype = it
-    lib.tgs_backward_opt.argtypes = [vp, it] + lib.tgs_backward.argtypes
-    lib.tgs_forward_views.restype = it
+    lib.tgs_backward_opt.argtypes = [vp, it, vp, it, it, it, C.c_int64, vp, it, it, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, fl, fl, vp,
+                                     vp, vp, vp, vp] + [vp] * 9 + [it]
     lib.tgs_set_render_streams.restype = it
     lib.tgs_set_render_streams.argtypes = [vp, it]
-    lib.tgs_forward_views.argtypes = [vp, it, C.c_int64, it, it, it, vp, vp, vp, vp, vp, fl, vp, vp, it, it, vp]
     lib.tgs_forward_views_opt.restype = it
-    lib.tgs_forward_views_opt.argtypes = [vp] + lib.tgs_forward_views.argtypes
-    lib.tgs_backward_render_views.restype = it
-    lib.tgs_backward_render_views.argtypes = [vp, it, it, it, vp]
+    lib.tgs_forward_views_opt.argtypes = [vp, vp, it, C.c_int64, it, it, it, vp, vp, vp, vp, vp, fl, vp, vp, it, it, vp]
     lib.tgs_backward_render_views_opt.restype = it
-    lib.tgs_backward_render_views_opt.argtypes = [vp] + lib.tgs_backward_render_views.argtypes
+    lib.tgs_backward_render_views_opt.argtypes = [vp, vp, it, it, it, vp]
     lib.tgs_backward_render_opt.restype = it
     lib.tgs_backward_render_opt.argtypes = [vp, vp, it, C.c_int64, vp, it, it, vp, vp, vp]
-    lib.tgs_backward_render.restype = it
-    lib.tgs_backward_render.argtypes = [vp, it, C.c_int64, vp, it, it, vp, vp, vp]
     lib.tgs_backward_batch.restype = it
     lib.tgs_backward_batch.argtypes = [vp, it, it, it, it, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, vp, vp, vp, it]
     lib.tgs_backward_batch_range.restype = it
@@ -83,8 +65,6 @@ def _load() -> C.CDLL:
         lib.tgs_backward_batch_range_planes.argtypes = lib.tgs_backward_batch_range.argtypes + [C.c_int64]
     except AttributeError:
         pass
-    lib.tgs_mark_visible.restype = it
-    lib.tgs_mark_visible.argtypes = [vp, it, vp, vp, vp, vp]
     lib.tgs_state_field.restype = C.c_int64
     lib.tgs_state_field.argtypes = [vp, C.c_char_p, it, it, it, C.c_int64, it, it, vp, vp, vp, vp, C.c_size_t]
     lib.tgs_set_sort_lds_cap.restype = it
@@ -187,7 +167,6 @@ def profile_end():
     if _lib.tgs_profile_end(ms, cnt) < 0:
         raise RuntimeError("profiling not active")
     return {n: (float(ms[i]), int(cnt[i])) for i, n in enumerate(STAGES)}
-_ALLOC_T = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_size_t)
 
 
 class _OptionsT(C.Structure):
@@ -195,11 +174,6 @@ class _OptionsT(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("instance_pruning", C.c_int32), ("deterministic", C.c_int32), ("forward_group", C.c_int32),
                 ("sort_lds_cap", C.c_uint32), ("tile_bound", C.c_int64), ("heavy_bound", C.c_int64), ("mid_bound", C.c_int64),
                 ("light_tiles", C.c_int32)]
-
-
-class _FrameInfoT(C.Structure):
-    """tgs_frame_info_t"""
-    _fields_ = [("num_rendered", C.c_int64), ("nonempty_tiles", C.c_int64), ("flags", C.c_int32), ("mid_tiles", C.c_int32)]
 
 
 def options(tile_bound: int = 0, pruning: Optional[bool] = None, deterministic: Optional[bool] = None, forward_group: int = 0, sort_lds_cap: int = 0,
@@ -246,59 +220,6 @@ def _require_gpu(means3D: torch.Tensor) -> torch.device:
     return means3D.device
 
 
-def _rasterize_gaussians_ctypes(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                                viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                                prefiltered, debug, r_capacity: Optional[int] = None, r_guess: Optional[int] = None, tile_bound: int = 0,
-                                pruning: Optional[bool] = None, sort_lds_cap: int = 0, info: bool = False, mid_bound: int = 0,
-                                light_tiles: Optional[bool] = None
-                                ) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    """RasterizeGaussiansCUDA (rasterize_points.cu:35-115) over ctypes -- kept for A/B measurements of the host cost
-    (``TGS_CTYPES_GLUE=1``); the module-level ``rasterize_gaussians`` is the compiled one (csrc/tgs_torch_ext.cpp).
-
-    ``r_capacity`` (extension, tgs_forward_async): render without the host read-back of num_rendered; the binning
-    buffer holds ``r_capacity`` instances and that number is returned in place of num_rendered.  Check the frame with
-    ``frame_status`` / ``frame_meta`` afterwards: a rejected frame renders as background and back-propagates nothing.
-
-    ``r_guess`` (extension, tgs_forward_speculative): the complete frame like the plain call, but the stages behind the scan are
-    enqueued against the guessed instance count while the read-back is in flight (they run again if the guess was too small).
-    Returns an 8-tuple then (also with ``info=True``): the value to pass as ``R`` to the backward / ``state_field`` first, the true
-    num_rendered and the pair (tiles with instances, tiles with >= 128 instances) last -- the exact ``tile_bound`` / ``mid_bound`` of the
-    frame's backward.  ``tile_bound`` / ``pruning`` / ``sort_lds_cap``: tgs_options_t fields."""
-    if means3D.dim() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    dev = _require_gpu(means3D)
-    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    M = int(sh.size(1)) if (sh.dim() > 1 and sh.size(0) != 0) else 0
-    with torch.cuda.device(dev):
-        out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        bufs: List[Optional[torch.Tensor]] = [torch.empty(0, dtype=torch.uint8, device=dev) for _ in range(3)]
-
-        def alloc(_ctx, which, nbytes):     # resizeFunctional (rasterize_points.cu:27-33)
-            bufs[which] = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-            return bufs[which].data_ptr()
-
-        cb = _ALLOC_T(alloc)
-        t = dict(bg=_dev_f32(background, dev, "background"), means=_dev_f32(means3D, dev, "means3D"),
-                 colors=_dev_f32(colors, dev, "colors"), opac=_dev_f32(opacity, dev, "opacity"),
-                 scales=_dev_f32(scales, dev, "scales"), rots=_dev_f32(rotations, dev, "rotations"),
-                 cov=_dev_f32(cov3D_precomp, dev, "cov3D_precomp"), view=_dev_f32(viewmatrix, dev, "viewmatrix"),
-                 proj=_dev_f32(projmatrix, dev, "projmatrix"), sh=_dev_f32(sh, dev, "sh"), campos=_dev_f32(campos, dev, "campos"))
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        args = (C.cast(cb, C.c_void_p), None, stream, P, int(degree), M, _p(t["bg"]), W, H, _p(t["means"]),
-                _p(t["sh"]), _p(t["colors"]), _p(t["opac"]), _p(t["scales"]), float(scale_modifier), _p(t["rots"]),
-                _p(t["cov"]), _p(t["view"]), _p(t["proj"]), _p(t["campos"]), float(tan_fovx), float(tan_fovy),
-                int(bool(prefiltered)), out_color.data_ptr(), _p(radii) if P else None, int(bool(debug)))
-        opt, fi = options(tile_bound=tile_bound, pruning=pruning, sort_lds_cap=sort_lds_cap, mid_bound=mid_bound, light_tiles=light_tiles), _FrameInfoT()
-        mode, rr = (2, int(r_guess)) if r_guess is not None else ((1, int(r_capacity)) if r_capacity is not None else (0, 0))
-        r = _lib.tgs_forward_opt(C.byref(opt), mode, rr, C.byref(fi), *args)
-        if r < 0:
-            raise _err(int(r))
-    if r_guess is not None or info:
-        return int(r), out_color, radii, bufs[0], bufs[1], bufs[2], int(fi.num_rendered), (int(fi.nonempty_tiles), int(fi.mid_tiles))
-    return int(r), out_color, radii, bufs[0], bufs[1], bufs[2]
-
-
 META_BYTES = 64
 FRAME_PREFILTERED, FRAME_REJECTED = 1, 2
 
@@ -342,50 +263,6 @@ def frame_status(image_buffer: torch.Tensor) -> Tuple[int, int]:
     if r < 0:
         raise _err(int(r))
     return int(R.value), int(fl.value)
-
-
-def _rasterize_gaussians_backward_ctypes(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
-                                         viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                                         geomBuffer, R, binningBuffer, imageBuffer, debug, _with_conic=False, tile_bound: int = 0,
-                                         deterministic: Optional[bool] = None, mid_bound: int = 0, light_tiles: Optional[bool] = None,
-                                         need_colors: bool = True, need_cov3D: bool = True):
-    """RasterizeGaussiansBackwardCUDA (rasterize_points.cu:117-196) over ctypes (see _rasterize_gaussians_ctypes); return order of :195.
-    ``_with_conic`` (tests only) appends the scratch tensor dL_dconic[P,2,2].  ``need_colors`` / ``need_cov3D`` False: the caller discards
-    dL_dcolors (SH path) / dL_dcov3D (scale + rotation path) -- not written, empty tensors returned (as the compiled module does)."""
-    dev = _require_gpu(means3D)
-    P = int(means3D.size(0))
-    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
-    M = int(sh.size(1)) if (sh.dim() > 1 and sh.size(0) != 0) else 0
-    with torch.cuda.device(dev):
-        e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        has_sr0 = scales is not None and scales.numel() != 0
-        want_col, want_cov = bool(need_colors) or M == 0, bool(need_cov3D) or not has_sr0
-        dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dconic = e(P, 3), e(P, 3), e(P if want_col else 0, 3), e(P if _with_conic else 0, 2, 2)
-        dL_dopacity, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations = e(P, 1), e(P if want_cov else 0, 6), e(P, M, 3), e(P, 3), e(P, 4)
-        t = dict(bg=_dev_f32(background, dev, "background"), means=_dev_f32(means3D, dev, "means3D"),
-                 colors=_dev_f32(colors, dev, "colors"), scales=_dev_f32(scales, dev, "scales"),
-                 rots=_dev_f32(rotations, dev, "rotations"), cov=_dev_f32(cov3D_precomp, dev, "cov3D_precomp"),
-                 view=_dev_f32(viewmatrix, dev, "viewmatrix"), proj=_dev_f32(projmatrix, dev, "projmatrix"),
-                 sh=_dev_f32(sh, dev, "sh"), campos=_dev_f32(campos, dev, "campos"), dL=_dev_f32(dL_dout_color, dev, "dL_dout_color"))
-        if P != 0:
-            has_sr = t["scales"] is not None
-            if not has_sr:      # the reference leaves these at zero on the cov3D_precomp path
-                dL_dscales.zero_(); dL_drotations.zero_()
-            radii_c = radii.contiguous()
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            opt = options(tile_bound=tile_bound, deterministic=deterministic, mid_bound=mid_bound, light_tiles=light_tiles)
-            r = _lib.tgs_backward_opt(C.byref(opt), 0, stream, P, int(degree), M, int(R), _p(t["bg"]), W, H, _p(t["means"]), _p(t["sh"]), _p(t["colors"]),
-                                  _p(t["scales"]), float(scale_modifier), _p(t["rots"]), _p(t["cov"]), _p(t["view"]), _p(t["proj"]),
-                                  _p(t["campos"]), float(tan_fovx), float(tan_fovy), radii_c.data_ptr(), geomBuffer.data_ptr(),
-                                  binningBuffer.data_ptr(), imageBuffer.data_ptr(), _p(t["dL"]), dL_dmeans2D.data_ptr(),
-                                  dL_dconic.data_ptr() if _with_conic else None, dL_dopacity.data_ptr(), dL_dcolors.data_ptr() if want_col else None, dL_dmeans3D.data_ptr(),
-                                  dL_dcov3D.data_ptr() if want_cov else None, dL_dsh.data_ptr() if M else None,
-                                  dL_dscales.data_ptr() if has_sr else None, dL_drotations.data_ptr() if has_sr else None,
-                                  int(bool(debug)))
-            if r < 0:
-                raise _err(int(r))
-    out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
-    return out + (dL_dconic,) if _with_conic else out
 
 
 def rasterize_gaussians_backward_accumulate(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -561,20 +438,6 @@ def rasterize_gaussians_backward_batch(views, means3D, sh, degree, scales, rotat
     return outs
 
 
-def _mark_visible_ctypes(means3D, viewmatrix, projmatrix) -> torch.Tensor:
-    """markVisible (rasterize_points.cu:198-217) over ctypes."""
-    dev = _require_gpu(means3D)
-    P = int(means3D.size(0))
-    with torch.cuda.device(dev):
-        present = torch.zeros((P,), dtype=torch.bool, device=dev)
-        if P != 0:
-            m, v, pj = _dev_f32(means3D, dev, "means3D"), _dev_f32(viewmatrix, dev, "viewmatrix"), _dev_f32(projmatrix, dev, "projmatrix")
-            r = _lib.tgs_mark_visible(torch.cuda.current_stream(dev).cuda_stream, P, _p(m), _p(v), _p(pj), present.data_ptr())
-            if r < 0:
-                raise _err(int(r))
-    return present
-
-
 _FIELD_DTYPES = {"n_contrib": torch.int32, "final_T": torch.float32, "ranges": torch.int32, "point_list": torch.int32, "block_masks": torch.int32,
                  "means2D": torch.float32, "depths": torch.float32, "conic_opacity": torch.float32, "rgb": torch.float32,
                  "tiles_touched": torch.int32, "tile_order": torch.int32, "stamps": torch.int64, "quad_masks": torch.int64}
@@ -599,9 +462,6 @@ def state_field(name: str, P: int, width: int, height: int, R: int, has_sh: bool
 
 # The reference's three exports (ext.cpp:15-19): the compiled module's functions, positional signatures of rasterize_points.h:18-67
 # (+ the keyword-only extensions r_capacity / r_guess / _with_conic documented in csrc/tgs_torch_ext.cpp).
-if os.environ.get("TGS_CTYPES_GLUE") == "1":        # A/B of the host cost only
-    rasterize_gaussians, rasterize_gaussians_backward, mark_visible = _rasterize_gaussians_ctypes, _rasterize_gaussians_backward_ctypes, _mark_visible_ctypes
-else:
-    rasterize_gaussians = _ext.rasterize_gaussians
-    rasterize_gaussians_backward = _ext.rasterize_gaussians_backward
-    mark_visible = _ext.mark_visible
+rasterize_gaussians = _ext.rasterize_gaussians
+rasterize_gaussians_backward = _ext.rasterize_gaussians_backward
+mark_visible = _ext.mark_visible
