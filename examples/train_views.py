@@ -2,11 +2,12 @@
 """A whole training step on the MI355X-native path, end to end, on synthetic data:
 
   cameras computed once (RasterCameras)  ->  8 views rendered without a per-frame host sync (SyncFreeBatch.run_views)
-  ->  the trainers' L1 + SSIM loss and its gradient for all views in one call (loss.l1_ssim_value_and_grad)
+  ->  the trainers' L1 + SSIM loss and its gradient for all views in one call (loss.l1_ssim_value_and_grad; --loss l1 / l2: the pointwise
+      pass loss.pixel_value_and_grad)
   ->  per-pixel backward per view, ONE per-Gaussian backward for the batch  ->  Adam on the Gaussian parameters.
 
 It fits a perturbed copy of a Gaussian cloud back to images rendered from the original one and prints the loss per step.
-Usage:  python examples/train_views.py [--steps 30] [--gaussians 20000] [--size 320 200] [--views 8]
+Usage:  python examples/train_views.py [--steps 30] [--gaussians 20000] [--size 320 200] [--views 8] [--loss l1+dssim|l1|l2]
 """
 import argparse
 import math
@@ -32,10 +33,10 @@ def orbit_c2w(n, radius=3.0, elevation_deg=10.0):
     return np.stack(out).astype(np.float32)
 
 
-def run(steps=30, P=20000, W=320, H=200, V=8, seed=0, device="cuda", log=print):
+def run(steps=30, P=20000, W=320, H=200, V=8, seed=0, device="cuda", log=print, loss="l1+dssim"):
     from youreditableavatar_amd import scenes
     from youreditableavatar_amd.cameras import RasterCameras
-    from youreditableavatar_amd.loss import l1_ssim_value_and_grad
+    from youreditableavatar_amd.loss import l1_ssim_value_and_grad, pixel_value_and_grad
     from youreditableavatar_amd.multiview import FlatGradients, SyncFreeBatch
     dev = torch.device(device)
     cloud = scenes.make_cloud(P, 3, seed=seed, scale_mult=2.0)
@@ -63,8 +64,8 @@ def run(steps=30, P=20000, W=320, H=200, V=8, seed=0, device="cuda", log=print):
     losses = []
 
     def upstream(images):
-        out3, grad = l1_ssim_value_and_grad(images, targets, 0.2)
-        losses.append(out3)                                 # device tensor: no host sync inside the step
+        out3, grad = l1_ssim_value_and_grad(images, targets, 0.2) if loss == "l1+dssim" else pixel_value_and_grad(images, targets, kind=loss)
+        losses.append(out3.reshape(-1))                     # device tensor ([0] = the loss): no host sync inside the step
         return grad
 
     for step in range(steps):
@@ -86,5 +87,6 @@ if __name__ == "__main__":
     ap.add_argument("--gaussians", type=int, default=20000)
     ap.add_argument("--size", type=int, nargs=2, default=[320, 200])
     ap.add_argument("--views", type=int, default=8)
+    ap.add_argument("--loss", default="l1+dssim", choices=["l1+dssim", "l1", "l2"], help="the trainers' loss_function setting (refine.py:241-247)")
     a = ap.parse_args()
-    run(a.steps, a.gaussians, a.size[0], a.size[1], a.views)
+    run(a.steps, a.gaussians, a.size[0], a.size[1], a.views, loss=a.loss)

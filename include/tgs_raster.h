@@ -399,6 +399,30 @@ int tgs_l1_ssim(void* stream, int planes, int height, int width, const float* im
  * at the loss; NULL = 1) -- the chain rule is folded into the pass instead of a separate image-sized multiply. */
 int tgs_l1_ssim_backward(void* stream, int planes, int height, int width, const float* img, const float* gt, float dssim_factor,
                          const float* upstream, float* dL_dimg, const void* workspace, size_t workspace_bytes);
+/* The same per image (loss_utils.py:60-63, `size_average=False`: one value per image of a [B,C,H,W] batch): `images` x `channels` planes,
+ * out[images][3] = (loss, ssim, l1) of each image with 1 / (channels * height * width); dL_dimg (may be NULL) receives the gradient of the
+ * SUM of the per-image losses.  The backward takes `upstream` = NULL (1), one device scalar (upstream_per_image = 0) or one device value per
+ * image (upstream_per_image = 1).  images = 1 is tgs_l1_ssim / tgs_l1_ssim_backward bit for bit.  images * channels <= 65535. */
+size_t tgs_l1_ssim_images_workspace_bytes(int images, int channels, int height, int width);
+int tgs_l1_ssim_images(void* stream, int images, int channels, int height, int width, const float* img, const float* gt, float dssim_factor,
+                       float* out, float* dL_dimg, void* workspace, size_t workspace_bytes);
+int tgs_l1_ssim_images_backward(void* stream, int images, int channels, int height, int width, const float* img, const float* gt, float dssim_factor,
+                                const float* upstream, int upstream_per_image, float* dL_dimg, const void* workspace, size_t workspace_bytes);
+
+/* The pointwise losses of the trainers' 'l1' and 'l2' settings (Edit_core/utils/loss_utils.py:17-18 l1_loss, :20-21 l2_loss; chosen in
+ * tetgs_texture/refine.py:241-244) without the SSIM passes: out[images] = per-image mean of |img - gt| (TGS_LOSS_L1) or (img - gt)^2
+ * (TGS_LOSS_L2) over elems_per_image contiguous floats; images = 1 is the reference's .mean() over everything.  dL_dimg (may be NULL)
+ * receives the gradient of the sum of the per-image values in the same pass: sign(img - gt) / elems_per_image (0 where they are equal: the
+ * reference's autograd gives abs that derivative) or 2 (img - gt) / elems_per_image.  Any 4-byte aligned pointers and any length; 16-byte aligned pointers (and, with
+ * several images, a length that is a multiple of 4) take the 16-byte path.  Sums are fixed-order: two calls give the same bits.
+ * tgs_pixel_loss_backward is the gradient pass on its own with the incoming gradient folded in: `upstream` as in
+ * tgs_l1_ssim_images_backward; it needs no workspace.  images <= 65535. */
+enum { TGS_LOSS_L1 = 0, TGS_LOSS_L2 = 1 };
+size_t tgs_pixel_loss_workspace_bytes(int images, int64_t elems_per_image);
+int tgs_pixel_loss(void* stream, int kind, int images, int64_t elems_per_image, const float* img, const float* gt, float* out, float* dL_dimg,
+                   void* workspace, size_t workspace_bytes);
+int tgs_pixel_loss_backward(void* stream, int kind, int images, int64_t elems_per_image, const float* img, const float* gt, const float* upstream,
+                            int upstream_per_image, float* dL_dimg);
 
 
 /* Hardware self-test of the wave-level 36-value reduction used by the backward render kernel:

@@ -10,10 +10,14 @@
 //   k_loss_reduce: fixed-order sum of the partials -> loss, ssim, l1 (no float atomics: reproducible);
 //   k_ssim_grad_stream : the adjoint of the same separable window applied to the three derivative maps
 //                  d loss / d x(p) = gl * sign(x - y) + gs * (conv(dM1)(p) + 2 x(p) conv(dX2)(p) + y(p) conv(dXY)(p)).
+// `images` > 1 (tgs_l1_ssim_images): the statistics kernel writes its partials plane-major, so one image's partials are one contiguous range:
+// k_loss_reduce runs one workgroup per image over that range, k_ssim_grad_stream takes image blockIdx.z / channels' upstream value.
+// The pointwise losses (l1 / l2 without the window: loss_utils.py:17-21) are k_pixel_loss at the end of the file.
 // No LDS, no barrier.  The statistics pass is bound by vector issue (53 % of its wave cycles issuing, 37 % waiting for an issue slot, 9 % for
 // memory: profiles/r05_ssim_counters.txt), the gradient pass by HBM (5 planes read with a 64 / 54 overlap + 1 written: ~5 TB/s).
 #include "tgs_device.hpp"
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 
 namespace tgs {
@@ -23,10 +27,12 @@ constexpr int NTAP = 2 * LR + 1;
 
 struct LossWin { float w[NTAP]; };
 
-// out[0] = loss, out[1] = ssim, out[2] = l1; sums in double, fixed order
+// One workgroup per image over that image's n partials: out[image][0] = loss, [1] = ssim, [2] = l1; sums in double, fixed order
 __global__ __launch_bounds__(1024) void k_loss_reduce(int n, const float2* __restrict__ partial, double inv_count, float f, float* __restrict__ out)
 {
     __shared__ double rm[16], rl[16];
+    partial += (size_t)blockIdx.x * n;
+    out += 3 * blockIdx.x;
     double a = 0.0, b = 0.0;
     for (int i = threadIdx.x; i < n; i += 1024) { const float2 p = partial[i]; a += (double)p.x; b += (double)p.y; }
     for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
@@ -235,11 +241,13 @@ __device__ __forceinline__ void grad_row(float a, float b, float c, float xo, fl
 
 __global__ __launch_bounds__(256) void k_ssim_grad_stream(int H, int W, int nstrips, const float* __restrict__ img, const float* __restrict__ gt, LossWin win,
                                                          const float* __restrict__ dM1, const float* __restrict__ dX2, const float* __restrict__ dXY,
-                                                         float gs, float gl, const float* __restrict__ upstream, float* __restrict__ grad)
+                                                         float gs, float gl, const float* __restrict__ upstream, int up_channels, float* __restrict__ grad)
 {
     StripGeom g;
     if (!strip_geom(g, H, W, nstrips)) return;
-    if (upstream) { const float u = upstream[0]; gs *= u; gl *= u; }      // d(outer)/d(loss), a device scalar: the chain rule costs no pass of its own
+    // d(outer)/d(loss), a device scalar -- or one per image (up_channels > 0: planes per image; the index is the same for the whole
+    // workgroup): the chain rule costs no pass of its own
+    if (upstream) { const float u = upstream[up_channels > 0 ? blockIdx.z / (unsigned)up_channels : 0u]; gs *= u; gl *= u; }
     float V[3][NTAP];
 #pragma unroll
     for (int m = 0; m < 3; m++)
@@ -274,6 +282,125 @@ __global__ __launch_bounds__(256) void k_ssim_grad_stream(int H, int W, int nstr
 #undef TGS_GRAD_STEP
 }
 
+// =====================================================================================================================================
+// POINTWISE losses: per-image mean |x - y| (L1) or mean (x - y)^2 (L2), value and / or gradient (loss_utils.py:17-21 and what autograd makes
+// of them).  Nothing but HBM traffic: the value pass reads two floats per element, the gradient pass reads two and writes one, the combined
+// pass does both for the price of the gradient pass.  Lane i works on consecutive addresses, 16 bytes per lane and access where the
+// pointers and the image length allow (VEC), 4 bytes where they do not (a sliced tensor, images whose length is no multiple of 4); a
+// workgroup takes PX_CHUNK float4 / floats per step with every load of the step issued before the first is used, and the grid is sized
+// to the chip (PX_GRID workgroups over all images), not to the data.  Sums: per lane in fp32 over the lane's few dozen elements, one partial
+// per wave, then k_pixel_reduce in double and in a fixed order -- no float atomics, two runs give the same bits.
+// =====================================================================================================================================
+constexpr int PX_L1 = 0, PX_L2 = 1;
+constexpr int PX_UNROLL = 4;                        // loads per map in flight per lane
+constexpr int PX_CHUNK = 256 * PX_UNROLL;           // float4 (or floats) per workgroup and step
+constexpr int PX_GRID = 2048;                       // 256 CUs x 8 workgroups
+
+template <int KIND>
+__device__ __forceinline__ float px_elem(float x, float y, float s, float& acc)
+{
+    const float d = x - y;
+    if (KIND == PX_L1) { acc += fabsf(d); return d > 0.f ? s : (d < 0.f ? -s : 0.f); }      // torch's abs backward: 0 at 0
+    acc += d * d;
+    return s * d;                                                                           // (s carries the 2)
+}
+template <int KIND, bool GRAD>
+__device__ __forceinline__ void px_one(const float& x, const float& y, float s, float& acc, float* g)
+{
+    const float r = px_elem<KIND>(x, y, s, acc);
+    if (GRAD) *g = r;
+}
+template <int KIND, bool GRAD>
+__device__ __forceinline__ void px_one(const float4& x, const float4& y, float s, float& acc, float4* g)
+{
+    float4 r;
+    r.x = px_elem<KIND>(x.x, y.x, s, acc); r.y = px_elem<KIND>(x.y, y.y, s, acc); r.z = px_elem<KIND>(x.z, y.z, s, acc); r.w = px_elem<KIND>(x.w, y.w, s, acc);
+    if (GRAD) *g = r;
+}
+
+template <int KIND, bool GRAD, typename T>
+__device__ __forceinline__ void px_span(const T* __restrict__ x, const T* __restrict__ y, T* __restrict__ g, size_t count, float s, float& acc)
+{
+    const size_t step = (size_t)gridDim.x * PX_CHUNK;
+    for (size_t c = (size_t)blockIdx.x * PX_CHUNK; c < count; c += step) {
+        const size_t i = c + threadIdx.x;
+        if (c + PX_CHUNK <= count) {                        // (the same for the whole workgroup) a full step: 2 x PX_UNROLL loads, then the arithmetic
+            T a[PX_UNROLL], b[PX_UNROLL];
+#pragma unroll
+            for (int u = 0; u < PX_UNROLL; u++) { a[u] = x[i + u * 256]; b[u] = y[i + u * 256]; }
+#pragma unroll
+            for (int u = 0; u < PX_UNROLL; u++) px_one<KIND, GRAD>(a[u], b[u], s, acc, GRAD ? g + i + u * 256 : nullptr);
+        } else {
+#pragma unroll
+            for (int u = 0; u < PX_UNROLL; u++)
+                if (i + u * 256 < count) px_one<KIND, GRAD>(x[i + u * 256], y[i + u * 256], s, acc, GRAD ? g + i + u * 256 : nullptr);
+        }
+    }
+}
+
+// grid (workgroups per image, images); partial[(image * gridDim.x + workgroup) * 4 + wave]
+template <int KIND, bool VALUE, bool GRAD, bool VEC>
+__global__ __launch_bounds__(256) void k_pixel_loss(size_t n, const float* __restrict__ img, const float* __restrict__ gt, float scale,
+                                                    const float* __restrict__ upstream, int up_per_image, float* __restrict__ grad, float* __restrict__ partial)
+{
+    const size_t base = (size_t)blockIdx.y * n;
+    float s = scale;
+    if (GRAD && upstream) s *= upstream[up_per_image ? blockIdx.y : 0u];        // the gradient arriving at the loss, folded in
+    const float* x = img + base;
+    const float* y = gt + base;
+    float* g = GRAD ? grad + base : nullptr;
+    float acc = 0.f;
+    if (VEC) {
+        const size_t n4 = n >> 2;
+        px_span<KIND, GRAD>((const float4*)x, (const float4*)y, (float4*)g, n4, s, acc);
+        const size_t t = (n4 << 2) + threadIdx.x;                               // the last n % 4 elements (a single image only)
+        if (blockIdx.x == 0 && t < n) px_one<KIND, GRAD>(x[t], y[t], s, acc, GRAD ? g + t : nullptr);
+    } else {
+        px_span<KIND, GRAD>(x, y, g, n, s, acc);
+    }
+    if (VALUE) {
+        acc = wave_sum(acc);
+        if ((threadIdx.x & 63) == 0) partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)] = acc;
+    }
+}
+
+// one workgroup per image over that image's n partials: out[image] = sum / count; double, fixed order
+__global__ __launch_bounds__(256) void k_pixel_reduce(int n, const float* __restrict__ partial, double inv_count, float* __restrict__ out)
+{
+    __shared__ double r[4];
+    partial += (size_t)blockIdx.x * n;
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) a += (double)partial[i];
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    if ((threadIdx.x & 63) == 0) r[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)((r[0] + r[1] + r[2] + r[3]) * inv_count);
+}
+
+static size_t pixel_grid_cap(int images) { return (size_t)(images < PX_GRID ? PX_GRID / images : 1); }      // workgroups per image, at most
+
+// workgroups per image: every one takes the same number of steps (+- 1 at the end), none is idle
+static unsigned pixel_blocks(int images, size_t n, bool vec)
+{
+    const size_t units = vec ? n / 4 : n;
+    const size_t chunks = units < (size_t)PX_CHUNK ? 1 : (units + PX_CHUNK - 1) / PX_CHUNK;
+    const size_t rounds = (chunks + pixel_grid_cap(images) - 1) / pixel_grid_cap(images);
+    return (unsigned)((chunks + rounds - 1) / rounds);
+}
+
+template <bool VALUE, bool GRAD>
+static void launch_pixel(hipStream_t st, int kind, int images, size_t n, const float* img, const float* gt, float scale, const float* upstream, int up_per_image,
+                         float* grad, float* partial, unsigned& blocks)
+{
+    const bool vec = (((uintptr_t)img | (uintptr_t)gt | (uintptr_t)grad) & 15) == 0 && (images == 1 || n % 4 == 0);
+    blocks = pixel_blocks(images, n, vec);
+    const dim3 grid(blocks, (unsigned)images);
+#define TGS_PX(KIND, VEC) hipLaunchKernelGGL((k_pixel_loss<KIND, VALUE, GRAD, VEC>), grid, dim3(256), 0, st, n, img, gt, scale, upstream, up_per_image, grad, partial)
+    if (kind == PX_L1) { if (vec) TGS_PX(PX_L1, true); else TGS_PX(PX_L1, false); }
+    else               { if (vec) TGS_PX(PX_L2, true); else TGS_PX(PX_L2, false); }
+#undef TGS_PX
+}
+
 static dim3 stream_grid(int planes, int height, int width, int& nstrips)
 {
     nstrips = (width + SS_OUT - 1) / SS_OUT;
@@ -295,6 +422,8 @@ static LossWin make_window()
 extern "C" {
 #include "../../include/tgs_raster.h"
 
+static_assert(tgs::PX_L1 == TGS_LOSS_L1 && tgs::PX_L2 == TGS_LOSS_L2, "loss kinds");
+
 size_t tgs_l1_ssim_workspace_bytes(int planes, int height, int width)
 {
     if (planes <= 0 || height <= 0 || width <= 0) return 0;
@@ -304,17 +433,39 @@ size_t tgs_l1_ssim_workspace_bytes(int planes, int height, int width)
     return 3 * n * sizeof(float) + waves * sizeof(float2) + 1024;
 }
 
-int tgs_l1_ssim(void* stream, int planes, int height, int width, const float* img, const float* gt, float dssim_factor, float* out3,
-                float* dL_dimg, void* workspace, size_t workspace_bytes)
+size_t tgs_l1_ssim_images_workspace_bytes(int images, int channels, int height, int width)
+{
+    if (images <= 0 || channels <= 0 || (int64_t)images * channels > 65535) return 0;
+    return tgs_l1_ssim_workspace_bytes(images * channels, height, width);
+}
+
+// What the four L1 + SSIM entry points check before any HIP call; `fn` and `outname` are the caller's own names.
+static int l1_ssim_check(const char* fn, const char* outname, const char* wsfn, int images, int channels, int height, int width, bool pointers, const void* workspace, size_t workspace_bytes)
+{
+    char msg[200];
+    if (images <= 0 || channels <= 0 || height <= 0 || width <= 0 || !pointers || !workspace) {
+        snprintf(msg, sizeof msg, "%s: positive sizes and non-NULL img / gt / %s / workspace required", fn, outname);
+        return tgs::set_error(TGS_ERR_INVALID, msg);
+    }
+    if ((int64_t)images * channels > 65535 || (height + tgs::SS_SEG - 1) / tgs::SS_SEG > 65535) {
+        snprintf(msg, sizeof msg, "%s: image too large", fn);
+        return tgs::set_error(TGS_ERR_INVALID, msg);
+    }
+    if (workspace_bytes < tgs_l1_ssim_workspace_bytes(images * channels, height, width)) {
+        snprintf(msg, sizeof msg, "%s: workspace smaller than %s()", fn, wsfn);
+        return tgs::set_error(TGS_ERR_INVALID, msg);
+    }
+    return TGS_OK;
+}
+
+// The general form: `images` images of `channels` planes each, every value and gradient scaled by 1 / (channels H W).  images = 1 is
+// tgs_l1_ssim / tgs_l1_ssim_backward: the same launches with the same arguments as before there were images.
+static int l1_ssim_forward(const char* fn, hipStream_t st, int images, int channels, int height, int width, const float* img, const float* gt, float dssim_factor,
+                           float* out, float* dL_dimg, void* workspace)
 {
     using namespace tgs;
-    hipStream_t st = (hipStream_t)stream;
-    if (planes <= 0 || height <= 0 || width <= 0 || !img || !gt || !out3 || !workspace)
-        return set_error(TGS_ERR_INVALID, "tgs_l1_ssim: positive sizes and non-NULL img / gt / out3 / workspace required");
-    if (workspace_bytes < tgs_l1_ssim_workspace_bytes(planes, height, width))
-        return set_error(TGS_ERR_INVALID, "tgs_l1_ssim: workspace smaller than tgs_l1_ssim_workspace_bytes()");
-    const size_t n = (size_t)planes * height * width;
-    if (planes > 65535) return set_error(TGS_ERR_INVALID, "tgs_l1_ssim: image too large");
+    const int planes = images * channels;
+    const size_t n = (size_t)planes * height * width, per_image = (size_t)channels * height * width;
     float* dM1 = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     float* dX2 = dM1 + n;
     float* dXY = dX2 + n;
@@ -322,37 +473,110 @@ int tgs_l1_ssim(void* stream, int planes, int height, int width, const float* im
     const LossWin win = make_window();
     int nstrips = 0;
     const dim3 sgrid = stream_grid(planes, height, width, nstrips);
-    if (sgrid.y > 65535u) return set_error(TGS_ERR_INVALID, "tgs_l1_ssim: image too large");
-    const int nblk = (int)(sgrid.x * 4 * sgrid.y * sgrid.z);
+    const int nblk = (int)(sgrid.x * 4 * sgrid.y * (unsigned)channels);         // partials per image: plane-major, so contiguous
     hipLaunchKernelGGL(k_ssim_stats_stream, sgrid, dim3(256), 0, st, height, width, nstrips, img, gt, win, dM1, dX2, dXY, partial);
-    hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(1024), 0, st, nblk, partial, 1.0 / (double)n, dssim_factor, out3);
+    hipLaunchKernelGGL(k_loss_reduce, dim3((unsigned)images), dim3(1024), 0, st, nblk, partial, 1.0 / (double)per_image, dssim_factor, out);
     if (dL_dimg) {
-        const float gs = (float)(-(double)dssim_factor / (double)n), gl = (float)((1.0 - (double)dssim_factor) / (double)n);
-        hipLaunchKernelGGL(k_ssim_grad_stream, sgrid, dim3(256), 0, st, height, width, nstrips, img, gt, win, dM1, dX2, dXY, gs, gl, (const float*)nullptr, dL_dimg);
+        const float gs = (float)(-(double)dssim_factor / (double)per_image), gl = (float)((1.0 - (double)dssim_factor) / (double)per_image);
+        hipLaunchKernelGGL(k_ssim_grad_stream, sgrid, dim3(256), 0, st, height, width, nstrips, img, gt, win, dM1, dX2, dXY, gs, gl, (const float*)nullptr, 0, dL_dimg);
     }
-    return hip_status("tgs_l1_ssim");
+    return hip_status(fn);
+}
+
+static int l1_ssim_gradient(const char* fn, hipStream_t st, int images, int channels, int height, int width, const float* img, const float* gt, float dssim_factor,
+                            const float* upstream, int upstream_per_image, float* dL_dimg, const void* workspace)
+{
+    using namespace tgs;
+    const int planes = images * channels;
+    const size_t n = (size_t)planes * height * width, per_image = (size_t)channels * height * width;
+    const float* dM1 = (const float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    const float* dX2 = dM1 + n;
+    const float* dXY = dX2 + n;
+    const LossWin win = make_window();
+    const float gs = (float)(-(double)dssim_factor / (double)per_image), gl = (float)((1.0 - (double)dssim_factor) / (double)per_image);
+    int nstrips = 0;
+    const dim3 sgrid = stream_grid(planes, height, width, nstrips);
+    hipLaunchKernelGGL(k_ssim_grad_stream, sgrid, dim3(256), 0, st, height, width, nstrips, img, gt, win, dM1, dX2, dXY, gs, gl, upstream,
+                       upstream && upstream_per_image ? channels : 0, dL_dimg);
+    return hip_status(fn);
+}
+
+int tgs_l1_ssim(void* stream, int planes, int height, int width, const float* img, const float* gt, float dssim_factor, float* out3,
+                float* dL_dimg, void* workspace, size_t workspace_bytes)
+{
+    if (const int r = l1_ssim_check("tgs_l1_ssim", "out3", "tgs_l1_ssim_workspace_bytes", 1, planes, height, width, img && gt && out3, workspace, workspace_bytes)) return r;
+    return l1_ssim_forward("tgs_l1_ssim", (hipStream_t)stream, 1, planes, height, width, img, gt, dssim_factor, out3, dL_dimg, workspace);
 }
 
 int tgs_l1_ssim_backward(void* stream, int planes, int height, int width, const float* img, const float* gt, float dssim_factor,
                          const float* upstream, float* dL_dimg, const void* workspace, size_t workspace_bytes)
 {
+    if (const int r = l1_ssim_check("tgs_l1_ssim_backward", "dL_dimg", "tgs_l1_ssim_workspace_bytes", 1, planes, height, width, img && gt && dL_dimg, workspace, workspace_bytes)) return r;
+    return l1_ssim_gradient("tgs_l1_ssim_backward", (hipStream_t)stream, 1, planes, height, width, img, gt, dssim_factor, upstream, 0, dL_dimg, workspace);
+}
+
+int tgs_l1_ssim_images(void* stream, int images, int channels, int height, int width, const float* img, const float* gt, float dssim_factor,
+                       float* out, float* dL_dimg, void* workspace, size_t workspace_bytes)
+{
+    if (const int r = l1_ssim_check("tgs_l1_ssim_images", "out", "tgs_l1_ssim_images_workspace_bytes", images, channels, height, width, img && gt && out, workspace, workspace_bytes)) return r;
+    return l1_ssim_forward("tgs_l1_ssim_images", (hipStream_t)stream, images, channels, height, width, img, gt, dssim_factor, out, dL_dimg, workspace);
+}
+
+int tgs_l1_ssim_images_backward(void* stream, int images, int channels, int height, int width, const float* img, const float* gt, float dssim_factor,
+                                const float* upstream, int upstream_per_image, float* dL_dimg, const void* workspace, size_t workspace_bytes)
+{
+    if (const int r = l1_ssim_check("tgs_l1_ssim_images_backward", "dL_dimg", "tgs_l1_ssim_images_workspace_bytes", images, channels, height, width, img && gt && dL_dimg, workspace, workspace_bytes)) return r;
+    return l1_ssim_gradient("tgs_l1_ssim_images_backward", (hipStream_t)stream, images, channels, height, width, img, gt, dssim_factor, upstream, upstream_per_image,
+                            dL_dimg, workspace);
+}
+
+size_t tgs_pixel_loss_workspace_bytes(int images, int64_t elems_per_image)
+{
+    if (images <= 0 || images > 65535 || elems_per_image <= 0) return 0;
+    return (size_t)images * tgs::pixel_grid_cap(images) * 4 * sizeof(float) + 256;          // one partial per wave
+}
+
+static int pixel_loss_check(const char* fn, int kind, int images, int64_t elems_per_image, bool pointers)
+{
+    char msg[200];
+    if ((kind != TGS_LOSS_L1 && kind != TGS_LOSS_L2) || images <= 0 || elems_per_image <= 0 || !pointers) {
+        snprintf(msg, sizeof msg, "%s: kind TGS_LOSS_L1 / TGS_LOSS_L2, positive sizes and non-NULL pointers required", fn);
+        return tgs::set_error(TGS_ERR_INVALID, msg);
+    }
+    if (images > 65535) {
+        snprintf(msg, sizeof msg, "%s: more than 65535 images", fn);
+        return tgs::set_error(TGS_ERR_INVALID, msg);
+    }
+    return TGS_OK;
+}
+
+int tgs_pixel_loss(void* stream, int kind, int images, int64_t elems_per_image, const float* img, const float* gt, float* out, float* dL_dimg,
+                   void* workspace, size_t workspace_bytes)
+{
     using namespace tgs;
+    if (const int r = pixel_loss_check("tgs_pixel_loss", kind, images, elems_per_image, img && gt && out && workspace)) return r;
+    if (workspace_bytes < tgs_pixel_loss_workspace_bytes(images, elems_per_image))
+        return set_error(TGS_ERR_INVALID, "tgs_pixel_loss: workspace smaller than tgs_pixel_loss_workspace_bytes()");
     hipStream_t st = (hipStream_t)stream;
-    if (planes <= 0 || height <= 0 || width <= 0 || !img || !gt || !dL_dimg || !workspace)
-        return set_error(TGS_ERR_INVALID, "tgs_l1_ssim_backward: positive sizes and non-NULL img / gt / dL_dimg / workspace required");
-    if (workspace_bytes < tgs_l1_ssim_workspace_bytes(planes, height, width))
-        return set_error(TGS_ERR_INVALID, "tgs_l1_ssim_backward: workspace smaller than tgs_l1_ssim_workspace_bytes()");
-    const size_t n = (size_t)planes * height * width;
-    if (planes > 65535) return set_error(TGS_ERR_INVALID, "tgs_l1_ssim_backward: image too large");
-    const float* dM1 = (const float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    const float* dX2 = dM1 + n;
-    const float* dXY = dX2 + n;
-    const LossWin win = make_window();
-    const float gs = (float)(-(double)dssim_factor / (double)n), gl = (float)((1.0 - (double)dssim_factor) / (double)n);
-    int nstrips = 0;
-    const dim3 sgrid = stream_grid(planes, height, width, nstrips);
-    if (sgrid.y > 65535u) return set_error(TGS_ERR_INVALID, "tgs_l1_ssim_backward: image too large");
-    hipLaunchKernelGGL(k_ssim_grad_stream, sgrid, dim3(256), 0, st, height, width, nstrips, img, gt, win, dM1, dX2, dXY, gs, gl, upstream, dL_dimg);
-    return hip_status("tgs_l1_ssim_backward");
+    const size_t n = (size_t)elems_per_image;
+    float* partial = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    const float scale = (float)((kind == TGS_LOSS_L2 ? 2.0 : 1.0) / (double)n);
+    unsigned blocks = 0;
+    if (dL_dimg) launch_pixel<true, true>(st, kind, images, n, img, gt, scale, nullptr, 0, dL_dimg, partial, blocks);
+    else launch_pixel<true, false>(st, kind, images, n, img, gt, scale, nullptr, 0, nullptr, partial, blocks);
+    hipLaunchKernelGGL(k_pixel_reduce, dim3((unsigned)images), dim3(256), 0, st, (int)(blocks * 4), partial, 1.0 / (double)n, out);
+    return hip_status("tgs_pixel_loss");
+}
+
+int tgs_pixel_loss_backward(void* stream, int kind, int images, int64_t elems_per_image, const float* img, const float* gt, const float* upstream,
+                            int upstream_per_image, float* dL_dimg)
+{
+    using namespace tgs;
+    if (const int r = pixel_loss_check("tgs_pixel_loss_backward", kind, images, elems_per_image, img && gt && dL_dimg)) return r;
+    const size_t n = (size_t)elems_per_image;
+    const float scale = (float)((kind == TGS_LOSS_L2 ? 2.0 : 1.0) / (double)n);
+    unsigned blocks = 0;
+    launch_pixel<false, true>((hipStream_t)stream, kind, images, n, img, gt, scale, upstream, upstream_per_image, dL_dimg, nullptr, blocks);
+    return hip_status("tgs_pixel_loss_backward");
 }
 }
