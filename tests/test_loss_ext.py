@@ -177,7 +177,8 @@ def test_gpu_ssim_per_image_matches_reference_fixture(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [(3, 1, 1), (3, 5, 200), (1, 33, 17), (2, 3, 40, 56), (3, 1080, 1920), (4, 3, 1080, 1920)])
+@pytest.mark.parametrize("shape", [(3, 1, 1), (3, 5, 200), (1, 33, 17), (2, 3, 40, 56), (3, 1080, 1920), (4, 3, 1080, 1920),
+                                   (3, 7, 1003)])      # 7021 elements per image: not a multiple of 4 and several 1024-element steps (per_image: the 4-byte path over several workgroups)
 def test_gpu_l2_matches_fp64(shape):
     from youreditableavatar_amd import loss
     pred, gt = _inputs(shape)

@@ -17,7 +17,8 @@ SET_FILES = {
 SETS = {"r01_n": "end of round 1", "r02_g": "end of round 2", "r03_f": "end of round 3", "r04_b": "end of round 4", "r05_g": "end of round 5 (csrc 23587000822bfd1d)", "r06_e": "round 6, mid-round set",
         "r06_f": "END OF ROUND 6: the set `bench.py` quotes counters from"}
 NAMED = {
- "parity_r02.json": "achieved rel-L2 of every GPU parity test, round 2 (written by the suite: tests/util.record_parity)", "parity_r03.json": "the same, round 3", "parity_r04.json": "round 4", "parity_r05.json": "round 5", "parity_r06.json": "round 6",
+ "parity_r04.json": "achieved rel-L2 of every GPU parity test, round 4 (written by the suite: tests/util.record_parity)", "parity_r05.json": "round 5", "parity_r06.json": "round 6",
+ "parity_r07.json": "the suite with tests/test_sh_color_matrix.py: its `sh_rows_*` entries hold, per case, the whole-tensor rel-L2 and the largest row distance in units of u = 2^-24 (`*_u`; bars 32 / 32 / 128)",
  "r02_a_valu_issue_rate.txt": "first VALU issue-rate measurement (cited by DESIGN_HISTORY)", "r02_fuzz": "round-2 fuzz summary", "r02_lds": "LDS atomic rate microbenchmark",
  "r03_block": "block-serial forward: per-tile timeline (lost: 63 -> 157 us)", "r03_d_bench_default.json": "bench line at the end of round 3 proper", "r03_d_kernel_stats_trainer_protocol.csv": "trainers' step by kernel, round 3",
  "r03_final": "round-3 final bench", "r03_fuzz": "round-3 fuzz summary", "r03_fwd": "phases of a forward workgroup (-DTGS_STAMPS=2)", "r03_multirank": "90 two-rank rehearsals in a row: 0 stalls", "r03_persistent": "persistent render workgroups: slots over time (lost)",

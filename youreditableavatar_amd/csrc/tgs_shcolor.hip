@@ -79,7 +79,9 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_sh_rgb(const ShArgs a)
     const int idx = blockIdx.x * PRE_BLOCK + threadIdx.x;
     const bool in_range = idx < a.P;
     const int ncoef = a.levels * a.levels;
-    const bool staged = a.M == 16;
+    // float4 traffic needs 16-byte aligned tensors (a view such as sh[1:] of a larger parameter is 4-byte aligned only): those take the row-wise
+    // path, as in k_sh_rgb_dcrest
+    const bool staged = a.M == 16 && ((reinterpret_cast<uintptr_t>(a.sh) | reinterpret_cast<uintptr_t>(a.dL_dsh)) & 15) == 0;
     const size_t base4 = (size_t)blockIdx.x * PRE_BLOCK * 12, total4 = (size_t)a.P * 12;
     float camx = 0.f, camy = 0.f, camz = 0.f;
     if (a.camera) { camx = a.camera[0]; camy = a.camera[1]; camz = a.camera[2]; }
