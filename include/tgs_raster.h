@@ -425,6 +425,38 @@ int tgs_pixel_loss_backward(void* stream, int kind, int images, int64_t elems_pe
                             int upstream_per_image, float* dL_dimg);
 
 
+/* ---- the trainers' optimizer step: Adam over every Gaussian parameter group in one launch ----
+ * Replaces optim.Adam(l, lr=0.0, eps=1e-15).step() of Edit_core/tetgs_scene/tetgs_optimizer.py:92,101-103,167,176-178 (on a HIP device: about
+ * seven multi-tensor element-wise kernels per step, 72 bytes moved per parameter float) by one pass of 28 bytes per float.  For every element of
+ * every tensor, in fp32:   g = grad * grad_scale;   m += (g - m) * (1 - beta1);   v = v * beta2 + g * g * (1 - beta2);
+ *                          p -= step_size * (m / (sqrt(v) / bc2_sqrt + eps))
+ * -- the framework's non-capturable single-tensor Adam on grad * grad_scale.  The caller computes step_size = lr / (1 - beta1^t) and
+ * bc2_sqrt = sqrt(1 - beta2^t) in double from the tensor's OWN step count t (after its increment) and passes them as floats; the betas are
+ * doubles because 1 - beta2 is formed from them (beta2 = 0.999 rounded to a float first misstates 1 - beta2 by 1.3e-5 of itself).
+ * grad: laid out like param (grad_plane_stride = 0), or LEVEL-MAJOR as tgs_backward_batch_range_planes writes dL_dsh: param / exp_avg /
+ * exp_avg_sq row-major [rows, planes, 3], element (r, k, c) of the gradient at grad[k * grad_plane_stride + 3 r + c]; then numel = 3 * planes *
+ * rows, 1 <= planes <= 64, grad_plane_stride >= 3 rows a multiple of 4 floats, grad 16-byte aligned.  Any 4-byte aligned param / state / contiguous
+ * grad pointers and any numel <= 2^31-1; a tensor whose pointers are all 16-byte aligned takes the 16-byte path.  The table is copied into the
+ * kernel argument: no device memory is allocated or written except param, exp_avg and exp_avg_sq, nothing is synchronised.  One launch per
+ * TGS_ADAM_MAX_TENSORS non-empty tensors. */
+#define TGS_ADAM_MAX_TENSORS 48
+typedef struct {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+    int64_t grad_plane_stride;  /* floats between coefficient planes of a level-major grad; 0: grad is laid out like param */
+    int32_t planes;             /* level-major: coefficients per row (M of a [rows, M, 3] parameter); ignored otherwise */
+    float step_size;            /* lr / (1 - beta1^t) */
+    float bc2_sqrt;             /* sqrt(1 - beta2^t) */
+    int32_t reserved;
+} tgs_adam_tensor_t;
+int tgs_adam_step(void* stream, const tgs_adam_tensor_t* tensors, int count, double beta1, double beta2, float eps, float grad_scale);
+int tgs_adam_max_tensors(void);             /* TGS_ADAM_MAX_TENSORS of THIS build */
+size_t tgs_sizeof_adam_tensor(void);        /* sizeof(tgs_adam_tensor_t) of THIS build: a binding checks it before it fills an array */
+
+
 /* Hardware self-test of the wave-level 36-value reduction used by the backward render kernel:
  * in[64][36] (one row per lane) -> out[4][9], out[e][k] = sum over lanes of in[lane][e*9+k]. */
 int tgs_selftest_reduce36(void* stream, const float* in, float* out);
