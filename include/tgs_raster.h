@@ -289,6 +289,41 @@ int tgs_bind_groups_backward(void* stream, int Pk, int Pe, const float* edit_qua
                              const float* g_opacity, const float* g_scales, const float* g_quats, const float* g_points,
                              float* d_density, float* d_scales, float* d_quats, float* d_points, float* d_offsets);
 
+/* ---- the scaling regulariser of the refinement loops ----
+ * Every iteration of Edit_core/tetgs_texture/refine.py:306-317 and refine_3dgs.py:339-350 (scaling_reg = True is the default, refine.py:42):
+ *     radii = tetgs.radii;  max_vals / min_vals = max / min of scaling over the three axes;
+ *     thresh_idxs = (max_vals > radii * 1.0) & (max_vals / min_vals > 10.0);  if thresh_idxs.sum() > 0: loss += max_vals[thresh_idxs].mean()
+ * -- about a dozen framework kernels each way, a mesh walk and a host synchronisation per step.
+ *
+ * tgs_gaussian_radii <- the `radii` property (tetgs_scene/tetgs_model.py:299-310, tetgs_edit_3d.py:332-343; circumcircle_radius,
+ * utils/graphics_utils.py:109-116), computed ONCE (the mesh vertices are fixed buffers, tetgs_model.py:149): radii[i] = a b c / (4 sqrt(s (s-a)
+ * (s-b) (s-c))) of face face_indices[i], evaluated in double; a degenerate face gives inf or NaN as the reference's formula does.
+ * verts[V,3] fp32; faces[F,3] int32 (faces_i64 = 0) or int64 (1); face_indices[P] int32 / int64 / fp32 (index_kind = TGS_INDEX_*; fp32 indices
+ * -- Edit3DTetGS stores them so, tetgs_model.py:719 -- are truncated like .int(), tetgs_edit_3d.py:341).  Sizes are checked on the host; an index
+ * outside [0, F) or a vertex outside [0, V) is found on the device: nothing is read through it, its radius is NaN and *invalid_flag (a device
+ * int, cleared by the call) becomes 1 -- the caller reads it back and treats 1 as TGS_ERR_INVALID.
+ *
+ * tgs_scale_reg_forward: scales[P,3] are the activated scales (raw = 0) or the raw parameters (raw = 1: expf is applied inside, the same one
+ * tgs_bind_forward applies).  A row is selected when max > radii * max_factor and max / min > ratio_threshold: strict comparisons on fp32
+ * values, a correctly rounded division; a NaN or inf radius never selects, min == 0 selects.  codes[P]: 0 = not selected, 1..3 = index of the
+ * maximum + 1, the lowest index among equal maxima.  out3 (12 bytes on the device): float value = mean of the selected rows' maxima, or 0 when
+ * none is selected (what the reference's `if` amounts to, without the read-back); uint32 count; float 1 / count (0 when count == 0).
+ * workspace: tgs_scale_reg_workspace_bytes(P) bytes of device scratch (one 16-byte partial per 256 rows).  Sums are fixed-order, in double:
+ * two calls give the same bits.  P == 0: out3 = zeros, nothing is launched.
+ *
+ * tgs_scale_reg_backward: the gradient of weight * value, times upstream[0] (a device scalar, NULL = 1): for a selected row
+ * upstream * weight / count on the component the code byte names (raw_scales != NULL: times that component's expf, the gradient with respect to
+ * the RAW scales), 0 elsewhere.  The rows are never decided again: codes / out3 are the forward's, unmodified.  accumulate = 0 writes every
+ * element of grad[P,3]; accumulate = 1 adds to it.  Nothing is synchronised. */
+enum { TGS_INDEX_I32 = 0, TGS_INDEX_I64 = 1, TGS_INDEX_F32 = 2 };
+int tgs_gaussian_radii(void* stream, int V, int F, int P, const float* verts, const void* faces, int faces_i64, const void* face_indices, int index_kind,
+                       float* radii, int* invalid_flag);
+size_t tgs_scale_reg_workspace_bytes(int P);
+int tgs_scale_reg_forward(void* stream, int P, const float* scales, int raw, const float* radii, float max_factor, float ratio_threshold, uint8_t* codes, void* out3,
+                          void* workspace, size_t workspace_bytes);
+int tgs_scale_reg_backward(void* stream, int P, const uint8_t* codes, const void* out3, const float* raw_scales, const float* upstream, float weight, int accumulate,
+                           float* grad);
+
 /* ---- "next" row 4: simple-knn ----
  * distCUDA2 (Edit_core/thirdparties/simple-knn/spatial.cu:15-26 -> SimpleKNN::knn, simple_knn.cu:185-221):
  * mean_dist2[i] = mean of the 3 smallest squared distances from points[i] to the other points (FLT_MAX terms, i.e.
