@@ -206,6 +206,40 @@ int tgs_backward_opt(const tgs_options_t* opt, int accumulate, void* stream, int
                      float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                      int debug);
 
+/* ---- accumulated alpha (an extension: the reference's rasterizer has no alpha output) ----
+ * Definition: alpha[H*W] = 1 - final_T, where final_T is the transmittance the frame multiplies the background by (forward.cu:366-373), so
+ *     out_color == C_premultiplied + (1 - alpha) * bg
+ * holds with the frame's own stored values.  Instance pruning does not change alpha (a pruned instance blends nowhere); a tile without
+ * instances and a frame the sync-free forward rejected have alpha == 0 everywhere.
+ * Gradient: d final_T / d alpha_i = -final_T / (1 - alpha_i) for every contributor i of the pixel -- the derivative the reference's
+ * background term evaluates (backward.cu:533-541) -- so an upstream gradient dL_dalpha[H*W] enters the per-pixel backward as the per-pixel
+ * scalar (bg . dL_dpixel) - dL_dalpha where (bg . dL_dpixel) stands, with the reference's conventions for that term: the min(0.99, .) clamp
+ * is straight-through, entries behind the pixel's last contributor take no part (backward.cu:487), and the skip rules power > 0 and
+ * alpha < 1/255 apply as everywhere else.  From there it reaches dL_dopacity, dL_dconic, dL_dmean2D and the per-Gaussian gradients through
+ * the unchanged per-Gaussian pass; dL_dcolor / dL_dsh get nothing from it.
+ *
+ * tgs_alpha: out_alpha[H*W] = 1 - final_T of a finished forward (any of the forward entry points; width / height as given to it), enqueued
+ * on `stream`.  A forward with P == 0 writes no image state: its alpha is zero and there is nothing to call this with. */
+int tgs_alpha(void* stream, int width, int height, const void* img_buffer, float* out_alpha);
+
+/* tgs_backward_opt with one more upstream gradient, dL_dalpha[H*W] (NULL: exactly tgs_backward_opt, the same kernels).  dL_dpix stays required. */
+int tgs_backward_alpha_opt(const tgs_options_t* opt, int accumulate, void* stream, int P, int D, int M, int64_t R,
+                           const float* background, int width, int height,
+                           const float* means3D, const float* shs, const float* colors_precomp,
+                           const float* scales, float scale_modifier, const float* rotations,
+                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                           const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                           const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
+                           const float* dL_dpix, const float* dL_dalpha,
+                           float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                           float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                           int debug);
+
+/* The per-pixel half alone (tgs_backward_render_opt below + dL_dalpha; NULL: exactly that function): the tile partials stay in the binning
+ * buffer for tgs_backward_batch.  What a batch path calls per view. */
+int tgs_backward_render_alpha_opt(const tgs_options_t* opt, void* stream, int P, int64_t R, const float* background, int width, int height,
+                                  const void* binning_buffer, const void* img_buffer, const float* dL_dpix, const float* dL_dalpha);
+
 /* present[P]: 1 byte per Gaussian, 1 iff view-space z > 0.2 (auxiliary.h:154). */
 int tgs_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix,
                      const float* projmatrix, uint8_t* present);

@@ -20,8 +20,9 @@ void launch_tile_sort(hipStream_t, const GeomState&, const ImgState&, const BinS
 void launch_render_fwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t T, const Meta* m, const float* bg,
                        float* out_color, uint32_t tile_bound, uint32_t mid_bound, int light);
 void launch_mark_visible(hipStream_t, int P, const float* means3D, const float* view, uint8_t* present);
+void launch_alpha(hipStream_t, const ImgState&, size_t N, float* out_alpha);
 void launch_render_bwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t tiles, const float* bg, const float* dL_dpix,
-                       bool deterministic, uint32_t mid_tiles, int light, uint32_t T);
+                       const float* dL_dalpha, bool deterministic, uint32_t mid_tiles, int light, uint32_t T);
 void launch_preprocess_bwd(hipStream_t, const BwdIn&, const CamParams&, const GeomState&, const BinState&);
 void launch_preprocess_bwd_batch(hipStream_t, const BwdIn&, const BatchViews&);
 void launch_selftest_reduce36(hipStream_t, const float* in, float* out);
@@ -142,6 +143,14 @@ static int fail(int code, const char* fmt, ...)
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
+}
+// an entry point that shares its implementation with others names itself in front of the message that implementation left
+static int named(const char* fn, int r)
+{
+    if (r >= 0) return r;
+    char msg[sizeof(g_err)];
+    snprintf(msg, sizeof(msg), "%s", g_err);
+    return fail(r, "%s: %s", fn, msg);
 }
 
 #define HIP_TRY(expr)                                                                                     \
@@ -483,6 +492,7 @@ static int64_t forward_impl(const Opts& opt, const FwdCall& c, const Model& m, c
 struct BwdArgs {
     int64_t R; const int* radii; const void *geom_buffer, *binning_buffer, *img_buffer; const float* dL_dpix;
     float *dL_dmean2D, *dL_dconic, *dL_dopacity, *dL_dcolor, *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot;
+    const float* dL_dalpha = nullptr;       // upstream gradient of the accumulated alpha, [H * W] (tgs_backward_alpha_opt; NULL: none)
 };
 
 static BwdIn bwd_in(const Model& m)
@@ -495,12 +505,13 @@ static BwdIn bwd_in(const Model& m)
 }
 
 // the per-pixel half of a frame's backward; the tile partials stay in the binning buffer
-static int enqueue_render_bwd(const Opts& opt, hipStream_t st, int debug, const FrameBuffers& fb, const ViewArgs& v, int64_t R, const float* dL_dpix)
+static int enqueue_render_bwd(const Opts& opt, hipStream_t st, int debug, const FrameBuffers& fb, const ViewArgs& v, int64_t R, const float* dL_dpix,
+                              const float* dL_dalpha = nullptr)
 {
     if (R <= 0) return TGS_OK;
     const Bounds b = resolve_bounds(opt, v.T());
     return stage(st, TGS_STAGE_RENDER_BWD, "render_bwd", debug, [&] {
-        launch_render_bwd(st, fb.s, fb.b, v.width, v.height, v.gx(), b.tiles, v.background, dL_dpix, opt.deterministic, b.mid, opt.light, (uint32_t)v.T()); });
+        launch_render_bwd(st, fb.s, fb.b, v.width, v.height, v.gx(), b.tiles, v.background, dL_dpix, dL_dalpha, opt.deterministic, b.mid, opt.light, (uint32_t)v.T()); });
 }
 
 // strict: tgs_backward / tgs_backward_accumulate as the reference's Rasterizer::backward declares them (every output required);
@@ -525,19 +536,19 @@ static int backward_impl(bool strict, const Opts& opt, int accumulate, hipStream
     in.accumulate = accumulate;
     in.meta = fb.s.meta;
 
-    if (int r = enqueue_render_bwd(opt, st, debug, fb, v, a.R, a.dL_dpix)) return r;
+    if (int r = enqueue_render_bwd(opt, st, debug, fb, v, a.R, a.dL_dpix, a.dL_dalpha)) return r;
     return stage(st, TGS_STAGE_PREPROCESS_BWD, "preprocess_bwd", debug, [&] { launch_preprocess_bwd(st, in, cam, fb.g, fb.b); });
 }
 
 // tgs_backward_render[_views]: the view's own fields (tgs_backward_render packs its arguments into one)
-static int backward_render_impl(const Opts& opt, hipStream_t st, int P, const tgs_view_t& w)
+static int backward_render_impl(const Opts& opt, hipStream_t st, int P, const tgs_view_t& w, const float* dL_dalpha = nullptr)
 {
     g_err[0] = 0;
     if (P == 0) return TGS_OK;
     if (P < 0) return fail(TGS_ERR_INVALID, "bad sizes");
     if (int r = check_view(w, 0, VIEW_RENDER_BWD, false)) return r;
     const ViewArgs v = view_args(w);
-    return enqueue_render_bwd(opt, st, 0, carve_frame(GeomShape{(size_t)P, false, false}, v, w.R, nullptr, w.binning_buffer, w.img_buffer), v, w.R, w.dL_dpix);
+    return enqueue_render_bwd(opt, st, 0, carve_frame(GeomShape{(size_t)P, false, false}, v, w.R, nullptr, w.binning_buffer, w.img_buffer), v, w.R, w.dL_dpix, dL_dalpha);
 }
 
 // the shared per-Gaussian stage of a group of views of tgs_forward_views: one launch on the group's first stream
@@ -725,6 +736,20 @@ int tgs_backward_opt(const tgs_options_t* o, int accumulate, void* stream, int P
                          BwdArgs{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot});
 }
 
+int tgs_backward_alpha_opt(const tgs_options_t* o, int accumulate, void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height,
+                           const float* means3D, const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                           const int* radii, const void* geom_buffer, const void* binning_buffer, const void* img_buffer, const float* dL_dpix, const float* dL_dalpha,
+                           float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                           float* dL_drot, int debug)
+{
+    return named("tgs_backward_alpha_opt", backward_impl(false, resolve_options(o), accumulate ? 1 : 0, (hipStream_t)stream, debug,
+                         Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
+                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy},
+                         BwdArgs{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                                 dL_dalpha}));
+}
+
 int tgs_backward_accumulate(void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height, const float* means3D,
                             const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
                             const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
@@ -851,6 +876,29 @@ int tgs_backward_render_opt(const tgs_options_t* o, void* stream, int P, int64_t
     memset(&v, 0, sizeof(v));
     v.width = width; v.height = height; v.R = R; v.background = background; v.binning_buffer = binning_buffer; v.img_buffer = img_buffer; v.dL_dpix = dL_dpix;
     return backward_render_impl(resolve_options(o), (hipStream_t)stream, P, v);
+}
+
+int tgs_backward_render_alpha_opt(const tgs_options_t* o, void* stream, int P, int64_t R, const float* background, int width, int height,
+                                  const void* binning_buffer, const void* img_buffer, const float* dL_dpix, const float* dL_dalpha)
+{
+    tgs_view_t v;
+    memset(&v, 0, sizeof(v));
+    v.width = width; v.height = height; v.R = R; v.background = background; v.binning_buffer = binning_buffer; v.img_buffer = img_buffer; v.dL_dpix = dL_dpix;
+    return named("tgs_backward_render_alpha_opt", backward_render_impl(resolve_options(o), (hipStream_t)stream, P, v, dL_dalpha));
+}
+
+int tgs_alpha(void* stream, int width, int height, const void* img_buffer, float* out_alpha)
+{
+    g_err[0] = 0;
+    if (width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "tgs_alpha: bad sizes W=%d H=%d", width, height);
+    if (!img_buffer || !out_alpha) return fail(TGS_ERR_INVALID, "tgs_alpha: NULL required pointer");
+    const ViewArgs v{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
+    ImgState s;
+    img_carve(s, (char*)img_buffer, v.N(), v.T());
+    launch_alpha((hipStream_t)stream, s, v.N(), out_alpha);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(TGS_ERR_HIP, "tgs_alpha: %s", hipGetErrorString(e));
+    return TGS_OK;
 }
 
 int tgs_backward_batch(void* stream, int P, int D, int M, int n_views, const tgs_view_t* views, const float* means3D, const float* shs,

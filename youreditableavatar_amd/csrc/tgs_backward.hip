@@ -1,6 +1,7 @@
 // tgs_backward.hip -- backward pass kernels for gfx950 (wave64).
 //
 //   k_render_bwd      back-to-front gradient of the compositing                      (backward.cu:399-557)
+//   k_render_bwd_alpha / k_render_bwd_det_alpha: the same bodies with an upstream gradient on the accumulated alpha 1 - T_final as well
 //   k_preprocess_bwd  per-Gaussian: sum of the tile partials, then cov2D / projection / SH / cov3D
 //                     backward fused in one pass          (backward.cu:144-274 + :346-396, two kernels there)
 //
@@ -40,8 +41,13 @@ __device__ __forceinline__ ConicHiLo conic_hilo(float op, double sum)
     return r;
 }
 
-__global__ __launch_bounds__(256) void k_render_bwd_det(const ImgState s, const BinState b, int W, int H, uint32_t gx,
-                                                    const float* __restrict__ bg, const float* __restrict__ dL_dpix)
+// WITH_DALPHA (the three per-pixel variants alike): the frame's accumulated alpha A = 1 - T_final has an upstream gradient of its own,
+// dL_dalpha[H * W].  dT_final / dalpha_i = -T_final / (1 - alpha_i) is the derivative the background term evaluates already, so the gradient
+// enters the PROLOGUE as one per-pixel scalar: (bg . dL_dpixel) - dL_dA where (bg . dL_dpixel) stood.  The inner loops, the accumulators and
+// the flush are the same code for both instantiations; <false> is the kernel as it was.
+template <bool WITH_DALPHA>
+__device__ __forceinline__ void render_bwd_det_body(const ImgState& s, const BinState& b, int W, int H, uint32_t gx,
+                                                    const float* __restrict__ bg, const float* __restrict__ dL_dpix, const float* __restrict__ dL_dalpha_pix)
 {
     __shared__ float4 sA[RCHUNK + 1];
     __shared__ float4 sB[RCHUNK + 1];
@@ -77,6 +83,7 @@ __global__ __launch_bounds__(256) void k_render_bwd_det(const ImgState s, const 
     if (inside) { dpx0 = dL_dpix[pix_id]; dpx1 = dL_dpix[N + pix_id]; dpx2 = dL_dpix[2 * N + pix_id]; }
     float bg_dot_dpixel = 0.f;                              // backward.cu:533-535
     bg_dot_dpixel += bg[0] * dpx0; bg_dot_dpixel += bg[1] * dpx1; bg_dot_dpixel += bg[2] * dpx2;
+    if constexpr (WITH_DALPHA) { if (inside) bg_dot_dpixel -= dL_dalpha_pix[pix_id]; }
     float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;               // accum_rec
     float last_alpha = 0.f, lc0 = 0.f, lc1 = 0.f, lc2 = 0.f;
     const float ddelx_dx = (float)(0.5 * W), ddely_dy = (float)(0.5 * H);   // backward.cu:460-461
@@ -215,6 +222,16 @@ __global__ __launch_bounds__(256) void k_render_bwd_det(const ImgState s, const 
         }
     }
     stamp(s, tile, 3);
+}
+__global__ __launch_bounds__(256) void k_render_bwd_det(const ImgState s, const BinState b, int W, int H, uint32_t gx,
+                                                    const float* __restrict__ bg, const float* __restrict__ dL_dpix)
+{
+    render_bwd_det_body<false>(s, b, W, H, gx, bg, dL_dpix, nullptr);
+}
+__global__ __launch_bounds__(256) void k_render_bwd_det_alpha(const ImgState s, const BinState b, int W, int H, uint32_t gx,
+                                                          const float* __restrict__ bg, const float* __restrict__ dL_dpix, const float* __restrict__ dL_dalpha_pix)
+{
+    render_bwd_det_body<true>(s, b, W, H, gx, bg, dL_dpix, dL_dalpha_pix);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -367,8 +384,9 @@ __device__ __forceinline__ void bwd_passes(const unsigned short* myq, uint32_t n
 // 4w .. 4w+3 one after the other (the forward gives a light tile a 256-thread workgroup of its own: k_render_fwd; why light tiles are set apart: tgs_device.hpp, LIGHT_MAX).  Same arithmetic per (pixel, entry) pair, same f64
 // LDS accumulator and flush as the heavy path; the pixel inputs of a wave's four blocks are fetched up front.
 // ---------------------------------------------------------------------------------------------
+template <bool WITH_DALPHA>
 __device__ __forceinline__ void bwd_light_group(const ImgState& s, const BinState& b, int W, int H, uint32_t gx, const float* __restrict__ bg,
-                                                const float* __restrict__ dL_dpix, uint4 td, bool active, float4* sA, float4* sB, uint32_t* sSlot,
+                                                const float* __restrict__ dL_dpix, const float* __restrict__ dL_dalpha_pix, uint4 td, bool active, float4* sA, float4* sB, uint32_t* sSlot,
                                                 BwdAcc& acc, uint2* sQ, unsigned short (*lists)[BCH + 8], unsigned short (*qlists)[4][QL_ROW])
 {
     const int sub = threadIdx.x >> 8, lt = threadIdx.x & 255;
@@ -382,7 +400,7 @@ __device__ __forceinline__ void bwd_light_group(const ImgState& s, const BinStat
     const uint32_t qmax = active ? min(td.w, n) : 0u;                  // deepest position any pixel of the tile blended (k_render_fwd wrote it into the descriptor)
     // pixel inputs of a block (5 loads), asked for ONE BLOCK AHEAD: block 0's here, block bi + 1's in front of block bi's passes (round 5: all four
     // blocks' inputs held at once were 20 VGPRs -- with the pass's own registers the light path spilled them right behind their loads)
-    struct PixIn { float Tf, d0, d1, d2; uint32_t lc; bool in; };     // (raw loads from a clamped address; select_loaded at the use)
+    struct PixIn { float Tf, d0, d1, d2, da; uint32_t lc; bool in; };     // (raw loads from a clamped address; select_loaded at the use; da: WITH_DALPHA only)
     auto load_block = [&](int bi) {
         const int blk = 4 * w4 + bi;
         const int px = tx * TILE + (blk & 3) * 4 + (qd & 1) * 2 + (pq & 1);
@@ -394,6 +412,8 @@ __device__ __forceinline__ void bwd_light_group(const ImgState& s, const BinStat
         r.Tf = s.final_T[pix_id];
         r.lc = inside ? s.n_contrib[pix_id] : 0u;
         r.d0 = dL_dpix[pix_id]; r.d1 = dL_dpix[N + pix_id]; r.d2 = dL_dpix[2 * N + pix_id];
+        r.da = 0.f;
+        if constexpr (WITH_DALPHA) r.da = dL_dalpha_pix[pix_id];
         return r;
     };
     PixIn nxt = load_block(0);
@@ -436,6 +456,7 @@ __device__ __forceinline__ void bwd_light_group(const ImgState& s, const BinStat
         float T = T_final;
         float bg_dot_dpixel = 0.f;                          // backward.cu:533-535
         bg_dot_dpixel += bgr * dpx0; bg_dot_dpixel += bgg * dpx1; bg_dot_dpixel += bgb * dpx2;
+        if constexpr (WITH_DALPHA) bg_dot_dpixel -= select_loaded(keep, cur.da);
         const float tfinal_bg = T_final * bg_dot_dpixel;
         float arA = 0.f;
         const BwdPixel pxl = {pixfx, pixfy, dpx0, dpx1, dpx2, tfinal_bg, ((int)qmax - 1 - (int)last_contributor) * 16, (uint32_t)pq * (uint32_t)(ACC_PLANE * 8)};
@@ -473,8 +494,9 @@ __device__ __forceinline__ void bwd_light_group(const ImgState& s, const BinStat
 
 // light != 0: tiles with fewer than LIGHT_MAX instances are composited three per workgroup by the LAST workgroups of the grid (bwd_light_group);
 // this kernel's one-tile workgroups end at Meta::n_mid
-__global__ __launch_bounds__(BWD_THREADS, 8) void k_render_bwd(const ImgState s, const BinState b, int W, int H, uint32_t gx,
-                                                            const float* __restrict__ bg, const float* __restrict__ dL_dpix, int light, uint32_t n_tiles)
+template <bool WITH_DALPHA>
+__device__ __forceinline__ void render_bwd_body(const ImgState& s, const BinState& b, int W, int H, uint32_t gx, const float* __restrict__ bg,
+                                                const float* __restrict__ dL_dpix, const float* __restrict__ dL_dalpha_pix, int light, uint32_t n_tiles)
 {
     // ONE object, members in the order of their use in a pass: the arrays a pass addresses (records, accumulator) sit in the first 64 KB of the
     // workgroup's LDS, so their base is an instruction's 16-bit offset and not a VGPR (the compiler orders separate __shared__ arrays by size)
@@ -495,7 +517,7 @@ __global__ __launch_bounds__(BWD_THREADS, 8) void k_render_bwd(const ImgState s,
         if (blockIdx.x >= n_ne) {
             if (lgroup >= n_lgroups) return;                // (uniform over the workgroup)
             if (threadIdx.x == 0) { sA[BNULL] = make_float4(0.f, 0.f, 0.f, 0.f); sB[BNULL] = make_float4(0.f, 0.f, 0.f, 0.f); acc.t[BNULL].cb = 0.f; }
-            bwd_light_group(s, b, W, H, gx, bg, dL_dpix, tdl, lsub < (uint32_t)BWD_LIGHT_PER_WG && li < n_light, sA, sB, sSlot[0], acc, sQ, lists, qlists);
+            bwd_light_group<WITH_DALPHA>(s, b, W, H, gx, bg, dL_dpix, dL_dalpha_pix, tdl, lsub < (uint32_t)BWD_LIGHT_PER_WG && li < n_light, sA, sB, sSlot[0], acc, sQ, lists, qlists);
             return;
         }
     } else check_tile_bound(s);
@@ -532,6 +554,8 @@ __global__ __launch_bounds__(BWD_THREADS, 8) void k_render_bwd(const ImgState s,
     const float T_raw = s.final_T[pixc];
     const uint32_t last_contributor = inside ? s.n_contrib[pixc] : 0u;
     const float d_raw0 = dL_dpix[pixc], d_raw1 = dL_dpix[N + pixc], d_raw2 = dL_dpix[2 * N + pixc];
+    float da_raw = 0.f;
+    if constexpr (WITH_DALPHA) da_raw = dL_dalpha_pix[pixc];
     if (ht < qmax) fetch(rg.x + qmax - 1 - ht);
     asm volatile("" ::: "memory");
     // (the selects behind the loads' issue: an asm statement waits for its operand where it stands)
@@ -541,6 +565,7 @@ __global__ __launch_bounds__(BWD_THREADS, 8) void k_render_bwd(const ImgState s,
     float T = T_final;
     float bg_dot_dpixel = 0.f;                              // backward.cu:533-535
     bg_dot_dpixel += bg[0] * dpx0; bg_dot_dpixel += bg[1] * dpx1; bg_dot_dpixel += bg[2] * dpx2;
+    if constexpr (WITH_DALPHA) bg_dot_dpixel -= select_loaded(keep, da_raw);
     const float tfinal_bg = T_final * bg_dot_dpixel;
     float arA = 0.f;                                        // dL_dpixel . accum_rec with (last_alpha, last_color) already applied (bwd_chain4s)
     float vone = 1.0f, vzero = 0.0f;                        // identity elements, pinned to VGPRs for the DPP selects
@@ -623,6 +648,16 @@ __global__ __launch_bounds__(BWD_THREADS, 8) void k_render_bwd(const ImgState s,
     }
     busy_report(s, tile, 1, busy);
     stamp(s, tile, 3);
+}
+__global__ __launch_bounds__(BWD_THREADS, 8) void k_render_bwd(const ImgState s, const BinState b, int W, int H, uint32_t gx,
+                                                            const float* __restrict__ bg, const float* __restrict__ dL_dpix, int light, uint32_t n_tiles)
+{
+    render_bwd_body<false>(s, b, W, H, gx, bg, dL_dpix, nullptr, light, n_tiles);
+}
+__global__ __launch_bounds__(BWD_THREADS, 8) void k_render_bwd_alpha(const ImgState s, const BinState b, int W, int H, uint32_t gx, const float* __restrict__ bg,
+                                                                  const float* __restrict__ dL_dpix, const float* __restrict__ dL_dalpha_pix, int light, uint32_t n_tiles)
+{
+    render_bwd_body<true>(s, b, W, H, gx, bg, dL_dpix, dL_dalpha_pix, light, n_tiles);
 }
 
 
@@ -1571,17 +1606,27 @@ void launch_selftest_reduce36(hipStream_t st, const float* in, float* out)
 // `tiles`: leading entries of tile_order to visit -- all of them, or the caller's bound on the tiles with instances (the rest is empty)
 // tiles: leading entries of tile_order that can hold instances (all, or the caller's bound); mid_tiles (light != 0): how many of them can hold
 // >= LIGHT_MAX instances -- the caller's bound, or `tiles`.  T: tiles of the image.
+// dL_dalpha: upstream gradient of the accumulated alpha, [H * W], or nullptr -- then exactly the kernels without it are launched.
 void launch_render_bwd(hipStream_t st, const ImgState& s, const BinState& b, int W, int H, uint32_t gx, uint32_t tiles, const float* bg, const float* dL_dpix,
-                       bool deterministic, uint32_t mid_tiles, int light, uint32_t T)
+                       const float* dL_dalpha, bool deterministic, uint32_t mid_tiles, int light, uint32_t T)
 {
     // (-DTGS_FAST_MATH=0 builds always take the fixed-order kernel: it evaluates exp / the divisions in their accurate forms)
-    if (deterministic || !TGS_FAST_MATH) { hipLaunchKernelGGL(k_render_bwd_det, dim3(tiles), dim3(256), 0, st, s, b, W, H, gx, bg, dL_dpix); return; }
-    if (!light) { hipLaunchKernelGGL(k_render_bwd, dim3(tiles), dim3(BWD_THREADS), 0, st, s, b, W, H, gx, bg, dL_dpix, 0, T); return; }
+    if (deterministic || !TGS_FAST_MATH) {
+        if (dL_dalpha) hipLaunchKernelGGL(k_render_bwd_det_alpha, dim3(tiles), dim3(256), 0, st, s, b, W, H, gx, bg, dL_dpix, dL_dalpha);
+        else hipLaunchKernelGGL(k_render_bwd_det, dim3(tiles), dim3(256), 0, st, s, b, W, H, gx, bg, dL_dpix);
+        return;
+    }
+    if (!light) {
+        if (dL_dalpha) hipLaunchKernelGGL(k_render_bwd_alpha, dim3(tiles), dim3(BWD_THREADS), 0, st, s, b, W, H, gx, bg, dL_dpix, dL_dalpha, 0, T);
+        else hipLaunchKernelGGL(k_render_bwd, dim3(tiles), dim3(BWD_THREADS), 0, st, s, b, W, H, gx, bg, dL_dpix, 0, T);
+        return;
+    }
     const uint32_t heavy = mid_tiles < tiles ? mid_tiles : tiles;
     // one-tile workgroups for the (bound on the) tiles with >= LIGHT_MAX instances + light groups for the rest, three tiles each.  With exact
     // counts (heavy = n_mid, tiles = n_nonempty) that is n_mid + ceil((n_nonempty - n_mid) / 3); with bounds it is an upper bound of it.
     const uint32_t grid = heavy + (tiles - heavy + BWD_LIGHT_PER_WG - 1) / BWD_LIGHT_PER_WG;      // (largest when n_mid reaches its bound)
-    hipLaunchKernelGGL(k_render_bwd, dim3(grid > 0 ? grid : 1u), dim3(BWD_THREADS), 0, st, s, b, W, H, gx, bg, dL_dpix, 1, T);
+    if (dL_dalpha) hipLaunchKernelGGL(k_render_bwd_alpha, dim3(grid > 0 ? grid : 1u), dim3(BWD_THREADS), 0, st, s, b, W, H, gx, bg, dL_dpix, dL_dalpha, 1, T);
+    else hipLaunchKernelGGL(k_render_bwd, dim3(grid > 0 ? grid : 1u), dim3(BWD_THREADS), 0, st, s, b, W, H, gx, bg, dL_dpix, 1, T);
 }
 void launch_preprocess_bwd(hipStream_t st, const BwdIn& in, const CamParams& cam, const GeomState& g, const BinState& b)
 {

@@ -1344,8 +1344,31 @@ __global__ __launch_bounds__(256) void k_mark_visible(int P, const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_alpha: out_alpha = 1 - final_T over the whole image of a finished forward (the accumulated alpha; include/tgs_raster.h, tgs_alpha).
+// Pointwise, 4 B read + 4 B written per pixel: thread i < n4 takes pixels 4 i .. 4 i + 3 as one float4, the next `tail` threads one pixel
+// each behind them (n4 = 0 when out_alpha is not 16-byte aligned; final_T always is, img_carve).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_alpha(const float* __restrict__ final_T, float* __restrict__ out_alpha, size_t n4, size_t tail)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n4) {
+        const float4 t = reinterpret_cast<const float4*>(final_T)[i];
+        reinterpret_cast<float4*>(out_alpha)[i] = make_float4(1.f - t.x, 1.f - t.y, 1.f - t.z, 1.f - t.w);
+    } else if (i - n4 < tail) {
+        const size_t j = 4 * n4 + (i - n4);
+        out_alpha[j] = 1.f - final_T[j];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
+void launch_alpha(hipStream_t st, const ImgState& s, size_t N, float* out_alpha)
+{
+    const bool vec = ((uintptr_t)out_alpha & 15u) == 0 && ((uintptr_t)s.final_T & 15u) == 0;
+    const size_t n4 = vec ? N / 4 : 0, tail = N - 4 * n4, threads = n4 + tail;
+    if (threads > 0) hipLaunchKernelGGL(k_alpha, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, s.final_T, out_alpha, n4, tail);
+}
 void launch_preprocess_fwd(hipStream_t st, const FwdIn& in, const CamParams& cam, const GeomState& g, const ImgState& s)
 {
     const dim3 grid((unsigned)n_blocks(in.P)), blk(PRE_BLOCK);

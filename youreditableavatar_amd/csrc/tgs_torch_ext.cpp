@@ -122,8 +122,10 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
                                        const torch::Tensor& dL_dout_color, const torch::Tensor& sh, int degree, const torch::Tensor& campos,
                                        const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, bool debug,
                                        bool with_conic, int64_t tile_bound, c10::optional<bool> deterministic, int64_t mid_bound, c10::optional<bool> light_tiles,
-                                       bool need_colors, bool need_cov3D)
+                                       bool need_colors, bool need_cov3D, const c10::optional<torch::Tensor>& grad_out_alpha)
 {
+    // grad_out_alpha (extension keyword): upstream gradient of the accumulated alpha (alpha_from_state), [1,H,W] or [H,W]; None takes today's call
+    // (tgs_backward_opt) unchanged, a tensor goes to tgs_backward_alpha_opt.
     // need_colors / need_cov3D = false (extension keywords; the reference's signature has neither): the caller will discard dL_dcolors / dL_dcov3D --
     // GaussianRasterizer's backward does when the forward was given shs / scales + rotations (__init__.py:137-152 hands them to inputs that are None) --
     // so they are neither allocated nor written (empty tensors come back); dL_dconic, an intermediate of the reference's two kernels, only on request.
@@ -143,12 +145,23 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
         const Arg bg(background, dev, "background"), means(means3D, dev, "means3D"), col(colors, dev, "colors"), cov(cov3D_precomp, dev, "cov3D_precomp"),
             view(viewmatrix, dev, "viewmatrix"), proj(projmatrix, dev, "projmatrix"), shs(sh, dev, "sh"), cam(campos, dev, "campos"),
             dL(dL_dout_color, dev, "dL_dout_color");
+        const bool with_alpha = grad_out_alpha.has_value() && grad_out_alpha->defined();
+        if (with_alpha && grad_out_alpha->numel() != (int64_t)H * W) throw std::runtime_error("grad_out_alpha must have H*W elements ([1,H,W])");
+        const Arg dA(with_alpha ? *grad_out_alpha : torch::Tensor(), dev, "grad_out_alpha");
         const torch::Tensor radii_c = radii.contiguous();
         void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         const tgs_options_t opt = make_options(tile_bound, c10::nullopt, deterministic, 0, mid_bound, light_tiles);
         int r;
         {
             py::gil_scoped_release nogil;
+            if (with_alpha)
+                r = tgs_backward_alpha_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p,
+                                           tan_fovx, tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p, dA.p,
+                                           dL_dmeans2D.data_ptr<float>(), with_conic ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
+                                           want_col ? dL_dcolors.data_ptr<float>() : nullptr, dL_dmeans3D.data_ptr<float>(), want_cov ? dL_dcov3D.data_ptr<float>() : nullptr,
+                                           M ? dL_dsh.data_ptr<float>() : nullptr,
+                                           has_sr ? dL_dscales.data_ptr<float>() : nullptr, has_sr ? dL_drotations.data_ptr<float>() : nullptr, debug);
+            else
             r = tgs_backward_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p, tan_fovx,
                                  tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p,
                                  dL_dmeans2D.data_ptr<float>(), with_conic ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
@@ -160,6 +173,25 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
     }
     if (with_conic) return py::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dconic);
     return py::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations);
+}
+
+// The accumulated alpha of a finished forward (tgs_alpha): [1,H,W] = 1 - final_T.  The forward of an empty model (P == 0) carves no image
+// state -- its buffer is smaller than a frame's -- and has alpha 0 everywhere.
+torch::Tensor alpha_from_state(const torch::Tensor& imageBuffer, int H, int W)
+{
+    if (!imageBuffer.is_cuda()) throw std::runtime_error("alpha_from_state: imageBuffer must be the image state buffer of a forward, on a HIP device");
+    if (H <= 0 || W <= 0) throw std::runtime_error("alpha_from_state: bad sizes");
+    const c10::Device dev = imageBuffer.device();
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
+    size_t sizes[3];
+    tgs_state_sizes(0, W, H, 0, 0, 0, sizes);
+    if ((size_t)imageBuffer.numel() * imageBuffer.element_size() < sizes[TGS_BUF_IMAGE]) return torch::zeros({1, H, W}, f32);
+    torch::Tensor alpha = torch::empty({1, H, W}, f32);
+    void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+    const int r = tgs_alpha(stream, W, H, imageBuffer.data_ptr(), alpha.data_ptr<float>());
+    if (r < 0) raise_last(r);
+    return alpha;
 }
 
 // markVisible (rasterize_points.cu:198-217)
@@ -193,7 +225,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("dL_dout_color"), py::arg("sh"), py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"),
           py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"), py::arg("_with_conic") = false, py::arg("tile_bound") = 0,
           py::arg("deterministic") = py::none(), py::arg("mid_bound") = 0, py::arg("light_tiles") = py::none(), py::arg("need_colors") = true,
-          py::arg("need_cov3D") = true);
+          py::arg("need_cov3D") = true, py::arg("grad_out_alpha") = py::none());
+    m.def("alpha_from_state", &alpha_from_state, py::arg("imageBuffer"), py::arg("H"), py::arg("W"));
     m.def("mark_visible", &mark_visible);
     m.def("abi_version", []() { return tgs_abi_version(); });
     m.def("compiled_abi_version", []() { return TGS_ABI_VERSION; });      // the header THIS module was compiled against

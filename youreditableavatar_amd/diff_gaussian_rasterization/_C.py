@@ -56,6 +56,11 @@ def _load() -> C.CDLL:
     lib.tgs_backward_render_views_opt.argtypes = [vp, vp, it, it, it, vp]
     lib.tgs_backward_render_opt.restype = it
     lib.tgs_backward_render_opt.argtypes = [vp, vp, it, C.c_int64, vp, it, it, vp, vp, vp]
+    try:                                                     # (additive: an older A/B build of the same ABI version lacks it)
+        lib.tgs_backward_render_alpha_opt.restype = it
+        lib.tgs_backward_render_alpha_opt.argtypes = lib.tgs_backward_render_opt.argtypes + [vp]
+    except AttributeError:
+        pass
     lib.tgs_backward_batch.restype = it
     lib.tgs_backward_batch.argtypes = [vp, it, it, it, it, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, vp, vp, vp, it]
     lib.tgs_backward_batch_range.restype = it
@@ -373,16 +378,24 @@ def backward_batch_raw(stream, P, D, M, views, n_views, means3D, shs, scales, sc
 
 
 def rasterize_gaussians_backward_render(background, dL_dout_color, R, binningBuffer, imageBuffer, P, tile_bound: int = 0,
-                                        deterministic: Optional[bool] = None) -> None:
+                                        deterministic: Optional[bool] = None, grad_out_alpha: Optional[torch.Tensor] = None) -> None:
     """tgs_backward_render: the per-pixel half of one view's backward; the tile partials stay in ``binningBuffer`` for
-    ``rasterize_gaussians_backward_batch``."""
+    ``rasterize_gaussians_backward_batch``.  ``grad_out_alpha`` ([1,H,W]): upstream gradient of the accumulated alpha as well
+    (tgs_backward_render_alpha_opt); None: today's call."""
     dev = _require_gpu(dL_dout_color)
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
     with torch.cuda.device(dev):
         bg, dL = _dev_f32(background, dev, "background"), _dev_f32(dL_dout_color, dev, "dL_dout_color")
         opt = options(tile_bound=tile_bound, deterministic=deterministic)
-        r = _lib.tgs_backward_render_opt(C.byref(opt), torch.cuda.current_stream(dev).cuda_stream, int(P), int(R), _p(bg), W, H, binningBuffer.data_ptr(),
-                                         imageBuffer.data_ptr(), _p(dL))
+        if grad_out_alpha is not None:
+            if grad_out_alpha.numel() != H * W:
+                raise RuntimeError("grad_out_alpha must have H*W elements ([1,H,W])")
+            dA = _dev_f32(grad_out_alpha, dev, "grad_out_alpha")
+            r = _lib.tgs_backward_render_alpha_opt(C.byref(opt), torch.cuda.current_stream(dev).cuda_stream, int(P), int(R), _p(bg), W, H,
+                                                   binningBuffer.data_ptr(), imageBuffer.data_ptr(), _p(dL), _p(dA))
+        else:
+            r = _lib.tgs_backward_render_opt(C.byref(opt), torch.cuda.current_stream(dev).cuda_stream, int(P), int(R), _p(bg), W, H, binningBuffer.data_ptr(),
+                                             imageBuffer.data_ptr(), _p(dL))
     if r < 0:
         raise _err(int(r))
 
@@ -461,7 +474,8 @@ def state_field(name: str, P: int, width: int, height: int, R: int, has_sh: bool
 
 
 # The reference's three exports (ext.cpp:15-19): the compiled module's functions, positional signatures of rasterize_points.h:18-67
-# (+ the keyword-only extensions r_capacity / r_guess / _with_conic documented in csrc/tgs_torch_ext.cpp).
+# (+ the keyword-only extensions r_capacity / r_guess / _with_conic / grad_out_alpha documented in csrc/tgs_torch_ext.cpp).
 rasterize_gaussians = _ext.rasterize_gaussians
 rasterize_gaussians_backward = _ext.rasterize_gaussians_backward
 mark_visible = _ext.mark_visible
+alpha_from_state = _ext.alpha_from_state       # (imageBuffer, H, W) -> the frame's accumulated alpha [1,H,W] = 1 - final_T (tgs_alpha; an extension)

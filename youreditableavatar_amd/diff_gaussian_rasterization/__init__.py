@@ -135,6 +135,12 @@ _KEEP_ALL_OUTPUTS = os.environ.get("TGS_KEEP_ALL_OUTPUTS") == "1"      # A/B: ha
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+        color, radii, _img = _RasterizeGaussians.native_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+        return color, radii
+
+    @staticmethod
+    def native_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+        """the forward of both autograd nodes (this one and _RasterizeGaussiansAlpha): -> colour, radii and the frame's image state buffer"""
         rs = raster_settings
         # native argument order (__init__.py:60-80)
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
@@ -167,10 +173,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         # autograd otherwise hands backward() a zero tensor for the int32 `radii` output on every step: a P-element fill kernel (5 us at
         # 500 k Gaussians) in front of every backward pass
         ctx.set_materialize_grads(False)
-        return color, radii
+        return color, radii, img
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
+        return _RasterizeGaussians.native_backward(ctx, grad_out_color, None)
+
+    @staticmethod
+    def native_backward(ctx, grad_out_color, grad_out_alpha):
+        """grad_out_alpha None: today's native call, today's kernels; a tensor: the extension keyword of the same call"""
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:                           # the image did not take part in the loss (gradients not materialised, see forward)
@@ -186,16 +197,41 @@ class _RasterizeGaussians(torch.autograd.Function):
         # dL_dcolors / dL_dcov3D go to inputs that were None in the forward (empty tensors here, __init__.py:137-152): autograd drops them, so the
         # native backward neither allocates nor writes them (36 of the ~300 B per Gaussian its per-Gaussian kernel stores; round 6)
         need_col, need_cov = colors_precomp.numel() != 0 or _KEEP_ALL_OUTPUTS, cov3Ds_precomp.numel() != 0 or _KEEP_ALL_OUTPUTS
+        extra = {} if grad_out_alpha is None else {"grad_out_alpha": grad_out_alpha}
         (g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rots) = _call_native(
-            lambda *a: _C.rasterize_gaussians_backward(*a, tile_bound=bound, mid_bound=mid, light_tiles=ctx.light, need_colors=need_col, need_cov3D=need_cov),
+            lambda *a: _C.rasterize_gaussians_backward(*a, tile_bound=bound, mid_bound=mid, light_tiles=ctx.light, need_colors=need_col, need_cov3D=need_cov, **extra),
             args, rs.debug, "snapshot_bw.dump", "backward")
         # forward-argument order (__init__.py:143-153)
         return (g_means3D, g_means2D, g_sh if sh.numel() != 0 else None, g_colors if need_col else None, g_opac, g_scales if scales.numel() != 0 else None,
                 g_rots if rotations.numel() != 0 else None, g_cov3D if need_cov else None, None)
 
 
-def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+class _RasterizeGaussiansAlpha(torch.autograd.Function):
+    """_RasterizeGaussians with a third, differentiable output: the accumulated alpha [1,H,W] = 1 - final_T of the frame (an extension:
+    the reference's rasterizer has none), so that ``color == C_premultiplied + (1 - alpha) * bg``.  Same native forward and backward; the
+    upstream gradient of alpha travels with the colour's in ONE backward call.  Gradients stay unmaterialised: an absent colour gradient
+    becomes zeros as in _RasterizeGaussians, an absent alpha gradient launches exactly the kernels of a frame without alpha."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+        rs = raster_settings
+        color, radii, img = _RasterizeGaussians.native_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs)
+        H, W = int(rs.image_height), int(rs.image_width)
+        if means3D.shape[0] == 0:                           # (the forward of an empty model writes no image state)
+            alpha = torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device)
+        else:
+            alpha = _C.alpha_from_state(img, H, W)
+        return color, radii, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_alpha):
+        return _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha)
+
+
+def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, return_alpha=False):
+    """``return_alpha=True`` (extension): -> (color[3,H,W], radii[P], alpha[1,H,W]) with a differentiable accumulated alpha."""
+    fn = _RasterizeGaussiansAlpha if return_alpha else _RasterizeGaussians
+    return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
 
 
 class GaussianRasterizer(nn.Module):
@@ -209,7 +245,7 @@ class GaussianRasterizer(nn.Module):
             rs = self.raster_settings
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
-    def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
+    def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, return_alpha=False):
         rs = self.raster_settings
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -226,4 +262,4 @@ class GaussianRasterizer(nn.Module):
             absent if scales is None else scales,
             absent if rotations is None else rotations,
             absent if cov3D_precomp is None else cov3D_precomp,
-            rs)
+            rs, return_alpha=return_alpha)
