@@ -240,6 +240,44 @@ int tgs_backward_alpha_opt(const tgs_options_t* opt, int accumulate, void* strea
 int tgs_backward_render_alpha_opt(const tgs_options_t* opt, void* stream, int P, int64_t R, const float* background, int width, int height,
                                   const void* binning_buffer, const void* img_buffer, const float* dL_dpix, const float* dL_dalpha);
 
+/* ---- expected depth (an extension: the reference's model classes have a return_depths flag and return None for it) ----
+ * Definition: depth[H*W] = sum_i T_i * alpha_i * z_i, the alpha-weighted and NOT normalised depth of the colour frame: the sum runs over
+ * exactly the (pixel, entry) pairs that frame blended -- the same lists, the same cut-offs (power > 0, alpha < 1/255, the min(0.99, .)
+ * clamp), the same termination -- so color, alpha = sum_i T_i alpha_i and depth describe one compositing.  z_i is the view-space z of the
+ * mean, the value the forward stores and sorts by (geomState.depths).  The background contributes 0; a tile without instances, a frame the
+ * sync-free forward rejected and an empty model have depth 0 everywhere.  Normalised depth is depth / alpha, the caller's business.
+ * Gradient under an upstream dL_ddepth[H*W]:
+ *   through z_i:      d depth / d z_i = T_i alpha_i; it reaches dL_dmean3D through the third row of the view transform,
+ *                     z = m[2] x + m[6] y + m[10] z + m[14] for the flat matrix as passed here;
+ *   through alpha_i:  the reference's recursion (backward.cu:486-541) with z where the colour stands, one channel and no background term:
+ *                     dL/dalpha_i = dL_ddepth * T_i * (z_i - accum_rec_i), the min(0.99, .) clamp straight-through as everywhere; from there
+ *                     to dL_dopacity, dL_dconic, dL_dmean2D and on through the unchanged per-Gaussian pass;
+ *   dL_dcolor / dL_dsh get nothing from it.
+ * Not part of the whole-batch path (tgs_*_views, tgs_backward_batch: tgs_view_t is frozen); no median / mode depth, normals or feature channels.
+ *
+ * tgs_depth: out_depth[H*W] of a finished forward (any of the forward entry points; P, width, height as given to it, R as it returned or was
+ * given), enqueued on `stream`: a pass of its own over the frame's state, the render kernels are not involved.  P == 0 or R == 0: nothing
+ * was blended, nothing is launched and out_depth is not written (its depth is zero). */
+int tgs_depth(void* stream, int P, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
+              float* out_depth);
+
+/* tgs_backward_alpha_opt with one more upstream gradient, dL_ddepth[H*W], and dz_scratch: R floats of the caller's (one per tile instance;
+ * contents on entry do not matter), required with dL_ddepth.  dL_ddepth == NULL: exactly tgs_backward_alpha_opt, the same kernels, and
+ * dz_scratch is not looked at.  dL_dalpha may be NULL or not, independently; dL_dpix stays required.  With dL_ddepth three more kernels run
+ * (per-pixel, fixed order: two runs give the same bits; no float atomics) and the depth's share is added to the colour's in every output
+ * but dL_dcolor / dL_dsh. */
+int tgs_backward_depth_opt(const tgs_options_t* opt, int accumulate, void* stream, int P, int D, int M, int64_t R,
+                           const float* background, int width, int height,
+                           const float* means3D, const float* shs, const float* colors_precomp,
+                           const float* scales, float scale_modifier, const float* rotations,
+                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                           const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                           const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
+                           const float* dL_dpix, const float* dL_dalpha, const float* dL_ddepth, float* dz_scratch,
+                           float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                           float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                           int debug);
+
 /* present[P]: 1 byte per Gaussian, 1 iff view-space z > 0.2 (auxiliary.h:154). */
 int tgs_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix,
                      const float* projmatrix, uint8_t* present);

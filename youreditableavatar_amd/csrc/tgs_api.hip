@@ -26,6 +26,10 @@ void launch_render_bwd(hipStream_t, const ImgState&, const BinState&, int W, int
 void launch_preprocess_bwd(hipStream_t, const BwdIn&, const CamParams&, const GeomState&, const BinState&);
 void launch_preprocess_bwd_batch(hipStream_t, const BwdIn&, const BatchViews&);
 void launch_selftest_reduce36(hipStream_t, const float* in, float* out);
+// tgs_depth.hip
+void launch_depth_fwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t T, float* out_depth);
+void launch_depth_bwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t tiles, size_t R, const float* dL_ddepth, float* dz_rows);
+void launch_depth_bwd_gauss(hipStream_t, int P, const Meta* meta, const int* radii, const GeomState&, const float* view, const float* dz_rows, float* dL_dmean3D);
 }  // namespace tgs
 
 using namespace tgs;
@@ -493,6 +497,8 @@ struct BwdArgs {
     int64_t R; const int* radii; const void *geom_buffer, *binning_buffer, *img_buffer; const float* dL_dpix;
     float *dL_dmean2D, *dL_dconic, *dL_dopacity, *dL_dcolor, *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot;
     const float* dL_dalpha = nullptr;       // upstream gradient of the accumulated alpha, [H * W] (tgs_backward_alpha_opt; NULL: none)
+    const float* dL_ddepth = nullptr;       // upstream gradient of the expected depth, [H * W] (tgs_backward_depth_opt; NULL: none, and no depth kernel runs)
+    float* dz_scratch = nullptr;            // with dL_ddepth: R floats of the caller's, one per instance (the slab row has no free float for dz)
 };
 
 static BwdIn bwd_in(const Model& m)
@@ -506,12 +512,14 @@ static BwdIn bwd_in(const Model& m)
 
 // the per-pixel half of a frame's backward; the tile partials stay in the binning buffer
 static int enqueue_render_bwd(const Opts& opt, hipStream_t st, int debug, const FrameBuffers& fb, const ViewArgs& v, int64_t R, const float* dL_dpix,
-                              const float* dL_dalpha = nullptr)
+                              const float* dL_dalpha = nullptr, const float* dL_ddepth = nullptr, float* dz_scratch = nullptr)
 {
     if (R <= 0) return TGS_OK;
     const Bounds b = resolve_bounds(opt, v.T());
     return stage(st, TGS_STAGE_RENDER_BWD, "render_bwd", debug, [&] {
-        launch_render_bwd(st, fb.s, fb.b, v.width, v.height, v.gx(), b.tiles, v.background, dL_dpix, dL_dalpha, opt.deterministic, b.mid, opt.light, (uint32_t)v.T()); });
+        launch_render_bwd(st, fb.s, fb.b, v.width, v.height, v.gx(), b.tiles, v.background, dL_dpix, dL_dalpha, opt.deterministic, b.mid, opt.light, (uint32_t)v.T());
+        // the depth's shares are ADDED to the slab rows the launch above has written (same stream: ordered behind it)
+        if (dL_ddepth) launch_depth_bwd(st, fb.s, fb.b, v.width, v.height, v.gx(), b.tiles, (size_t)R, dL_ddepth, dz_scratch); });
 }
 
 // strict: tgs_backward / tgs_backward_accumulate as the reference's Rasterizer::backward declares them (every output required);
@@ -524,7 +532,7 @@ static int backward_impl(bool strict, const Opts& opt, int accumulate, hipStream
     if (int r = check_model(m, MODEL_BACKWARD)) return r;
     if (!a.geom_buffer || !a.binning_buffer || !a.img_buffer || !a.radii || !a.dL_dpix || !a.dL_dmean2D || !a.dL_dopacity || !a.dL_dmean3D ||
         (m.has_sh() && !a.dL_dsh) || (!m.has_sh() && !a.dL_dcolor) || (!m.has_sr() && !a.dL_dcov3D) ||
-        (strict && (!a.dL_dconic || (!accumulate && (!a.dL_dcolor || !a.dL_dcov3D)))))
+        (strict && (!a.dL_dconic || (!accumulate && (!a.dL_dcolor || !a.dL_dcov3D)))) || (a.dL_ddepth && !a.dz_scratch) || (a.dL_ddepth && !v.viewmatrix))
         return fail(TGS_ERR_INVALID, "NULL required pointer");
     const CamParams cam = v.cam(m.scale_modifier);
     const FrameBuffers fb = carve_frame(m.shape(), v, a.R, a.geom_buffer, a.binning_buffer, a.img_buffer);
@@ -536,8 +544,11 @@ static int backward_impl(bool strict, const Opts& opt, int accumulate, hipStream
     in.accumulate = accumulate;
     in.meta = fb.s.meta;
 
-    if (int r = enqueue_render_bwd(opt, st, debug, fb, v, a.R, a.dL_dpix, a.dL_dalpha)) return r;
-    return stage(st, TGS_STAGE_PREPROCESS_BWD, "preprocess_bwd", debug, [&] { launch_preprocess_bwd(st, in, cam, fb.g, fb.b); });
+    if (int r = enqueue_render_bwd(opt, st, debug, fb, v, a.R, a.dL_dpix, a.dL_dalpha, a.dL_ddepth, a.dz_scratch)) return r;
+    return stage(st, TGS_STAGE_PREPROCESS_BWD, "preprocess_bwd", debug, [&] {
+        launch_preprocess_bwd(st, in, cam, fb.g, fb.b);
+        // dz . (third row of the view transform) is added behind the per-Gaussian pass: it holds for `accumulate` as well
+        if (a.dL_ddepth && a.R > 0) launch_depth_bwd_gauss(st, m.P, fb.s.meta, a.radii, fb.g, v.viewmatrix, a.dz_scratch, a.dL_dmean3D); });
 }
 
 // tgs_backward_render[_views]: the view's own fields (tgs_backward_render packs its arguments into one)
@@ -750,6 +761,21 @@ int tgs_backward_alpha_opt(const tgs_options_t* o, int accumulate, void* stream,
                                  dL_dalpha}));
 }
 
+int tgs_backward_depth_opt(const tgs_options_t* o, int accumulate, void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height,
+                           const float* means3D, const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                           const int* radii, const void* geom_buffer, const void* binning_buffer, const void* img_buffer, const float* dL_dpix, const float* dL_dalpha,
+                           const float* dL_ddepth, float* dz_scratch,
+                           float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                           float* dL_drot, int debug)
+{
+    BwdArgs a{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dalpha};
+    a.dL_ddepth = dL_ddepth; a.dz_scratch = dL_ddepth ? dz_scratch : nullptr;
+    return named("tgs_backward_depth_opt", backward_impl(false, resolve_options(o), accumulate ? 1 : 0, (hipStream_t)stream, debug,
+                         Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
+                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy}, a));
+}
+
 int tgs_backward_accumulate(void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height, const float* means3D,
                             const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
                             const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
@@ -898,6 +924,21 @@ int tgs_alpha(void* stream, int width, int height, const void* img_buffer, float
     launch_alpha((hipStream_t)stream, s, v.N(), out_alpha);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(TGS_ERR_HIP, "tgs_alpha: %s", hipGetErrorString(e));
+    return TGS_OK;
+}
+
+int tgs_depth(void* stream, int P, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* img_buffer, float* out_depth)
+{
+    g_err[0] = 0;
+    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "tgs_depth: bad sizes P=%d W=%d H=%d R=%lld", P, width, height, (long long)R);
+    if (P == 0 || R == 0) return TGS_OK;                    // nothing was blended: the depth is zero and nothing is launched (the caller's zeros stand)
+    if (!geom_buffer || !binning_buffer || !img_buffer || !out_depth) return fail(TGS_ERR_INVALID, "tgs_depth: NULL required pointer");
+    const ViewArgs v{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
+    if (v.gx() > 65535u || v.gy() > 65535u) return fail(TGS_ERR_INVALID, "tgs_depth: image too large");
+    const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, R, geom_buffer, binning_buffer, img_buffer);
+    launch_depth_fwd((hipStream_t)stream, fb.s, fb.b, width, height, v.gx(), (uint32_t)v.T(), out_depth);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(TGS_ERR_HIP, "tgs_depth: %s", hipGetErrorString(e));
     return TGS_OK;
 }
 

@@ -122,8 +122,11 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
                                        const torch::Tensor& dL_dout_color, const torch::Tensor& sh, int degree, const torch::Tensor& campos,
                                        const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, bool debug,
                                        bool with_conic, int64_t tile_bound, c10::optional<bool> deterministic, int64_t mid_bound, c10::optional<bool> light_tiles,
-                                       bool need_colors, bool need_cov3D, const c10::optional<torch::Tensor>& grad_out_alpha)
+                                       bool need_colors, bool need_cov3D, const c10::optional<torch::Tensor>& grad_out_alpha,
+                                       const c10::optional<torch::Tensor>& grad_out_depth)
 {
+    // grad_out_depth (extension keyword): upstream gradient of the expected depth (depth_from_state), [1,H,W] or [H,W]; None launches no depth kernel,
+    // a tensor goes to tgs_backward_depth_opt (with grad_out_alpha or without) together with a scratch of R floats allocated here.
     // grad_out_alpha (extension keyword): upstream gradient of the accumulated alpha (alpha_from_state), [1,H,W] or [H,W]; None takes today's call
     // (tgs_backward_opt) unchanged, a tensor goes to tgs_backward_alpha_opt.
     // need_colors / need_cov3D = false (extension keywords; the reference's signature has neither): the caller will discard dL_dcolors / dL_dcov3D --
@@ -148,13 +151,25 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
         const bool with_alpha = grad_out_alpha.has_value() && grad_out_alpha->defined();
         if (with_alpha && grad_out_alpha->numel() != (int64_t)H * W) throw std::runtime_error("grad_out_alpha must have H*W elements ([1,H,W])");
         const Arg dA(with_alpha ? *grad_out_alpha : torch::Tensor(), dev, "grad_out_alpha");
+        const bool with_depth = grad_out_depth.has_value() && grad_out_depth->defined();
+        if (with_depth && grad_out_depth->numel() != (int64_t)H * W) throw std::runtime_error("grad_out_depth must have H*W elements ([1,H,W])");
+        const Arg dD(with_depth ? *grad_out_depth : torch::Tensor(), dev, "grad_out_depth");
+        const torch::Tensor dz_scratch = with_depth ? torch::empty({R > 0 ? R : 1}, dL_dmeans3D.options()) : torch::Tensor();
         const torch::Tensor radii_c = radii.contiguous();
         void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         const tgs_options_t opt = make_options(tile_bound, c10::nullopt, deterministic, 0, mid_bound, light_tiles);
         int r;
         {
             py::gil_scoped_release nogil;
-            if (with_alpha)
+            if (with_depth)
+                r = tgs_backward_depth_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p,
+                                           tan_fovx, tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p,
+                                           with_alpha ? dA.p : nullptr, dD.p, dz_scratch.data_ptr<float>(),
+                                           dL_dmeans2D.data_ptr<float>(), with_conic ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
+                                           want_col ? dL_dcolors.data_ptr<float>() : nullptr, dL_dmeans3D.data_ptr<float>(), want_cov ? dL_dcov3D.data_ptr<float>() : nullptr,
+                                           M ? dL_dsh.data_ptr<float>() : nullptr,
+                                           has_sr ? dL_dscales.data_ptr<float>() : nullptr, has_sr ? dL_drotations.data_ptr<float>() : nullptr, debug);
+            else if (with_alpha)
                 r = tgs_backward_alpha_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p,
                                            tan_fovx, tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p, dA.p,
                                            dL_dmeans2D.data_ptr<float>(), with_conic ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
@@ -194,6 +209,29 @@ torch::Tensor alpha_from_state(const torch::Tensor& imageBuffer, int H, int W)
     return alpha;
 }
 
+// The expected depth of a finished forward (tgs_depth): [1,H,W] = sum_i T_i alpha_i z_i over the pairs the colour frame blended.  An empty
+// model or a frame without instances (P == 0 / R == 0) has depth 0 everywhere and launches nothing.
+torch::Tensor depth_from_state(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, int P, int H, int W, int64_t R)
+{
+    if (!imageBuffer.is_cuda()) throw std::runtime_error("depth_from_state: the state buffers must be those of a forward, on a HIP device");
+    if (P < 0 || H <= 0 || W <= 0 || R < 0) throw std::runtime_error("depth_from_state: bad sizes");
+    const c10::Device dev = imageBuffer.device();
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
+    if (P == 0 || R == 0) return torch::zeros({1, H, W}, f32);
+    size_t sizes[3];
+    tgs_state_sizes(P, W, H, 0, 0, R, sizes);
+    const auto bytes = [](const torch::Tensor& t) { return (size_t)t.numel() * t.element_size(); };
+    if (!geomBuffer.is_cuda() || !binningBuffer.is_cuda() || bytes(geomBuffer) < sizes[TGS_BUF_GEOM] || bytes(binningBuffer) < sizes[TGS_BUF_BINNING] ||
+        bytes(imageBuffer) < sizes[TGS_BUF_IMAGE])
+        throw std::runtime_error("depth_from_state: state buffers smaller than a frame of these sizes");
+    torch::Tensor depth = torch::empty({1, H, W}, f32);
+    void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+    const int r = tgs_depth(stream, P, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), depth.data_ptr<float>());
+    if (r < 0) raise_last(r);
+    return depth;
+}
+
 // markVisible (rasterize_points.cu:198-217)
 torch::Tensor mark_visible(const torch::Tensor& means3D, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix)
 {
@@ -225,7 +263,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("dL_dout_color"), py::arg("sh"), py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"),
           py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"), py::arg("_with_conic") = false, py::arg("tile_bound") = 0,
           py::arg("deterministic") = py::none(), py::arg("mid_bound") = 0, py::arg("light_tiles") = py::none(), py::arg("need_colors") = true,
-          py::arg("need_cov3D") = true, py::arg("grad_out_alpha") = py::none());
+          py::arg("need_cov3D") = true, py::arg("grad_out_alpha") = py::none(), py::arg("grad_out_depth") = py::none());
+    m.def("depth_from_state", &depth_from_state, py::arg("geomBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("P"), py::arg("H"), py::arg("W"), py::arg("R"));
     m.def("alpha_from_state", &alpha_from_state, py::arg("imageBuffer"), py::arg("H"), py::arg("W"));
     m.def("mark_visible", &mark_visible);
     m.def("abi_version", []() { return tgs_abi_version(); });

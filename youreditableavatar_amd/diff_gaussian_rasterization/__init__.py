@@ -139,8 +139,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         return color, radii
 
     @staticmethod
-    def native_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-        """the forward of both autograd nodes (this one and _RasterizeGaussiansAlpha): -> colour, radii and the frame's image state buffer"""
+    def native_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, with_state=False):
+        """the forward of both autograd nodes (this one and _RasterizeGaussiansExt): -> colour, radii and the frame's image state buffer
+        (with_state: and its geometry and binning buffers behind it)"""
         rs = raster_settings
         # native argument order (__init__.py:60-80)
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
@@ -173,6 +174,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         # autograd otherwise hands backward() a zero tensor for the int32 `radii` output on every step: a P-element fill kernel (5 us at
         # 500 k Gaussians) in front of every backward pass
         ctx.set_materialize_grads(False)
+        if with_state:
+            return color, radii, img, geom, binning
         return color, radii, img
 
     @staticmethod
@@ -180,8 +183,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         return _RasterizeGaussians.native_backward(ctx, grad_out_color, None)
 
     @staticmethod
-    def native_backward(ctx, grad_out_color, grad_out_alpha):
-        """grad_out_alpha None: today's native call, today's kernels; a tensor: the extension keyword of the same call"""
+    def native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth=None):
+        """grad_out_alpha / grad_out_depth None: today's native call, today's kernels; a tensor: the extension keyword of the same call"""
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:                           # the image did not take part in the loss (gradients not materialised, see forward)
@@ -198,6 +201,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         # native backward neither allocates nor writes them (36 of the ~300 B per Gaussian its per-Gaussian kernel stores; round 6)
         need_col, need_cov = colors_precomp.numel() != 0 or _KEEP_ALL_OUTPUTS, cov3Ds_precomp.numel() != 0 or _KEEP_ALL_OUTPUTS
         extra = {} if grad_out_alpha is None else {"grad_out_alpha": grad_out_alpha}
+        if grad_out_depth is not None:
+            extra["grad_out_depth"] = grad_out_depth
         (g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rots) = _call_native(
             lambda *a: _C.rasterize_gaussians_backward(*a, tile_bound=bound, mid_bound=mid, light_tiles=ctx.light, need_colors=need_col, need_cov3D=need_cov, **extra),
             args, rs.debug, "snapshot_bw.dump", "backward")
@@ -206,32 +211,54 @@ class _RasterizeGaussians(torch.autograd.Function):
                 g_rots if rotations.numel() != 0 else None, g_cov3D if need_cov else None, None)
 
 
-class _RasterizeGaussiansAlpha(torch.autograd.Function):
-    """_RasterizeGaussians with a third, differentiable output: the accumulated alpha [1,H,W] = 1 - final_T of the frame (an extension:
-    the reference's rasterizer has none), so that ``color == C_premultiplied + (1 - alpha) * bg``.  Same native forward and backward; the
-    upstream gradient of alpha travels with the colour's in ONE backward call.  Gradients stay unmaterialised: an absent colour gradient
-    becomes zeros as in _RasterizeGaussians, an absent alpha gradient launches exactly the kernels of a frame without alpha."""
+class _RasterizeGaussiansExt(torch.autograd.Function):
+    """_RasterizeGaussians with further differentiable outputs behind (color, radii), each on request (extensions: the reference's
+    rasterizer has neither):
+      alpha [1,H,W] = 1 - final_T of the frame, so that ``color == C_premultiplied + (1 - alpha) * bg``;
+      depth [1,H,W] = sum_i T_i alpha_i z_i over the pairs the colour frame blended (expected depth, not normalised; z = view-space z).
+    Same native forward and backward; the upstream gradients of the extra outputs travel with the colour's in ONE backward call.
+    Gradients stay unmaterialised: an absent colour gradient becomes zeros as in _RasterizeGaussians, an absent alpha / depth gradient
+    launches exactly the kernels of a frame without that output."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, want_alpha, want_depth):
         rs = raster_settings
-        color, radii, img = _RasterizeGaussians.native_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs)
-        H, W = int(rs.image_height), int(rs.image_width)
-        if means3D.shape[0] == 0:                           # (the forward of an empty model writes no image state)
-            alpha = torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device)
-        else:
-            alpha = _C.alpha_from_state(img, H, W)
-        return color, radii, alpha
+        color, radii, img, geom, binning = _RasterizeGaussians.native_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs,
+                                                                              with_state=True)
+        H, W, P = int(rs.image_height), int(rs.image_width), int(means3D.shape[0])
+        ctx.want_alpha, ctx.want_depth = bool(want_alpha), bool(want_depth)
+        out = [color, radii]
+        if want_alpha:
+            if P == 0:                                          # (the forward of an empty model writes no image state)
+                out.append(torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device))
+            else:
+                out.append(_C.alpha_from_state(img, H, W))
+        if want_depth:
+            if P == 0:
+                out.append(torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device))
+            else:
+                out.append(_C.depth_from_state(geom, binning, img, P, H, W, int(ctx.num_rendered)))
+        return tuple(out)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_out_alpha):
-        return _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha)
+    def backward(ctx, grad_out_color, _grad_radii, *extra):
+        extra = list(extra)
+        grad_out_alpha = extra.pop(0) if ctx.want_alpha else None
+        grad_out_depth = extra.pop(0) if ctx.want_depth else None
+        return _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth) + (None, None)
 
 
-def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, return_alpha=False):
-    """``return_alpha=True`` (extension): -> (color[3,H,W], radii[P], alpha[1,H,W]) with a differentiable accumulated alpha."""
-    fn = _RasterizeGaussiansAlpha if return_alpha else _RasterizeGaussians
-    return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+_RasterizeGaussiansAlpha = _RasterizeGaussiansExt           # (the name of the node when it had one extra output)
+
+
+def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, return_alpha=False,
+                        return_depth=False):
+    """``return_alpha=True`` / ``return_depth=True`` (extensions): -> (color[3,H,W], radii[P]), then alpha[1,H,W] if asked, then depth[1,H,W]
+    if asked -- the differentiable accumulated alpha and expected depth of the same compositing."""
+    if return_alpha or return_depth:
+        return _RasterizeGaussiansExt.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                                            bool(return_alpha), bool(return_depth))
+    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
 
 
 class GaussianRasterizer(nn.Module):
@@ -245,7 +272,7 @@ class GaussianRasterizer(nn.Module):
             rs = self.raster_settings
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
-    def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, return_alpha=False):
+    def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, return_alpha=False, return_depth=False):
         rs = self.raster_settings
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -262,4 +289,4 @@ class GaussianRasterizer(nn.Module):
             absent if scales is None else scales,
             absent if rotations is None else rotations,
             absent if cov3D_precomp is None else cov3D_precomp,
-            rs, return_alpha=return_alpha)
+            rs, return_alpha=return_alpha, return_depth=return_depth)
