@@ -253,7 +253,8 @@ int tgs_backward_render_alpha_opt(const tgs_options_t* opt, void* stream, int P,
  *                     dL/dalpha_i = dL_ddepth * T_i * (z_i - accum_rec_i), the min(0.99, .) clamp straight-through as everywhere; from there
  *                     to dL_dopacity, dL_dconic, dL_dmean2D and on through the unchanged per-Gaussian pass;
  *   dL_dcolor / dL_dsh get nothing from it.
- * Not part of the whole-batch path (tgs_*_views, tgs_backward_batch: tgs_view_t is frozen); no median / mode depth, normals or feature channels.
+ * Not part of the whole-batch path (tgs_*_views, tgs_backward_batch: tgs_view_t is frozen); no median / mode depth; normals and
+ * feature channels are tgs_features below.
  *
  * tgs_depth: out_depth[H*W] of a finished forward (any of the forward entry points; P, width, height as given to it, R as it returned or was
  * given), enqueued on `stream`: a pass of its own over the frame's state, the render kernels are not involved.  P == 0 or R == 0: nothing
@@ -277,6 +278,48 @@ int tgs_backward_depth_opt(const tgs_options_t* opt, int accumulate, void* strea
                            float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                            float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                            int debug);
+
+/* ---- per-Gaussian feature channels (an extension: normals, keep / edit masks, labels composited like the colour) ----
+ * #define TGS_FEATURE_MAX_CHANNELS: the largest C.
+ * Definition: for features[P*C] (row i = Gaussian i, 1 <= C <= 16)
+ *     feature_map[c*H*W + p] = sum_i T_i(p) * alpha_i(p) * features[i*C + c]
+ * over exactly the (pixel, entry) pairs the colour frame blended -- the same lists, cut-offs, clamp and termination as tgs_depth, which is
+ * the case "one channel, the feature is z".  Values are signed and nothing is clamped; the background contributes 0; the map is NOT
+ * normalised (feature_map / alpha is the caller's expression).  A tile without instances, a frame without visible Gaussians, a frame the
+ * sync-free forward rejected and an empty model give exactly 0.
+ * Gradient under an upstream dL_dfeature_map[C*H*W] (g_c):
+ *   through features:  dL_dfeatures[i*C + c] = sum_p g_c(p) T_i(p) alpha_i(p); the rows of culled Gaussians are exactly 0;
+ *   through alpha_i:   the reference's recursion (backward.cu:486-541) with the feature where the colour stands and no background term:
+ *                      dL/dalpha_i = T_i * sum_c g_c * (f_ic - accum_rec_ic); from there to dL_dopacity, dL_dconic, dL_dmean2D as the
+ *                      colour's share (added to it) and on through the unchanged per-Gaussian pass;
+ *   dL_dcolor / dL_dsh get nothing from it.
+ * Channels travel in groups of 8 per launch (C = 9 .. 16: two launches each way).  No float atomics: two runs give the same bits.
+ * Not part of the whole-batch path (tgs_*_views, tgs_backward_batch: tgs_view_t is frozen).
+ *
+ * tgs_features: out[C*H*W] of a finished forward (P, width, height as given to it, R as it returned or was given), enqueued on `stream`: a
+ * pass of its own over the frame's state, the render kernels are not involved.  P == 0 or R == 0: nothing was blended, nothing is launched
+ * and out is not written (the map is zero). */
+#define TGS_FEATURE_MAX_CHANNELS 16
+int tgs_features(void* stream, int P, int C, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer,
+                 const void* img_buffer, const float* features, float* out);
+
+/* tgs_backward_depth_opt with five more arguments: C, features[P*C], the upstream dL_dfeature_map[C*H*W], feature_scratch (R*C floats of the
+ * caller's; contents on entry do not matter) and the output dL_dfeatures[P*C] (written; added to with `accumulate`).
+ * dL_dfeature_map == NULL: exactly tgs_backward_depth_opt, the same kernels, and the other four are not looked at.  Otherwise features,
+ * feature_scratch and dL_dfeatures are required and 1 <= C <= TGS_FEATURE_MAX_CHANNELS.  dL_dalpha and dL_ddepth may be NULL or not,
+ * independently; dL_dpix stays required. */
+int tgs_backward_features_opt(const tgs_options_t* opt, int accumulate, void* stream, int P, int D, int M, int64_t R,
+                              const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp,
+                              const float* scales, float scale_modifier, const float* rotations,
+                              const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                              const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                              const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
+                              const float* dL_dpix, const float* dL_dalpha, const float* dL_ddepth, float* dz_scratch,
+                              int C, const float* features, const float* dL_dfeature_map, float* feature_scratch, float* dL_dfeatures,
+                              float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                              int debug);
 
 /* present[P]: 1 byte per Gaussian, 1 iff view-space z > 0.2 (auxiliary.h:154). */
 int tgs_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix,

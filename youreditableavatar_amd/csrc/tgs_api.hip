@@ -30,6 +30,11 @@ void launch_selftest_reduce36(hipStream_t, const float* in, float* out);
 void launch_depth_fwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t T, float* out_depth);
 void launch_depth_bwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t tiles, size_t R, const float* dL_ddepth, float* dz_rows);
 void launch_depth_bwd_gauss(hipStream_t, int P, const Meta* meta, const int* radii, const GeomState&, const float* view, const float* dz_rows, float* dL_dmean3D);
+// tgs_feature.hip
+void launch_feat_fwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t T, int P, int C, const float* features, float* out);
+void launch_feat_bwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t tiles, size_t R, int P, int C, const float* features,
+                     const float* dL_dmap, float* feat_rows);
+void launch_feat_bwd_gauss(hipStream_t, int P, int C, const Meta* meta, const int* radii, const GeomState&, const float* feat_rows, float* dL_dfeatures, int accumulate);
 }  // namespace tgs
 
 using namespace tgs;
@@ -499,6 +504,9 @@ struct BwdArgs {
     const float* dL_dalpha = nullptr;       // upstream gradient of the accumulated alpha, [H * W] (tgs_backward_alpha_opt; NULL: none)
     const float* dL_ddepth = nullptr;       // upstream gradient of the expected depth, [H * W] (tgs_backward_depth_opt; NULL: none, and no depth kernel runs)
     float* dz_scratch = nullptr;            // with dL_ddepth: R floats of the caller's, one per instance (the slab row has no free float for dz)
+    // tgs_backward_features_opt: upstream gradient of the feature map, [C * H * W] (NULL: none, and no feature kernel runs); with it the
+    // features [P * C], R * C floats of the caller's and the output dL_dfeatures [P * C]
+    int C = 0; const float* features = nullptr; const float* dL_dfeat_map = nullptr; float* feat_scratch = nullptr; float* dL_dfeatures = nullptr;
 };
 
 static BwdIn bwd_in(const Model& m)
@@ -512,14 +520,17 @@ static BwdIn bwd_in(const Model& m)
 
 // the per-pixel half of a frame's backward; the tile partials stay in the binning buffer
 static int enqueue_render_bwd(const Opts& opt, hipStream_t st, int debug, const FrameBuffers& fb, const ViewArgs& v, int64_t R, const float* dL_dpix,
-                              const float* dL_dalpha = nullptr, const float* dL_ddepth = nullptr, float* dz_scratch = nullptr)
+                              const float* dL_dalpha = nullptr, const float* dL_ddepth = nullptr, float* dz_scratch = nullptr, const BwdArgs* feat = nullptr, int P = 0)
 {
     if (R <= 0) return TGS_OK;
     const Bounds b = resolve_bounds(opt, v.T());
     return stage(st, TGS_STAGE_RENDER_BWD, "render_bwd", debug, [&] {
         launch_render_bwd(st, fb.s, fb.b, v.width, v.height, v.gx(), b.tiles, v.background, dL_dpix, dL_dalpha, opt.deterministic, b.mid, opt.light, (uint32_t)v.T());
         // the depth's shares are ADDED to the slab rows the launch above has written (same stream: ordered behind it)
-        if (dL_ddepth) launch_depth_bwd(st, fb.s, fb.b, v.width, v.height, v.gx(), b.tiles, (size_t)R, dL_ddepth, dz_scratch); });
+        if (dL_ddepth) launch_depth_bwd(st, fb.s, fb.b, v.width, v.height, v.gx(), b.tiles, (size_t)R, dL_ddepth, dz_scratch);
+        // so are the feature channels' (a group of 8 channels per launch, each adding its share)
+        if (feat && feat->dL_dfeat_map)
+            launch_feat_bwd(st, fb.s, fb.b, v.width, v.height, v.gx(), b.tiles, (size_t)R, P, feat->C, feat->features, feat->dL_dfeat_map, feat->feat_scratch); });
 }
 
 // strict: tgs_backward / tgs_backward_accumulate as the reference's Rasterizer::backward declares them (every output required);
@@ -532,8 +543,10 @@ static int backward_impl(bool strict, const Opts& opt, int accumulate, hipStream
     if (int r = check_model(m, MODEL_BACKWARD)) return r;
     if (!a.geom_buffer || !a.binning_buffer || !a.img_buffer || !a.radii || !a.dL_dpix || !a.dL_dmean2D || !a.dL_dopacity || !a.dL_dmean3D ||
         (m.has_sh() && !a.dL_dsh) || (!m.has_sh() && !a.dL_dcolor) || (!m.has_sr() && !a.dL_dcov3D) ||
-        (strict && (!a.dL_dconic || (!accumulate && (!a.dL_dcolor || !a.dL_dcov3D)))) || (a.dL_ddepth && !a.dz_scratch) || (a.dL_ddepth && !v.viewmatrix))
+        (strict && (!a.dL_dconic || (!accumulate && (!a.dL_dcolor || !a.dL_dcov3D)))) || (a.dL_ddepth && !a.dz_scratch) || (a.dL_ddepth && !v.viewmatrix) ||
+        (a.dL_dfeat_map && (!a.features || !a.feat_scratch || !a.dL_dfeatures)))
         return fail(TGS_ERR_INVALID, "NULL required pointer");
+    if (a.dL_dfeat_map && (a.C < 1 || a.C > TGS_FEATURE_MAX_CHANNELS)) return fail(TGS_ERR_INVALID, "bad channel count C=%d (1 .. %d)", a.C, TGS_FEATURE_MAX_CHANNELS);
     const CamParams cam = v.cam(m.scale_modifier);
     const FrameBuffers fb = carve_frame(m.shape(), v, a.R, a.geom_buffer, a.binning_buffer, a.img_buffer);
 
@@ -544,11 +557,13 @@ static int backward_impl(bool strict, const Opts& opt, int accumulate, hipStream
     in.accumulate = accumulate;
     in.meta = fb.s.meta;
 
-    if (int r = enqueue_render_bwd(opt, st, debug, fb, v, a.R, a.dL_dpix, a.dL_dalpha, a.dL_ddepth, a.dz_scratch)) return r;
+    if (int r = enqueue_render_bwd(opt, st, debug, fb, v, a.R, a.dL_dpix, a.dL_dalpha, a.dL_ddepth, a.dz_scratch, &a, m.P)) return r;
     return stage(st, TGS_STAGE_PREPROCESS_BWD, "preprocess_bwd", debug, [&] {
         launch_preprocess_bwd(st, in, cam, fb.g, fb.b);
         // dz . (third row of the view transform) is added behind the per-Gaussian pass: it holds for `accumulate` as well
-        if (a.dL_ddepth && a.R > 0) launch_depth_bwd_gauss(st, m.P, fb.s.meta, a.radii, fb.g, v.viewmatrix, a.dz_scratch, a.dL_dmean3D); });
+        if (a.dL_ddepth && a.R > 0) launch_depth_bwd_gauss(st, m.P, fb.s.meta, a.radii, fb.g, v.viewmatrix, a.dz_scratch, a.dL_dmean3D);
+        // the feature rows of every Gaussian (a frame without instances: zero rows, the scratch is not read)
+        if (a.dL_dfeat_map) launch_feat_bwd_gauss(st, m.P, a.C, fb.s.meta, a.radii, fb.g, a.feat_scratch, a.dL_dfeatures, accumulate); });
 }
 
 // tgs_backward_render[_views]: the view's own fields (tgs_backward_render packs its arguments into one)
@@ -776,6 +791,27 @@ int tgs_backward_depth_opt(const tgs_options_t* o, int accumulate, void* stream,
                          ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy}, a));
 }
 
+int tgs_backward_features_opt(const tgs_options_t* o, int accumulate, void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                              const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                              const int* radii, const void* geom_buffer, const void* binning_buffer, const void* img_buffer, const float* dL_dpix, const float* dL_dalpha,
+                              const float* dL_ddepth, float* dz_scratch,
+                              int C, const float* features, const float* dL_dfeature_map, float* feature_scratch, float* dL_dfeatures,
+                              float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                              float* dL_drot, int debug)
+{
+    if (!dL_dfeature_map)                                   // exactly the depth call: the other four arguments are not looked at
+        return tgs_backward_depth_opt(o, accumulate, stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
+                                      cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dalpha,
+                                      dL_ddepth, dz_scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug);
+    BwdArgs a{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dalpha};
+    a.dL_ddepth = dL_ddepth; a.dz_scratch = dL_ddepth ? dz_scratch : nullptr;
+    a.C = C; a.features = features; a.dL_dfeat_map = dL_dfeature_map; a.feat_scratch = feature_scratch; a.dL_dfeatures = dL_dfeatures;
+    return named("tgs_backward_features_opt", backward_impl(false, resolve_options(o), accumulate ? 1 : 0, (hipStream_t)stream, debug,
+                         Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
+                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy}, a));
+}
+
 int tgs_backward_accumulate(void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height, const float* means3D,
                             const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
                             const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
@@ -939,6 +975,23 @@ int tgs_depth(void* stream, int P, int width, int height, int64_t R, const void*
     launch_depth_fwd((hipStream_t)stream, fb.s, fb.b, width, height, v.gx(), (uint32_t)v.T(), out_depth);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(TGS_ERR_HIP, "tgs_depth: %s", hipGetErrorString(e));
+    return TGS_OK;
+}
+
+int tgs_features(void* stream, int P, int C, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
+                 const float* features, float* out)
+{
+    g_err[0] = 0;
+    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "tgs_features: bad sizes P=%d W=%d H=%d R=%lld", P, width, height, (long long)R);
+    if (C < 1 || C > TGS_FEATURE_MAX_CHANNELS) return fail(TGS_ERR_INVALID, "tgs_features: bad channel count C=%d (1 .. %d)", C, TGS_FEATURE_MAX_CHANNELS);
+    if (P == 0 || R == 0) return TGS_OK;                    // nothing was blended: the map is zero and nothing is launched (the caller's zeros stand)
+    if (!geom_buffer || !binning_buffer || !img_buffer || !features || !out) return fail(TGS_ERR_INVALID, "tgs_features: NULL required pointer");
+    const ViewArgs v{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
+    if (v.gx() > 65535u || v.gy() > 65535u) return fail(TGS_ERR_INVALID, "tgs_features: image too large");
+    const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, R, geom_buffer, binning_buffer, img_buffer);
+    launch_feat_fwd((hipStream_t)stream, fb.s, fb.b, width, height, v.gx(), (uint32_t)v.T(), P, C, features, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(TGS_ERR_HIP, "tgs_features: %s", hipGetErrorString(e));
     return TGS_OK;
 }
 

@@ -1,0 +1,370 @@
+// tgs_feature.hip -- per-Gaussian feature channels composited over a finished colour frame, and their gradients, for gfx950 (wave64).
+//
+//   k_feat_fwd        feature_map[c](p) = sum_i T_i(p) alpha_i(p) features[i, c] over exactly the (pixel, entry) pairs the colour frame blended
+//   k_feat_bwd        back to front: the gradient of those sums through alpha_i (added into the slab rows the colour's per-pixel backward has
+//                     written, as k_depth_bwd adds its share) and through features[i, c] (a per-instance scratch row of C floats)
+//   k_feat_bwd_gauss  per Gaussian: sum of its scratch rows, in row order, into dL_dfeatures[i, :]
+//
+// tgs_depth.hip is the special case "one channel, the feature is z"; geometry, staging and the pair replay are its (256 threads per tile, one
+// lane per pixel, wave w owns the 8x8-pixel quadrant w, depth_pair_alpha / tile_deepest of tgs_device.hpp).  The feature row of a staged entry
+// is gathered by the Gaussian index, the low word of the instance's sorted key, and lies in LDS beside the records.
+// Channels travel in groups of at most FGROUP = 8 per launch (C = 9 .. 16: two launches each way).  The through-alpha share is linear in the
+// channels, so each launch adds its own share to the slab rows: launches on one stream are ordered and a row has one writer.  The kernels are
+// compiled for 4 and for 8 channel slots (a group of 1 .. 4 channels takes the narrow one; slots behind the group hold zeros and store nothing).
+// Signed values, nothing clamped, no float atomics: two runs give the same bits.
+#include "tgs_device.hpp"
+
+namespace tgs {
+
+constexpr int FGROUP = 8;          // channels per launch: 8 channels x 4 entries are one wave_reduce36 call
+constexpr int FGEO = 6;            // mean2D xy, conic xx / xy / yy, opacity
+constexpr int FSTRIDE = 9;         // wave_reduce36 sums 4 entries x 9 components
+// k_feat_bwd stages FCHUNK entries per round, not RCHUNK: the per-wave partial sums are 4 x (6 + 8) x (FCHUNK + 1) floats = 28.9 KB; at 256
+// entries they alone would be 57.6 KB on top of the staging arrays.  (The staging arrays keep RCHUNK + 1 slots: RNULL is the lists' padding.)
+constexpr int FCHUNK = 128;
+
+// the feature row of Gaussian `idx`, channels c0 .. c0 + nc - 1, into NC slots (zeros behind the group)
+template <int NC>
+__device__ __forceinline__ void load_feature_row(const float* __restrict__ features, uint32_t idx, int C, int c0, int nc, float4 (&f)[NC / 4])
+{
+    const float* row = features + (size_t)idx * C + c0;
+    float v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) v[c] = c < nc ? row[c] : 0.f;
+#pragma unroll
+    for (int q = 0; q < NC / 4; q++) f[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_feat_fwd: one workgroup per tile of tile_desc (the output is zero-filled in front of the launches, which is what a rejected frame, a tile
+// without instances and the workgroups behind the tiles with instances keep).  Each accumulation is one fmaf on w = alpha T, so a channel's
+// bits do not depend on its slot, its group or the channels that travel with it.
+// ---------------------------------------------------------------------------------------------
+template <int NC>
+__global__ __launch_bounds__(256) void k_feat_fwd(const ImgState s, const BinState b, int W, int H, uint32_t gx, uint32_t P, int C, int c0, int nc,
+                                                  const float* __restrict__ features, float* __restrict__ out)
+{
+    __shared__ float4 sA[RCHUNK + 1];
+    __shared__ float4 sB[RCHUNK + 1];
+    __shared__ float4 sF[NC / 4][RCHUNK + 1];
+    __shared__ QuadLists L;
+    __shared__ uint32_t wmax[4];
+
+    const uint2 ff = frame_flags(s);
+    if ((ff.x & META_ERR_CAPACITY) || blockIdx.x >= ff.y) return;
+    const uint4 td = s.tile_desc[blockIdx.x];
+    const uint32_t tile = td.x;
+    const uint32_t tx = tile % gx, ty = tile / gx;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int px = tx * TILE + (wv & 1) * 8 + (lane & 7);
+    const int py = ty * TILE + (wv >> 1) * 8 + (lane >> 3);
+    const bool inside = px < W && py < H;
+    const float pixfx = (float)px, pixfy = (float)py;
+    const uint32_t start = td.y, n = td.z - td.y;
+    const size_t pix_id = (size_t)W * py + px;
+    const uint32_t last_contributor = inside ? s.n_contrib[pix_id] : 0u;
+    const uint32_t qmax = min(tile_deepest(last_contributor, wmax, wv, lane), n);
+    if (qmax == 0) return;
+    if (threadIdx.x == 0) {
+        sA[RNULL] = make_float4(0.f, 0.f, 0.f, 0.f); sB[RNULL] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int q = 0; q < NC / 4; q++) sF[q][RNULL] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+
+    float T = 1.0f, F[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) F[c] = 0.f;
+    for (uint32_t base = 0; base < qmax; base += RCHUNK) {
+        const uint32_t cnt = min((uint32_t)RCHUNK, qmax - base);
+        __syncthreads();                                    // the previous round's records have been read
+        uint32_t qm = 0;
+        if (threadIdx.x < cnt) {
+            const uint32_t pos = start + base + threadIdx.x;
+            sA[threadIdx.x] = b.recA[pos]; sB[threadIdx.x] = b.recB[pos];
+            float4 f[NC / 4];
+            load_feature_row<NC>(features, min((uint32_t)b.keys[pos], P - 1u), C, c0, nc, f);
+#pragma unroll
+            for (int q = 0; q < NC / 4; q++) sF[q][threadIdx.x] = f[q];
+            qm = block_to_quadrant_mask(__float_as_uint(b.recC[pos].y));
+        }
+        build_quad_lists(L, qm, wv, lane);
+        __syncthreads();
+#pragma unroll 1
+        for (int sw = 0; sw < 4; sw++) {                    // staging waves in order: the quadrant's entries front to back
+            const uint32_t nl = __builtin_amdgcn_readfirstlane(L.cnt[wv][sw]);
+#pragma unroll 1
+            for (uint32_t k = 0; k < nl; k += RUNROLL) {
+                const uint2 pk = *reinterpret_cast<const uint2*>(&L.idx[wv][sw][k]);
+                const uint32_t j[RUNROLL] = {pk.x & 0xffffu, pk.x >> 16, pk.y & 0xffffu, pk.y >> 16};
+                float4 a[RUNROLL], bb[RUNROLL];
+#pragma unroll
+                for (int u = 0; u < RUNROLL; u++) { a[u] = sA[j[u]]; bb[u] = sB[j[u]]; }
+#pragma unroll
+                for (int u = 0; u < RUNROLL; u++) {
+                    float G; bool cut;
+                    const float alpha = depth_pair_alpha(a[u], bb[u], a[u].x - pixfx, a[u].y - pixfy, G, cut);
+                    // 1-based list position base + j + 1 <= n_contrib; a padding entry (slot RNULL) has opacity 0 and is cut
+                    if (base + j[u] < last_contributor && !cut) {
+                        const float w = alpha * T;
+#pragma unroll
+                        for (int q = 0; q < NC / 4; q++) {
+                            const float4 f = sF[q][j[u]];
+                            F[4 * q + 0] = fmaf(f.x, w, F[4 * q + 0]); F[4 * q + 1] = fmaf(f.y, w, F[4 * q + 1]);
+                            F[4 * q + 2] = fmaf(f.z, w, F[4 * q + 2]); F[4 * q + 3] = fmaf(f.w, w, F[4 * q + 3]);
+                        }
+                        T = T * (1.f - alpha);
+                    }
+                }
+            }
+        }
+    }
+    if (inside) {
+        const size_t N = (size_t)W * H;
+#pragma unroll
+        for (int c = 0; c < NC; c++) if (c < nc) out[(size_t)(c0 + c) * N + pix_id] = F[c];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_feat_bwd: backward.cu:486-541 with the feature where the colour stands, the group's channels, no background term.  Per blended pair,
+// back to front:
+//   T <- T / (1 - alpha)  (from final_T),   df_c += g_c alpha T,   dL_dalpha = T sum_c g_c (f_c - accum_rec_c),
+//   accum_rec_c <- alpha f_c + (1 - alpha) accum_rec_c
+// and from dL_dalpha the mean2D, conic and opacity terms as the colour's (backward.cu:537-555).  Entry j's sums over the tile's pixels:
+// wave_reduce36 inside a wave (the six geometry sums are one call, the channels a second), the four waves in order at the flush, which ADDS
+// the geometry sums into the instance's slab row (hi + lo for the conic, as k_depth_bwd) and stores the channel sums to
+// feat_rows[slot * C + c0 ..] (zero-filled in front of the launches; a row has one writer: this tile's workgroup).
+// ---------------------------------------------------------------------------------------------
+template <int NC>
+__global__ __launch_bounds__(256) void k_feat_bwd(const ImgState s, const BinState b, int W, int H, uint32_t gx, uint32_t P, int C, int c0, int nc,
+                                                  const float* __restrict__ features, const float* __restrict__ dL_dmap, float* __restrict__ feat_rows)
+{
+    constexpr int FACC = FGEO + NC;
+    __shared__ float4 sA[RCHUNK + 1];
+    __shared__ float4 sB[RCHUNK + 1];
+    __shared__ float4 sF[NC / 4][RCHUNK + 1];
+    __shared__ uint32_t sSlot[FCHUNK];
+    __shared__ float wacc[4][FACC][FCHUNK + 1];            // per-wave partial sums of the current round (+1: null slot)
+    __shared__ unsigned long long touched[4][FCHUNK / 64];
+    __shared__ QuadLists L;
+    __shared__ uint32_t wmax[4];
+
+    const uint2 ff = frame_flags(s);
+    if ((ff.x & META_ERR_CAPACITY) || blockIdx.x >= ff.y) return;
+    const uint4 td = s.tile_desc[blockIdx.x];
+    const uint32_t tile = td.x;
+    const uint32_t tx = tile % gx, ty = tile / gx;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int px = tx * TILE + (wv & 1) * 8 + (lane & 7);
+    const int py = ty * TILE + (wv >> 1) * 8 + (lane >> 3);
+    const bool inside = px < W && py < H;
+    const float pixfx = (float)px, pixfy = (float)py;
+    const uint32_t start = td.y, n = td.z - td.y;
+    const size_t pix_id = (size_t)W * py + px;
+    float T = inside ? s.final_T[pix_id] : 0.f;
+    const uint32_t last_contributor = inside ? s.n_contrib[pix_id] : 0u;
+    const uint32_t qmax = min(tile_deepest(last_contributor, wmax, wv, lane), n);
+    if (qmax == 0) return;                                  // (feat_rows is zero-filled in front of the launches: rows behind qmax keep 0)
+    if (threadIdx.x == 0) {
+        sA[RNULL] = make_float4(0.f, 0.f, 0.f, 0.f); sB[RNULL] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int q = 0; q < NC / 4; q++) sF[q][RNULL] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float g[NC], acc[NC], last_f[NC], last_alpha = 0.f;     // upstream, accum_rec and the entry behind it, per channel
+    {
+        const size_t N = (size_t)W * H;
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            g[c] = (inside && c < nc) ? dL_dmap[(size_t)(c0 + c) * N + pix_id] : 0.f;
+            acc[c] = 0.f; last_f[c] = 0.f;
+        }
+    }
+    const float ddelx_dx = (float)(0.5 * W), ddely_dy = (float)(0.5 * H);   // backward.cu:460-461
+
+    // slot t of a round = list position qhi - 1 - t: back to front
+    for (uint32_t qhi = qmax; qhi > 0; qhi = qhi > FCHUNK ? qhi - FCHUNK : 0) {
+        const uint32_t cnt = min((uint32_t)FCHUNK, qhi);
+        __syncthreads();                                    // the previous round's flush has read wacc / sSlot
+        uint32_t qm = 0;
+        if (threadIdx.x < cnt) {
+            const uint32_t pos = start + qhi - 1 - threadIdx.x;
+            sA[threadIdx.x] = b.recA[pos]; sB[threadIdx.x] = b.recB[pos];
+            float4 f[NC / 4];
+            load_feature_row<NC>(features, min((uint32_t)b.keys[pos], P - 1u), C, c0, nc, f);
+#pragma unroll
+            for (int q = 0; q < NC / 4; q++) sF[q][threadIdx.x] = f[q];
+            sSlot[threadIdx.x] = b.slot[pos];
+            qm = block_to_quadrant_mask(__float_as_uint(b.recC[pos].y));
+        }
+        build_quad_lists(L, qm, wv, lane);
+        if (lane < FCHUNK / 64) touched[wv][lane] = 0ull;
+        __syncthreads();
+
+#pragma unroll 1
+        for (int sw = 0; sw < FCHUNK / 64; sw++) {          // (the staging waves behind FCHUNK / 64 staged nothing: their lists are empty)
+            const uint32_t nl = __builtin_amdgcn_readfirstlane(L.cnt[wv][sw]);
+            unsigned long long tmask = 0;
+#pragma unroll 1
+            for (uint32_t k = 0; k < nl; k += RUNROLL) {
+                const uint2 pk = *reinterpret_cast<const uint2*>(&L.idx[wv][sw][k]);
+                const uint32_t j[RUNROLL] = {pk.x & 0xffffu, pk.x >> 16, pk.y & 0xffffu, pk.y >> 16};
+                float4 a[RUNROLL], bb[RUNROLL];
+                float dx[RUNROLL], dy[RUNROLL], G[RUNROLL], alpha[RUNROLL];
+                bool valid[RUNROLL];
+#pragma unroll
+                for (int u = 0; u < RUNROLL; u++) { a[u] = sA[j[u]]; bb[u] = sB[j[u]]; }
+                bool any = false;
+#pragma unroll
+                for (int u = 0; u < RUNROLL; u++) {
+                    dx[u] = a[u].x - pixfx; dy[u] = a[u].y - pixfy;
+                    bool cut;
+                    alpha[u] = depth_pair_alpha(a[u], bb[u], dx[u], dy[u], G[u], cut);
+                    valid[u] = (qhi - 1 - j[u] < last_contributor) && (j[u] < cnt) && !cut;
+                    any = any || valid[u];
+                }
+                if (__builtin_amdgcn_ballot_w64(any) == 0) continue;
+                float v[36], vf[36];                        // geometry and channel sums of the 4 entries
+#pragma unroll
+                for (int i = 0; i < 36; i++) { v[i] = 0.f; vf[i] = 0.f; }
+#pragma unroll
+                for (int u = 0; u < RUNROLL; u++) {
+                    if (valid[u]) {
+                        const float om = 1.f - alpha[u];
+                        T = tgs_div(T, om);
+                        const float w = alpha[u] * T;
+                        float fu[NC];
+#pragma unroll
+                        for (int q = 0; q < NC / 4; q++) {
+                            const float4 f = sF[q][j[u]];
+                            fu[4 * q] = f.x; fu[4 * q + 1] = f.y; fu[4 * q + 2] = f.z; fu[4 * q + 3] = f.w;
+                        }
+                        float sum = 0.f;
+#pragma unroll
+                        for (int c = 0; c < NC; c++) {
+                            acc[c] = last_alpha * last_f[c] + (1.f - last_alpha) * acc[c];
+                            last_f[c] = fu[c];
+                            sum += (fu[c] - acc[c]) * g[c];
+                            vf[u * FSTRIDE + c] = g[c] * w;
+                        }
+                        last_alpha = alpha[u];
+                        const float dL_dalpha = sum * T;
+                        const float dL_dG = bb[u].y * dL_dalpha;
+                        const float gdx = G[u] * dx[u], gdy = G[u] * dy[u];
+                        const float dG_ddelx = -gdx * a[u].z - gdy * a[u].w;
+                        const float dG_ddely = -gdy * bb[u].x - gdx * a[u].w;
+                        v[u * FSTRIDE + 0] = dL_dG * dG_ddelx * ddelx_dx;
+                        v[u * FSTRIDE + 1] = dL_dG * dG_ddely * ddely_dy;
+                        v[u * FSTRIDE + 2] = -0.5f * gdx * dx[u] * dL_dG;
+                        v[u * FSTRIDE + 3] = -0.5f * gdx * dy[u] * dL_dG;
+                        v[u * FSTRIDE + 4] = -0.5f * gdy * dy[u] * dL_dG;
+                        v[u * FSTRIDE + 5] = G[u] * dL_dalpha;
+                    }
+                }
+                float r[FSTRIDE], rf[FSTRIDE];
+                wave_reduce36(v, r);                        // row e of r[k]: total of entry e, component k
+                wave_reduce36(vf, rf);
+                const int row = lane >> 4;
+                const uint32_t je = row == 0 ? j[0] : row == 1 ? j[1] : row == 2 ? j[2] : j[3];
+                const uint32_t jr = min(je, (uint32_t)FCHUNK);   // (null slots go to the spare column)
+                if ((lane & 15) == 0) {
+#pragma unroll
+                    for (int c = 0; c < FGEO; c++) wacc[wv][c][jr] = r[c];
+#pragma unroll
+                    for (int c = 0; c < NC; c++) wacc[wv][FGEO + c][jr] = rf[c];
+                }
+#pragma unroll
+                for (int u = 0; u < RUNROLL; u++) if (j[u] < FCHUNK) tmask |= 1ull << (j[u] & 63);
+            }
+            if (lane == 0 && tmask) touched[wv][sw] = tmask;
+        }
+        __syncthreads();
+        // flush: thread j adds the (up to) 4 wave partials of entry j in wave order, then its slab row <- row + sums
+        if (threadIdx.x < cnt) {
+            const uint32_t j = threadIdx.x;
+            float r[FACC];
+            double rc[3] = {0.0, 0.0, 0.0};
+            bool some = false;
+#pragma unroll
+            for (int k = 0; k < FACC; k++) r[k] = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                if ((touched[w][j >> 6] >> (j & 63)) & 1ull) {
+                    some = true;
+#pragma unroll
+                    for (int k = 0; k < FACC; k++) r[k] += wacc[w][k][j];
+#pragma unroll
+                    for (int k = 0; k < 3; k++) rc[k] += (double)wacc[w][2 + k][j];
+                }
+            }
+            if (some) {
+                const uint32_t slot = sSlot[j];
+                float4* row = b.slab + (size_t)slot * SLAB_ROW;
+                float4 r0 = row[0], r1 = row[1], r2 = row[2];
+                // the conic shares lie in the row as hi + lo: add in double, split again
+                const double c5 = ((double)r1.y + (double)r2.y) + rc[0], c6 = ((double)r1.z + (double)r2.z) + rc[1], c7 = ((double)r1.w + (double)r2.w) + rc[2];
+                r0.w += r[0];
+                r1.x += r[1];
+                r1.y = (float)c5; r1.z = (float)c6; r1.w = (float)c7;
+                r2.x += r[5];
+                r2.y = (float)(c5 - (double)r1.y); r2.z = (float)(c6 - (double)r1.z); r2.w = (float)(c7 - (double)r1.w);
+                row[0] = r0; row[1] = r1; row[2] = r2;
+                float* fr = feat_rows + (size_t)slot * C + c0;
+#pragma unroll
+                for (int c = 0; c < NC; c++) if (c < nc) fr[c] = r[FGEO + c];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_feat_bwd_gauss: one lane per Gaussian: dL_dfeatures[i, c] = (or +=, with `accumulate`) the sum of the Gaussian's scratch rows in row order.
+// A culled Gaussian and every Gaussian of a rejected frame get a zero row.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PRE_BLOCK) void k_feat_bwd_gauss(int P, int C, const Meta* __restrict__ meta, const int* __restrict__ radii, const GeomState g,
+                                                              const float* __restrict__ feat_rows, float* __restrict__ dL_dfeatures, int accumulate)
+{
+    const int idx = blockIdx.x * PRE_BLOCK + threadIdx.x;
+    if (idx >= P) return;
+    const bool live = !(__builtin_nontemporal_load(&meta->error) & META_ERR_CAPACITY) && radii[idx] > 0;
+    if (!live && accumulate) return;
+    const uint32_t tiles = live ? g.tiles_touched[idx] : 0u, off = live ? g.offsets[idx] : 0u;
+    float* o = dL_dfeatures + (size_t)idx * C;
+    for (int c = 0; c < C; c++) {
+        float sum = 0.f;
+        for (uint32_t k = 0; k < tiles; k++) sum += feat_rows[(size_t)(off + k) * C + c];
+        o[c] = accumulate ? o[c] + sum : sum;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host launchers: one launch per group of FGROUP channels, the narrow kernel for a group of 1 .. 4
+// ---------------------------------------------------------------------------------------------
+// out[C * N] <- 0, then the tiles with instances (at most T workgroups have work)
+void launch_feat_fwd(hipStream_t st, const ImgState& s, const BinState& b, int W, int H, uint32_t gx, uint32_t T, int P, int C, const float* features, float* out)
+{
+    (void)hipMemsetAsync(out, 0, (size_t)C * W * H * sizeof(float), st);
+    if (T == 0) return;
+    for (int c0 = 0; c0 < C; c0 += FGROUP) {
+        const int nc = C - c0 < FGROUP ? C - c0 : FGROUP;
+        if (nc <= 4) hipLaunchKernelGGL(k_feat_fwd<4>, dim3(T), dim3(256), 0, st, s, b, W, H, gx, (uint32_t)P, C, c0, nc, features, out);
+        else hipLaunchKernelGGL(k_feat_fwd<8>, dim3(T), dim3(256), 0, st, s, b, W, H, gx, (uint32_t)P, C, c0, nc, features, out);
+    }
+}
+// tiles: leading entries of tile_order that can hold instances (launch_render_bwd's).  feat_rows[R * C] <- 0 first: rows the kernels do not visit read as 0.
+void launch_feat_bwd(hipStream_t st, const ImgState& s, const BinState& b, int W, int H, uint32_t gx, uint32_t tiles, size_t R, int P, int C, const float* features,
+                     const float* dL_dmap, float* feat_rows)
+{
+    (void)hipMemsetAsync(feat_rows, 0, R * C * sizeof(float), st);
+    if (tiles == 0) return;
+    for (int c0 = 0; c0 < C; c0 += FGROUP) {
+        const int nc = C - c0 < FGROUP ? C - c0 : FGROUP;
+        if (nc <= 4) hipLaunchKernelGGL(k_feat_bwd<4>, dim3(tiles), dim3(256), 0, st, s, b, W, H, gx, (uint32_t)P, C, c0, nc, features, dL_dmap, feat_rows);
+        else hipLaunchKernelGGL(k_feat_bwd<8>, dim3(tiles), dim3(256), 0, st, s, b, W, H, gx, (uint32_t)P, C, c0, nc, features, dL_dmap, feat_rows);
+    }
+}
+void launch_feat_bwd_gauss(hipStream_t st, int P, int C, const Meta* meta, const int* radii, const GeomState& g, const float* feat_rows, float* dL_dfeatures, int accumulate)
+{
+    hipLaunchKernelGGL(k_feat_bwd_gauss, dim3((unsigned)n_blocks((size_t)P)), dim3(PRE_BLOCK), 0, st, P, C, meta, radii, g, feat_rows, dL_dfeatures, accumulate);
+}
+
+}  // namespace tgs

@@ -123,8 +123,12 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
                                        const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, bool debug,
                                        bool with_conic, int64_t tile_bound, c10::optional<bool> deterministic, int64_t mid_bound, c10::optional<bool> light_tiles,
                                        bool need_colors, bool need_cov3D, const c10::optional<torch::Tensor>& grad_out_alpha,
-                                       const c10::optional<torch::Tensor>& grad_out_depth)
+                                       const c10::optional<torch::Tensor>& grad_out_depth, const c10::optional<torch::Tensor>& grad_out_features,
+                                       const c10::optional<torch::Tensor>& features)
 {
+    // grad_out_features (extension keyword): upstream gradient of the feature map (features_from_state), [C,H,W], with features [P,C]; None launches no
+    // feature kernel and returns today's tuple, a tensor goes to tgs_backward_features_opt (with grad_out_alpha / grad_out_depth or without) together with
+    // a scratch of R * C floats allocated here, and dL_dfeatures[P,C] is appended to the tuple.
     // grad_out_depth (extension keyword): upstream gradient of the expected depth (depth_from_state), [1,H,W] or [H,W]; None launches no depth kernel,
     // a tensor goes to tgs_backward_depth_opt (with grad_out_alpha or without) together with a scratch of R floats allocated here.
     // grad_out_alpha (extension keyword): upstream gradient of the accumulated alpha (alpha_from_state), [1,H,W] or [H,W]; None takes today's call
@@ -144,6 +148,17 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
                   dL_dsh = torch::empty({P, M, 3}, f32);
     // the reference leaves these at zero on the cov3D_precomp path
     torch::Tensor dL_dscales = has_sr ? torch::empty({P, 3}, f32) : torch::zeros({P, 3}, f32), dL_drotations = has_sr ? torch::empty({P, 4}, f32) : torch::zeros({P, 4}, f32);
+    const bool with_feat = grad_out_features.has_value() && grad_out_features->defined();
+    int C = 0;
+    torch::Tensor dL_dfeatures;
+    if (with_feat) {
+        if (!features.has_value() || !features->defined() || features->dim() != 2 || features->size(0) != P)
+            throw std::runtime_error("grad_out_features needs features of shape [P,C]");
+        C = (int)features->size(1);
+        if (C < 1 || C > TGS_FEATURE_MAX_CHANNELS) throw std::runtime_error("grad_out_features: features must have 1 .. 16 channels");
+        if (grad_out_features->numel() != (int64_t)C * H * W) throw std::runtime_error("grad_out_features must have C*H*W elements ([C,H,W])");
+        dL_dfeatures = torch::empty({P, C}, f32);
+    }
     if (P != 0) {
         const Arg bg(background, dev, "background"), means(means3D, dev, "means3D"), col(colors, dev, "colors"), cov(cov3D_precomp, dev, "cov3D_precomp"),
             view(viewmatrix, dev, "viewmatrix"), proj(projmatrix, dev, "projmatrix"), shs(sh, dev, "sh"), cam(campos, dev, "campos"),
@@ -155,13 +170,24 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
         if (with_depth && grad_out_depth->numel() != (int64_t)H * W) throw std::runtime_error("grad_out_depth must have H*W elements ([1,H,W])");
         const Arg dD(with_depth ? *grad_out_depth : torch::Tensor(), dev, "grad_out_depth");
         const torch::Tensor dz_scratch = with_depth ? torch::empty({R > 0 ? R : 1}, dL_dmeans3D.options()) : torch::Tensor();
+        const Arg dF(with_feat ? *grad_out_features : torch::Tensor(), dev, "grad_out_features"), feat(with_feat ? *features : torch::Tensor(), dev, "features");
+        const torch::Tensor feat_scratch = with_feat ? torch::empty({R > 0 ? R * C : 1}, dL_dmeans3D.options()) : torch::Tensor();
         const torch::Tensor radii_c = radii.contiguous();
         void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         const tgs_options_t opt = make_options(tile_bound, c10::nullopt, deterministic, 0, mid_bound, light_tiles);
         int r;
         {
             py::gil_scoped_release nogil;
-            if (with_depth)
+            if (with_feat)
+                r = tgs_backward_features_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p,
+                                              tan_fovx, tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p,
+                                              with_alpha ? dA.p : nullptr, with_depth ? dD.p : nullptr, with_depth ? dz_scratch.data_ptr<float>() : nullptr,
+                                              C, feat.p, dF.p, feat_scratch.data_ptr<float>(), dL_dfeatures.data_ptr<float>(),
+                                              dL_dmeans2D.data_ptr<float>(), with_conic ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
+                                              want_col ? dL_dcolors.data_ptr<float>() : nullptr, dL_dmeans3D.data_ptr<float>(), want_cov ? dL_dcov3D.data_ptr<float>() : nullptr,
+                                              M ? dL_dsh.data_ptr<float>() : nullptr,
+                                              has_sr ? dL_dscales.data_ptr<float>() : nullptr, has_sr ? dL_drotations.data_ptr<float>() : nullptr, debug);
+            else if (with_depth)
                 r = tgs_backward_depth_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p,
                                            tan_fovx, tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p,
                                            with_alpha ? dA.p : nullptr, dD.p, dz_scratch.data_ptr<float>(),
@@ -186,6 +212,8 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
         }
         if (r < 0) raise_last(r);
     }
+    if (with_feat && with_conic) return py::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dconic, dL_dfeatures);
+    if (with_feat) return py::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dfeatures);
     if (with_conic) return py::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dconic);
     return py::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations);
 }
@@ -232,6 +260,34 @@ torch::Tensor depth_from_state(const torch::Tensor& geomBuffer, const torch::Ten
     return depth;
 }
 
+// The feature map of a finished forward (tgs_features): [C,H,W] = sum_i T_i alpha_i features[i, :] over the pairs the colour frame blended.
+// An empty model or a frame without instances (P == 0 / R == 0) has the map 0 everywhere and launches nothing.
+torch::Tensor features_from_state(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const torch::Tensor& features,
+                                  int P, int H, int W, int64_t R)
+{
+    if (!features.is_cuda()) throw std::runtime_error("features_from_state: features must be on a HIP device");
+    if (P < 0 || H <= 0 || W <= 0 || R < 0) throw std::runtime_error("features_from_state: bad sizes");
+    if (features.dim() != 2 || features.size(0) != P) throw std::runtime_error("features_from_state: features must have shape [P,C]");
+    const int C = (int)features.size(1);
+    if (C < 1 || C > TGS_FEATURE_MAX_CHANNELS) throw std::runtime_error("features_from_state: features must have 1 .. 16 channels");
+    const c10::Device dev = features.device();
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
+    if (P == 0 || R == 0) return torch::zeros({C, H, W}, f32);
+    size_t sizes[3];
+    tgs_state_sizes(P, W, H, 0, 0, R, sizes);
+    const auto bytes = [](const torch::Tensor& t) { return (size_t)t.numel() * t.element_size(); };
+    if (!geomBuffer.is_cuda() || !binningBuffer.is_cuda() || !imageBuffer.is_cuda() || bytes(geomBuffer) < sizes[TGS_BUF_GEOM] ||
+        bytes(binningBuffer) < sizes[TGS_BUF_BINNING] || bytes(imageBuffer) < sizes[TGS_BUF_IMAGE])
+        throw std::runtime_error("features_from_state: state buffers smaller than a frame of these sizes");
+    const Arg feat(features, dev, "features");
+    torch::Tensor out = torch::empty({C, H, W}, f32);
+    void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+    const int r = tgs_features(stream, P, C, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), feat.p, out.data_ptr<float>());
+    if (r < 0) raise_last(r);
+    return out;
+}
+
 // markVisible (rasterize_points.cu:198-217)
 torch::Tensor mark_visible(const torch::Tensor& means3D, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix)
 {
@@ -263,7 +319,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("dL_dout_color"), py::arg("sh"), py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"),
           py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"), py::arg("_with_conic") = false, py::arg("tile_bound") = 0,
           py::arg("deterministic") = py::none(), py::arg("mid_bound") = 0, py::arg("light_tiles") = py::none(), py::arg("need_colors") = true,
-          py::arg("need_cov3D") = true, py::arg("grad_out_alpha") = py::none(), py::arg("grad_out_depth") = py::none());
+          py::arg("need_cov3D") = true, py::arg("grad_out_alpha") = py::none(), py::arg("grad_out_depth") = py::none(),
+          py::arg("grad_out_features") = py::none(), py::arg("features") = py::none());
+    m.def("features_from_state", &features_from_state, py::arg("geomBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("features"), py::arg("P"),
+          py::arg("H"), py::arg("W"), py::arg("R"));
     m.def("depth_from_state", &depth_from_state, py::arg("geomBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("P"), py::arg("H"), py::arg("W"), py::arg("R"));
     m.def("alpha_from_state", &alpha_from_state, py::arg("imageBuffer"), py::arg("H"), py::arg("W"));
     m.def("mark_visible", &mark_visible);

@@ -474,10 +474,14 @@ def state_field(name: str, P: int, width: int, height: int, R: int, has_sh: bool
 
 
 # The reference's three exports (ext.cpp:15-19): the compiled module's functions, positional signatures of rasterize_points.h:18-67
-# (+ the keyword-only extensions r_capacity / r_guess / _with_conic / grad_out_alpha / grad_out_depth documented in csrc/tgs_torch_ext.cpp).
+# (+ the keyword-only extensions r_capacity / r_guess / _with_conic / grad_out_alpha / grad_out_depth / grad_out_features + features documented in csrc/tgs_torch_ext.cpp).
 rasterize_gaussians = _ext.rasterize_gaussians
 rasterize_gaussians_backward = _ext.rasterize_gaussians_backward
 mark_visible = _ext.mark_visible
 alpha_from_state = _ext.alpha_from_state       # (imageBuffer, H, W) -> the frame's accumulated alpha [1,H,W] = 1 - final_T (tgs_alpha; an extension)
 # (geomBuffer, binningBuffer, imageBuffer, P, H, W, R) -> the frame's expected depth [1,H,W] = sum_i T_i alpha_i z_i (tgs_depth; an extension)
 depth_from_state = _ext.depth_from_state
+# (geomBuffer, binningBuffer, imageBuffer, features[P,C], P, H, W, R) -> the frame's feature map [C,H,W] = sum_i T_i alpha_i features[i, :]
+# (tgs_features; an extension, 1 <= C <= 16)
+features_from_state = _ext.features_from_state
+FEATURE_MAX_CHANNELS = 16      # TGS_FEATURE_MAX_CHANNELS

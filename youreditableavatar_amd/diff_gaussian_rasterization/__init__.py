@@ -183,8 +183,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         return _RasterizeGaussians.native_backward(ctx, grad_out_color, None)
 
     @staticmethod
-    def native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth=None):
-        """grad_out_alpha / grad_out_depth None: today's native call, today's kernels; a tensor: the extension keyword of the same call"""
+    def native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth=None, grad_out_features=None, features=None):
+        """grad_out_alpha / grad_out_depth / grad_out_features None: today's native call, today's kernels; a tensor: the extension keyword of
+        the same call.  With grad_out_features (and the forward's features) the gradient of the features follows the nine of today."""
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:                           # the image did not take part in the loss (gradients not materialised, see forward)
@@ -203,25 +204,30 @@ class _RasterizeGaussians(torch.autograd.Function):
         extra = {} if grad_out_alpha is None else {"grad_out_alpha": grad_out_alpha}
         if grad_out_depth is not None:
             extra["grad_out_depth"] = grad_out_depth
-        (g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rots) = _call_native(
+        if grad_out_features is not None:
+            extra["grad_out_features"], extra["features"] = grad_out_features, features
+        (g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rots, *g_feat) = _call_native(
             lambda *a: _C.rasterize_gaussians_backward(*a, tile_bound=bound, mid_bound=mid, light_tiles=ctx.light, need_colors=need_col, need_cov3D=need_cov, **extra),
             args, rs.debug, "snapshot_bw.dump", "backward")
         # forward-argument order (__init__.py:143-153)
+        tail = (g_feat[0],) if grad_out_features is not None else ()
         return (g_means3D, g_means2D, g_sh if sh.numel() != 0 else None, g_colors if need_col else None, g_opac, g_scales if scales.numel() != 0 else None,
-                g_rots if rotations.numel() != 0 else None, g_cov3D if need_cov else None, None)
+                g_rots if rotations.numel() != 0 else None, g_cov3D if need_cov else None, None) + tail
 
 
 class _RasterizeGaussiansExt(torch.autograd.Function):
     """_RasterizeGaussians with further differentiable outputs behind (color, radii), each on request (extensions: the reference's
     rasterizer has neither):
       alpha [1,H,W] = 1 - final_T of the frame, so that ``color == C_premultiplied + (1 - alpha) * bg``;
-      depth [1,H,W] = sum_i T_i alpha_i z_i over the pairs the colour frame blended (expected depth, not normalised; z = view-space z).
+      depth [1,H,W] = sum_i T_i alpha_i z_i over the pairs the colour frame blended (expected depth, not normalised; z = view-space z);
+      feature_map [C,H,W] = sum_i T_i alpha_i features[i, :] over the same pairs, for per-Gaussian features [P,C] (1 <= C <= 16; signed, not
+      clamped, not normalised, background 0) -- a real autograd input: its gradient is None when it does not need one.
     Same native forward and backward; the upstream gradients of the extra outputs travel with the colour's in ONE backward call.
-    Gradients stay unmaterialised: an absent colour gradient becomes zeros as in _RasterizeGaussians, an absent alpha / depth gradient
-    launches exactly the kernels of a frame without that output."""
+    Gradients stay unmaterialised: an absent colour gradient becomes zeros as in _RasterizeGaussians, an absent alpha / depth / feature-map
+    gradient launches exactly the kernels of a frame without that output."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, want_alpha, want_depth):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, want_alpha, want_depth, features=None):
         rs = raster_settings
         color, radii, img, geom, binning = _RasterizeGaussians.native_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs,
                                                                               with_state=True)
@@ -238,6 +244,13 @@ class _RasterizeGaussiansExt(torch.autograd.Function):
                 out.append(torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device))
             else:
                 out.append(_C.depth_from_state(geom, binning, img, P, H, W, int(ctx.num_rendered)))
+        ctx.want_features = features is not None
+        if features is not None:
+            ctx.features = features                             # (an input: held as save_for_backward holds the others, without a second call of it)
+            if P == 0:
+                out.append(torch.zeros((int(features.shape[1]), H, W), dtype=torch.float32, device=means3D.device))
+            else:
+                out.append(_C.features_from_state(geom, binning, img, features, P, H, W, int(ctx.num_rendered)))
         return tuple(out)
 
     @staticmethod
@@ -245,19 +258,35 @@ class _RasterizeGaussiansExt(torch.autograd.Function):
         extra = list(extra)
         grad_out_alpha = extra.pop(0) if ctx.want_alpha else None
         grad_out_depth = extra.pop(0) if ctx.want_depth else None
-        return _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth) + (None, None)
+        grad_out_features = extra.pop(0) if ctx.want_features else None
+        if grad_out_features is None:                       # no feature map, or one the loss did not use: no feature kernel runs
+            return _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth) + (None, None, None)
+        g = _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth, grad_out_features, ctx.features)
+        return g[:-1] + (None, None, g[-1] if ctx.needs_input_grad[11] else None)
 
 
 _RasterizeGaussiansAlpha = _RasterizeGaussiansExt           # (the name of the node when it had one extra output)
 
 
+def _check_features(features, means3D):
+    """features of the extended node: float32 [P, C] on the device of the means, 1 <= C <= 16; taken contiguous as the other inputs are"""
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] != means3D.shape[0]:
+        raise ValueError("features must be a tensor of shape [P, C], one row per Gaussian")
+    if not 1 <= features.shape[1] <= _C.FEATURE_MAX_CHANNELS:
+        raise ValueError(f"features must have 1 .. {_C.FEATURE_MAX_CHANNELS} channels, got {features.shape[1]}")
+    if features.dtype != torch.float32 or features.device != means3D.device:
+        raise ValueError("features must be float32 and on the device of means3D")
+    return features.contiguous()
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, return_alpha=False,
-                        return_depth=False):
-    """``return_alpha=True`` / ``return_depth=True`` (extensions): -> (color[3,H,W], radii[P]), then alpha[1,H,W] if asked, then depth[1,H,W]
-    if asked -- the differentiable accumulated alpha and expected depth of the same compositing."""
-    if return_alpha or return_depth:
+                        return_depth=False, features=None):
+    """``return_alpha=True`` / ``return_depth=True`` / ``features=F[P,C]`` (extensions): -> (color[3,H,W], radii[P]), then alpha[1,H,W] if
+    asked, then depth[1,H,W] if asked, then feature_map[C,H,W] if ``features`` is given -- the differentiable accumulated alpha, expected
+    depth and composited per-Gaussian features (sum_i T_i alpha_i F[i, :]; float32, 1 <= C <= 16) of the same compositing."""
+    if return_alpha or return_depth or features is not None:
         return _RasterizeGaussiansExt.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                                            bool(return_alpha), bool(return_depth))
+                                            bool(return_alpha), bool(return_depth), None if features is None else _check_features(features, means3D))
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
 
 
@@ -272,7 +301,8 @@ class GaussianRasterizer(nn.Module):
             rs = self.raster_settings
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
-    def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, return_alpha=False, return_depth=False):
+    def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, return_alpha=False, return_depth=False,
+                features=None):
         rs = self.raster_settings
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -289,4 +319,4 @@ class GaussianRasterizer(nn.Module):
             absent if scales is None else scales,
             absent if rotations is None else rotations,
             absent if cov3D_precomp is None else cov3D_precomp,
-            rs, return_alpha=return_alpha, return_depth=return_depth)
+            rs, return_alpha=return_alpha, return_depth=return_depth, features=features)
