@@ -253,8 +253,8 @@ int tgs_backward_render_alpha_opt(const tgs_options_t* opt, void* stream, int P,
  *                     dL/dalpha_i = dL_ddepth * T_i * (z_i - accum_rec_i), the min(0.99, .) clamp straight-through as everywhere; from there
  *                     to dL_dopacity, dL_dconic, dL_dmean2D and on through the unchanged per-Gaussian pass;
  *   dL_dcolor / dL_dsh get nothing from it.
- * Not part of the whole-batch path (tgs_*_views, tgs_backward_batch: tgs_view_t is frozen); no median / mode depth; normals and
- * feature channels are tgs_features below.
+ * Part of the whole-batch path since tgs_view_extras_t (below, behind tgs_backward_batch_range_planes): alpha and depth of every view of a
+ * batch and their gradients, beside the frozen tgs_view_t.  No median / mode depth; normals and feature channels are tgs_features below.
  *
  * tgs_depth: out_depth[H*W] of a finished forward (any of the forward entry points; P, width, height as given to it, R as it returned or was
  * given), enqueued on `stream`: a pass of its own over the frame's state, the render kernels are not involved.  P == 0 or R == 0: nothing
@@ -294,7 +294,8 @@ int tgs_backward_depth_opt(const tgs_options_t* opt, int accumulate, void* strea
  *                      colour's share (added to it) and on through the unchanged per-Gaussian pass;
  *   dL_dcolor / dL_dsh get nothing from it.
  * Channels travel in groups of 8 per launch (C = 9 .. 16: two launches each way).  No float atomics: two runs give the same bits.
- * Not part of the whole-batch path (tgs_*_views, tgs_backward_batch: tgs_view_t is frozen).
+ * Feature channels are NOT part of the whole-batch path (tgs_*_views, tgs_backward_batch; alpha and depth are: tgs_view_extras_t) -- the
+ * descriptor there is sized by its struct_size field so that they can be appended.
  *
  * tgs_features: out[C*H*W] of a finished forward (P, width, height as given to it, R as it returned or was given), enqueued on `stream`: a
  * pass of its own over the frame's state, the render kernels are not involved.  P == 0 or R == 0: nothing was blended, nothing is launched
@@ -535,6 +536,48 @@ int tgs_backward_batch_range_planes(void* stream, int P, int D, int M, int n_vie
                                     const float* rotations, const float* cov3D_precomp,
                                     float* dL_dopacity, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                                     float* dL_dscale, float* dL_drot, int accumulate, int first, int count, int64_t dsh_plane_stride);
+
+/* ---- alpha and depth in the whole-batch path ----
+ * tgs_view_t is frozen (its size is part of ABI 3), so what a view needs for the two extra outputs travels in a SECOND array beside it: same
+ * length, same index.  struct_size is the sizeof of the caller's build and the stride of the caller's array; fields beyond it read as NULL,
+ * and every element of one array carries the same value.  Any pointer may be NULL: that output / gradient then takes no part and no kernel
+ * is launched for it.  extras == NULL: no view has any. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(tgs_view_extras_t) of the caller's build: fields beyond it read as NULL */
+    float* out_alpha;         /* [H*W] or NULL */
+    float* out_depth;         /* [H*W] or NULL */
+    const float* dL_dalpha;   /* [H*W] or NULL */
+    const float* dL_ddepth;   /* [H*W] or NULL */
+    float* dz_scratch;        /* views[k].R floats of the caller's (contents on entry do not matter), required with dL_ddepth */
+} tgs_view_extras_t;
+size_t tgs_sizeof_view_extras(void);
+
+/* tgs_alpha into extras[k].out_alpha and / or tgs_depth into extras[k].out_depth for every view of a finished tgs_forward_views call, from the
+ * view's state (views[k]: width, height, R, the three buffers).  View k is enqueued on streams[k % n_streams].
+ * WHICH streams: the maps read final_T / n_contrib, which k_render_fwd writes, so pass the streams view k's k_render_fwd ran on and the pass is
+ * ordered behind it without an event.  That is, for tgs_forward_views[_opt](streams, n_streams, ...):
+ *   - no render streams set (the default):           the same streams, in the same order -- view k composites on streams[k % n_streams];
+ *   - tgs_set_render_streams(render, n_render) set:  the render streams -- view k composites on render[k % n_render], behind an event on
+ *                                                    its binning stream streams[k % n_streams].
+ * A frame the sync-free forward rejected, a frame without instances (R == 0) and an empty model (P == 0) give zeros. */
+int tgs_outputs_views(void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras);
+
+/* tgs_backward_render_views_opt with extras[k].dL_dalpha entering view k's per-pixel backward (tgs_backward_render_alpha_opt) and, with
+ * extras[k].dL_ddepth, the depth's per-pixel backward behind it on the same stream: dz_scratch is zero-filled, then the alpha-path share is
+ * ADDED into the slab rows the colour's backward has just written (the rows tgs_backward_batch reads) and the z-path share is left in
+ * dz_scratch for tgs_backward_batch_depth_range.  extras == NULL, or both gradient pointers NULL in every view: exactly the launches of
+ * tgs_backward_render_views_opt. */
+int tgs_backward_render_views_extras_opt(const tgs_options_t* opt, void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views,
+                                         const tgs_view_extras_t* extras);
+
+/* The z-path of the depth gradient for all views in one pass: for Gaussians [first, first + count) (the rule of tgs_backward_batch_range)
+ *     dL_dmean3D[p] += sum over the views k with dL_ddepth, ascending, of (sum of p's dz rows of view k, in row order) * (m_k[2], m_k[6], m_k[10]).
+ * Call it on the stream and behind the tgs_backward_batch_range[_planes] launch of the same range, which has stored or accumulated
+ * dL_dmean3D.  Views without dL_ddepth, rejected frames and Gaussians culled in a view contribute nothing; with no view that has dL_ddepth
+ * nothing is launched.  One launch per 8 such views, one read-modify-write of dL_dmean3D per Gaussian and launch; no float atomics, a fixed
+ * order: two runs give the same bits. */
+int tgs_backward_batch_depth_range(void* stream, int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras, float* dL_dmean3D,
+                                   int first, int count);
 
 /* ---- "next" row 2: the trainers' photometric loss ----
  * loss = (1 - dssim_factor) * l1_loss(img, gt) + dssim_factor * (1 - ssim(img, gt)), window 11, sigma 1.5, zero padding

@@ -30,6 +30,7 @@ void launch_selftest_reduce36(hipStream_t, const float* in, float* out);
 void launch_depth_fwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t T, float* out_depth);
 void launch_depth_bwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t tiles, size_t R, const float* dL_ddepth, float* dz_rows);
 void launch_depth_bwd_gauss(hipStream_t, int P, const Meta* meta, const int* radii, const GeomState&, const float* view, const float* dz_rows, float* dL_dmean3D);
+void launch_depth_bwd_gauss_views(hipStream_t, int first, int count, const DepthViews&, float* dL_dmean3D);
 // tgs_feature.hip
 void launch_feat_fwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t T, int P, int C, const float* features, float* out);
 void launch_feat_bwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t tiles, size_t R, int P, int C, const float* features,
@@ -567,14 +568,42 @@ static int backward_impl(bool strict, const Opts& opt, int accumulate, hipStream
 }
 
 // tgs_backward_render[_views]: the view's own fields (tgs_backward_render packs its arguments into one)
-static int backward_render_impl(const Opts& opt, hipStream_t st, int P, const tgs_view_t& w, const float* dL_dalpha = nullptr)
+static int backward_render_impl(const Opts& opt, hipStream_t st, int P, const tgs_view_t& w, const float* dL_dalpha = nullptr, const float* dL_ddepth = nullptr,
+                                float* dz_scratch = nullptr)
 {
     g_err[0] = 0;
     if (P == 0) return TGS_OK;
     if (P < 0) return fail(TGS_ERR_INVALID, "bad sizes");
     if (int r = check_view(w, 0, VIEW_RENDER_BWD, false)) return r;
+    if (dL_ddepth && !dz_scratch) return fail(TGS_ERR_INVALID, "NULL required pointer");
     const ViewArgs v = view_args(w);
-    return enqueue_render_bwd(opt, st, 0, carve_frame(GeomShape{(size_t)P, false, false}, v, w.R, nullptr, w.binning_buffer, w.img_buffer), v, w.R, w.dL_dpix, dL_dalpha);
+    return enqueue_render_bwd(opt, st, 0, carve_frame(GeomShape{(size_t)P, false, false}, v, w.R, nullptr, w.binning_buffer, w.img_buffer), v, w.R, w.dL_dpix, dL_dalpha,
+                              dL_ddepth, dz_scratch);
+}
+
+// element k of a caller's tgs_view_extras_t array (stride and valid prefix: the array's struct_size); fields beyond the caller's build read as NULL
+static int read_extras(const tgs_view_extras_t* base, int k, tgs_view_extras_t& out)
+{
+    memset(&out, 0, sizeof(out));
+    if (!base) return TGS_OK;
+    const size_t stride = base->struct_size;
+    if (stride < offsetof(tgs_view_extras_t, out_alpha) + sizeof(base->out_alpha))
+        return fail(TGS_ERR_INVALID, "tgs_view_extras_t: struct_size %zu is smaller than the first pointer field", stride);
+    memcpy(&out, (const char*)base + (size_t)k * stride, stride < sizeof(out) ? stride : sizeof(out));
+    if (out.struct_size != stride) return fail(TGS_ERR_INVALID, "view %d: tgs_view_extras_t.struct_size %u differs from the array's %zu", k, out.struct_size, stride);
+    if (out.dL_ddepth && !out.dz_scratch) return fail(TGS_ERR_INVALID, "view %d: dL_ddepth without dz_scratch", k);
+    return TGS_OK;
+}
+// the arguments the three *_views extras entry points share, checked before anything is enqueued
+static int check_extras_call(int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras)
+{
+    g_err[0] = 0;
+    if (P < 0 || n_views < 0) return fail(TGS_ERR_INVALID, "bad sizes P=%d n_views=%d", P, n_views);
+    if (n_views > 0 && !views) return fail(TGS_ERR_INVALID, "NULL required pointer (views)");
+    tgs_view_extras_t x;
+    for (int k = 0; k < n_views && extras; k++)
+        if (int r = read_extras(extras, k, x)) return r;
+    return TGS_OK;
 }
 
 // the shared per-Gaussian stage of a group of views of tgs_forward_views: one launch on the group's first stream
@@ -923,6 +952,87 @@ int tgs_backward_render_views_opt(const tgs_options_t* o, void* const* streams, 
         if (r < 0) return r;
     }
     return TGS_OK;
+}
+
+size_t tgs_sizeof_view_extras(void) { return sizeof(tgs_view_extras_t); }
+
+int tgs_outputs_views(void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras)
+{
+    static const char* fn = "tgs_outputs_views";
+    if (int r = check_extras_call(P, n_views, views, extras)) return named(fn, r);
+    if ((n_views > 0 && !streams) || n_streams <= 0) return named(fn, fail(TGS_ERR_INVALID, "bad arguments (streams, n_streams=%d)", n_streams));
+    if (!extras) return TGS_OK;
+    for (int k = 0; k < n_views; k++) {
+        tgs_view_extras_t x;
+        if (int r = read_extras(extras, k, x)) return named(fn, r);
+        if (!x.out_alpha && !x.out_depth) continue;
+        const tgs_view_t& w = views[k];
+        hipStream_t st = (hipStream_t)streams[k % n_streams];
+        if (w.width <= 0 || w.height <= 0 || w.R < 0) return named(fn, fail(TGS_ERR_INVALID, "view %d: bad sizes", k));
+        const ViewArgs v = view_args(w);
+        if (v.gx() > 65535u || v.gy() > 65535u) return named(fn, fail(TGS_ERR_INVALID, "view %d: image too large", k));
+        const size_t bytes = v.N() * sizeof(float);
+        if (P == 0 || w.R == 0) {                           // nothing was blended (an empty model writes no image state at all)
+            if (x.out_alpha) HIP_TRY(hipMemsetAsync(x.out_alpha, 0, bytes, st));
+            if (x.out_depth) HIP_TRY(hipMemsetAsync(x.out_depth, 0, bytes, st));
+            continue;
+        }
+        if (!w.img_buffer || (x.out_depth && (!w.geom_buffer || !w.binning_buffer))) return named(fn, fail(TGS_ERR_INVALID, "view %d: NULL required pointer", k));
+        const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, w.R, w.geom_buffer, w.binning_buffer, w.img_buffer);
+        if (x.out_alpha) launch_alpha(st, fb.s, v.N(), x.out_alpha);
+        if (x.out_depth) launch_depth_fwd(st, fb.s, fb.b, w.width, w.height, v.gx(), (uint32_t)v.T(), x.out_depth);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(TGS_ERR_HIP, "%s: view %d: %s", fn, k, hipGetErrorString(e));
+    }
+    return TGS_OK;
+}
+
+int tgs_backward_render_views_extras_opt(const tgs_options_t* o, void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views,
+                                         const tgs_view_extras_t* extras)
+{
+    static const char* fn = "tgs_backward_render_views_extras_opt";
+    if (int r = check_extras_call(P, n_views, views, extras)) return named(fn, r);
+    if ((n_views > 0 && !streams) || n_streams <= 0) return named(fn, fail(TGS_ERR_INVALID, "bad arguments (streams, n_streams=%d)", n_streams));
+    const Opts opt0 = resolve_options(o, true);
+    for (int k = 0; k < n_views; k++) {
+        tgs_view_extras_t x;
+        if (int r = read_extras(extras, k, x)) return named(fn, r);
+        const int r = backward_render_impl(view_options(opt0, views[k]), (hipStream_t)streams[k % n_streams], P, views[k], x.dL_dalpha, x.dL_ddepth, x.dz_scratch);
+        if (r < 0) return named(fn, r);
+    }
+    return TGS_OK;
+}
+
+int tgs_backward_batch_depth_range(void* stream, int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras, float* dL_dmean3D, int first, int count)
+{
+    static const char* fn = "tgs_backward_batch_depth_range";
+    hipStream_t st = (hipStream_t)stream;
+    if (int r = check_extras_call(P, n_views, views, extras)) return named(fn, r);
+    if (P == 0 || n_views == 0 || count == 0 || !extras) return TGS_OK;
+    if (first < 0 || count < 0 || first % PRE_BLOCK != 0 || (long long)first + count > P || ((first + count) % PRE_BLOCK != 0 && first + count != P))
+        return fail(TGS_ERR_INVALID, "%s: Gaussian range [%d, %d + %d) must start and end on multiples of %d (or end at P = %d)", fn, first, first, count, PRE_BLOCK, P);
+    DepthViews dv;
+    memset(&dv, 0, sizeof(dv));
+    auto flush = [&]() -> int {
+        if (dv.n == 0) return TGS_OK;
+        const int r = stage(st, TGS_STAGE_PREPROCESS_BWD, "depth_bwd_gauss_views", 0, [&] { launch_depth_bwd_gauss_views(st, first, count, dv, dL_dmean3D); });
+        dv.n = 0;
+        return r;
+    };
+    for (int k = 0; k < n_views; k++) {
+        tgs_view_extras_t x;
+        if (int r = read_extras(extras, k, x)) return named(fn, r);
+        const tgs_view_t& w = views[k];
+        if (!x.dL_ddepth || w.R <= 0) continue;             // (R == 0: the per-pixel backward launched nothing and dz_scratch was not filled)
+        if (!dL_dmean3D || !w.geom_buffer || !w.img_buffer || !w.radii || !w.viewmatrix || w.width <= 0 || w.height <= 0)
+            return fail(TGS_ERR_INVALID, "%s: view %d: bad sizes or NULL required pointer", fn, k);
+        const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, view_args(w), w.R, w.geom_buffer, nullptr, w.img_buffer);
+        DepthView& d = dv.v[dv.n++];
+        d.meta = fb.s.meta; d.radii = w.radii; d.tiles_touched = fb.g.tiles_touched; d.offsets = fb.g.offsets; d.dz_rows = x.dz_scratch; d.view = w.viewmatrix;
+        if (dv.n == BATCH_VIEWS)
+            if (int r = flush()) return named(fn, r);
+    }
+    return named(fn, flush());
 }
 
 int tgs_backward_render(void* stream, int P, int64_t R, const float* background, int width, int height, const void* binning_buffer,

@@ -4,6 +4,7 @@
 //   k_depth_bwd        back to front: the gradient of that sum through alpha_i (added into the slab rows the colour's per-pixel backward
 //                      has written) and through z_i (a per-instance scratch row)
 //   k_depth_bwd_gauss  per Gaussian: sum of its dz rows, times the third row of the view transform, added to dL_dmeans3D
+//   k_depth_bwd_gauss_views  the same for every view of a batch in one pass (tgs_backward_batch_depth_range)
 //
 // A pass of its own over the state every frame already stores (sorted records, n_contrib, final_T, the sorted keys): the render pair is not
 // touched and nothing here runs unless depth is asked for.  Geometry as k_render_bwd_det: 256 threads per tile, one lane per pixel, wave w
@@ -264,6 +265,48 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_depth_bwd_gauss(int P, const Meta
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_depth_bwd_gauss_views: k_depth_bwd_gauss for the views of a batch, behind the batch's per-Gaussian pass over the same range.  One lane
+// per Gaussian of [block0 * PRE_BLOCK, end); the views of the chunk in ascending index, a view's rows in row order, the products summed in
+// registers and ONE read-modify-write of dL_dmeans3D per Gaussian and chunk (the per-view kernel: one launch and one read-modify-write per
+// view).  No atomics, a fixed order: two runs give the same bits.
+// Load-latency bound, not VALU bound: per view a lane does three dependent steps (radii / tiles_touched / offsets -> the dz rows -> three
+// multiply-adds) and almost no arithmetic.  So the first step of EVERY view of the chunk is issued before any row is read -- the independent
+// loads of up to 8 views are in flight together instead of 8 round trips one behind the other -- and the kernel asks for no occupancy beyond
+// what 256-thread groups give: 24 VGPRs, no scratch, every wave slot of a SIMD usable to hide the row walk.  A view's meta / matrix words are uniform (scalar loads).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PRE_BLOCK) void k_depth_bwd_gauss_views(int end, int block0, const DepthViews dv, float* __restrict__ dL_dmean3D)
+{
+    const int idx = (block0 + (int)blockIdx.x) * PRE_BLOCK + (int)threadIdx.x;
+    if (idx >= end) return;
+    uint32_t tiles[BATCH_VIEWS], off[BATCH_VIEWS];
+#pragma unroll
+    for (int k = 0; k < BATCH_VIEWS; k++) {
+        tiles[k] = 0; off[k] = 0;
+        if (k < dv.n) {
+            const DepthView& w = dv.v[k];
+            // a rejected frame contributes nothing (and its offsets may point past its capacity: they are not followed)
+            const bool live = !(__builtin_nontemporal_load(&w.meta->error) & META_ERR_CAPACITY) && w.radii[idx] > 0;
+            if (live) { tiles[k] = w.tiles_touched[idx]; off[k] = w.offsets[idx]; }
+        }
+    }
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < BATCH_VIEWS; k++) {
+        if (k < dv.n && tiles[k] > 0) {
+            const DepthView& w = dv.v[k];
+            float dz = 0.f;
+            for (uint32_t r = 0; r < tiles[k]; r++) dz += w.dz_rows[off[k] + r];
+            ax += dz * w.view[2]; ay += dz * w.view[6]; az += dz * w.view[10];
+            any = any || dz != 0.f;
+        }
+    }
+    if (!any) return;
+    float* o = dL_dmean3D + 3 * (size_t)idx;
+    o[0] += ax; o[1] += ay; o[2] += az;
+}
+
+// ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
 // out_depth[N] <- 0, then the tiles with instances (at most T workgroups have work)
@@ -281,6 +324,12 @@ void launch_depth_bwd(hipStream_t st, const ImgState& s, const BinState& b, int 
 void launch_depth_bwd_gauss(hipStream_t st, int P, const Meta* meta, const int* radii, const GeomState& g, const float* view, const float* dz_rows, float* dL_dmean3D)
 {
     hipLaunchKernelGGL(k_depth_bwd_gauss, dim3((unsigned)n_blocks((size_t)P)), dim3(PRE_BLOCK), 0, st, P, meta, radii, g, view, dz_rows, dL_dmean3D);
+}
+// Gaussians [first, first + count) of P (first a multiple of PRE_BLOCK), the views of one chunk
+void launch_depth_bwd_gauss_views(hipStream_t st, int first, int count, const DepthViews& dv, float* dL_dmean3D)
+{
+    if (count <= 0 || dv.n <= 0) return;
+    hipLaunchKernelGGL(k_depth_bwd_gauss_views, dim3((unsigned)n_blocks((size_t)count)), dim3(PRE_BLOCK), 0, st, first + count, first / PRE_BLOCK, dv, dL_dmean3D);
 }
 
 }  // namespace tgs

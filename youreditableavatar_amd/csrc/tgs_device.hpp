@@ -1050,5 +1050,15 @@ struct FwdView {
     int* radii;
 };
 struct FwdViews { int n; FwdView v[BATCH_VIEWS]; };
+// One view of a batch for k_depth_bwd_gauss_views (tgs_depth.hip): where its dz rows lie and what to multiply their sum by (kernel argument)
+struct DepthView {
+    const Meta* meta;
+    const int* radii;
+    const uint32_t* tiles_touched;
+    const uint32_t* offsets;
+    const float* dz_rows;    // the view's dz scratch (k_depth_bwd), one float per instance slot
+    const float* view;       // the flat view matrix: d z / d mean = (view[2], view[6], view[10])
+};
+struct DepthViews { int n; DepthView v[BATCH_VIEWS]; };
 
 }  // namespace tgs

@@ -70,6 +70,16 @@ def _load() -> C.CDLL:
         lib.tgs_backward_batch_range_planes.argtypes = lib.tgs_backward_batch_range.argtypes + [C.c_int64]
     except AttributeError:
         pass
+    # alpha and depth in the whole-batch path (tgs_view_extras_t): part of this binding, so a library without them is stale
+    lib.tgs_sizeof_view_extras.restype = C.c_size_t
+    lib.tgs_outputs_views.restype = it
+    lib.tgs_outputs_views.argtypes = [vp, it, it, it, vp, vp]
+    lib.tgs_backward_render_views_extras_opt.restype = it
+    lib.tgs_backward_render_views_extras_opt.argtypes = [vp, vp, it, it, it, vp, vp]
+    lib.tgs_backward_batch_depth_range.restype = it
+    lib.tgs_backward_batch_depth_range.argtypes = [vp, it, it, vp, vp, vp, it, it]
+    lib.tgs_backward_depth_opt.restype = it
+    lib.tgs_backward_depth_opt.argtypes = lib.tgs_backward_opt.argtypes[:27] + [vp, vp, vp] + [vp] * 9 + [it]
     lib.tgs_state_field.restype = C.c_int64
     lib.tgs_state_field.argtypes = [vp, C.c_char_p, it, it, it, C.c_int64, it, it, vp, vp, vp, vp, C.c_size_t]
     lib.tgs_set_sort_lds_cap.restype = it
@@ -273,10 +283,13 @@ def frame_status(image_buffer: torch.Tensor) -> Tuple[int, int]:
 def rasterize_gaussians_backward_accumulate(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                             viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                             geomBuffer, R, binningBuffer, imageBuffer, debug, into, tile_bound: int = 0,
-                                            deterministic: Optional[bool] = None, mid_bound: int = 0):
+                                            deterministic: Optional[bool] = None, mid_bound: int = 0, *,
+                                            grad_out_alpha: Optional[torch.Tensor] = None, grad_out_depth: Optional[torch.Tensor] = None):
     """Multi-view extension (tgs_backward_accumulate): parameter gradients are ADDED into the fp32 tensors of ``into``
     (keys: means3D, opacities, and sh|colors_precomp, scales+rotations|cov3D_precomp; contiguous, on the device).
-    Returns dL_dmeans2D[P,3], the only per-view gradient."""
+    Returns dL_dmeans2D[P,3], the only per-view gradient.  ``grad_out_alpha`` / ``grad_out_depth`` ([1,H,W]): upstream gradients of the
+    frame's accumulated alpha / expected depth as well (tgs_backward_depth_opt with accumulate = 1; the dz scratch of R floats is
+    allocated here); both None: today's call (tgs_backward_opt), bit for bit."""
     dev = _require_gpu(means3D)
     P = int(means3D.size(0))
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
@@ -302,11 +315,19 @@ def rasterize_gaussians_backward_accumulate(background, means3D, radii, colors, 
 
         has_sh, has_sr = t["sh"] is not None, t["scales"] is not None
         opt = options(tile_bound=tile_bound, deterministic=deterministic, mid_bound=mid_bound)
-        r = _lib.tgs_backward_opt(
+        extras = []
+        if grad_out_alpha is not None or grad_out_depth is not None:
+            for name, g in (("grad_out_alpha", grad_out_alpha), ("grad_out_depth", grad_out_depth)):
+                if g is not None and g.numel() != H * W:
+                    raise RuntimeError(f"{name} must have H*W elements ([1,H,W])")
+            dA, dD = _dev_f32(grad_out_alpha, dev, "grad_out_alpha"), _dev_f32(grad_out_depth, dev, "grad_out_depth")
+            dz = torch.empty((max(int(R), 1),), dtype=torch.float32, device=dev) if dD is not None else None
+            extras = [_p(dA), _p(dD), _p(dz)]
+        r = (_lib.tgs_backward_depth_opt if extras else _lib.tgs_backward_opt)(
             C.byref(opt), 1, torch.cuda.current_stream(dev).cuda_stream, P, int(degree), M, int(R), _p(t["bg"]), W, H, _p(t["means"]), _p(t["sh"]), _p(t["colors"]),
             _p(t["scales"]), float(scale_modifier), _p(t["rots"]), _p(t["cov"]), _p(t["view"]), _p(t["proj"]), _p(t["campos"]),
             float(tan_fovx), float(tan_fovy), radii.contiguous().data_ptr(), geomBuffer.data_ptr(), binningBuffer.data_ptr(),
-            imageBuffer.data_ptr(), _p(t["dL"]), dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dst("opacities", (P, 1)),
+            imageBuffer.data_ptr(), _p(t["dL"]), *extras, dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dst("opacities", (P, 1)),
             None if has_sh else dst("colors_precomp", (P, 3)), dst("means3D", (P, 3)), None if has_sr else dst("cov3D_precomp", (P, 6)),
             dst("sh", (P, M, 3)) if has_sh else None, dst("scales", (P, 3)) if has_sr else None, dst("rotations", (P, 4)) if has_sr else None,
             int(bool(debug)))
@@ -330,6 +351,25 @@ if _lib.tgs_sizeof_view() != C.sizeof(_ViewT) or _ext.sizeof_view() != C.sizeof(
     raise ImportError(f"tgs_view_t / tgs_options_t: the library says {_lib.tgs_sizeof_view()} / {_lib.tgs_sizeof_options()} bytes, this binding declares "
                       f"{C.sizeof(_ViewT)} / {C.sizeof(_OptionsT)} -- a stale library or binding")
 ViewArray = lambda n: (_ViewT * n)()
+
+
+class _ViewExtrasT(C.Structure):
+    """tgs_view_extras_t (include/tgs_raster.h): alpha / depth outputs and gradients of one view, beside its tgs_view_t"""
+    _fields_ = [("struct_size", C.c_uint32), ("out_alpha", C.c_void_p), ("out_depth", C.c_void_p), ("dL_dalpha", C.c_void_p),
+                ("dL_ddepth", C.c_void_p), ("dz_scratch", C.c_void_p)]
+
+
+if _lib.tgs_sizeof_view_extras() != C.sizeof(_ViewExtrasT):
+    raise ImportError(f"tgs_view_extras_t: the library says {_lib.tgs_sizeof_view_extras()} bytes, this binding declares {C.sizeof(_ViewExtrasT)} "
+                      "-- a stale library or binding")
+
+
+def ViewExtrasArray(n: int):
+    """n zeroed tgs_view_extras_t with struct_size set (every pointer NULL: nothing asked of any view)"""
+    arr = (_ViewExtrasT * n)()
+    for x in arr:
+        x.struct_size = C.sizeof(_ViewExtrasT)
+    return arr
 
 
 def state_sizes(P: int, width: int, height: int, has_sh: bool, has_scale_rot: bool, r_capacity: int) -> Tuple[int, int, int]:
@@ -359,6 +399,33 @@ def backward_render_views(stream_handles, P, views, n_views, opt: Optional[_Opti
     arr = (C.c_void_p * len(stream_handles))(*stream_handles)
     r = _lib.tgs_backward_render_views_opt(C.byref(opt) if opt is not None else None, arr, len(stream_handles), int(P), int(n_views),
                                            views if isinstance(views, C.c_void_p) else C.cast(views, C.c_void_p))
+    if r < 0:
+        raise _err(int(r))
+
+
+def outputs_views(stream_handles, P, views, extras, n_views) -> None:
+    """tgs_outputs_views: alpha / depth of every view into extras[k].out_alpha / out_depth; ``stream_handles``: the streams the views'
+    k_render_fwd ran on (forward_views' streams, or the render streams when set_render_streams was in force)."""
+    arr = (C.c_void_p * len(stream_handles))(*stream_handles)
+    r = _lib.tgs_outputs_views(arr, len(stream_handles), int(P), int(n_views), C.cast(views, C.c_void_p), C.cast(extras, C.c_void_p))
+    if r < 0:
+        raise _err(int(r))
+
+
+def backward_render_views_extras(stream_handles, P, views, extras, n_views, opt: Optional[_OptionsT] = None) -> None:
+    """tgs_backward_render_views_extras_opt: backward_render_views with extras[k].dL_dalpha / dL_ddepth entering view k's per-pixel backward."""
+    arr = (C.c_void_p * len(stream_handles))(*stream_handles)
+    r = _lib.tgs_backward_render_views_extras_opt(C.byref(opt) if opt is not None else None, arr, len(stream_handles), int(P), int(n_views),
+                                                  C.cast(views, C.c_void_p), C.cast(extras, C.c_void_p) if extras is not None else None)
+    if r < 0:
+        raise _err(int(r))
+
+
+def backward_batch_depth_raw(stream, P, views, extras, n_views, dL_dmean3D, first: int = 0, count: Optional[int] = None) -> None:
+    """tgs_backward_batch_depth_range: the z-path of the depth gradient of all views, added to dL_dmean3D (a device pointer) for Gaussians
+    [first, first + count) -- behind the backward_batch_raw call of the same range, on the same stream."""
+    r = _lib.tgs_backward_batch_depth_range(stream, int(P), int(n_views), C.cast(views, C.c_void_p), C.cast(extras, C.c_void_p), dL_dmean3D,
+                                            int(first), int(P - first if count is None else count))
     if r < 0:
         raise _err(int(r))
 

@@ -475,15 +475,34 @@ def _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_b
     return _Call(settings, V, P, H, W, D, M, precomp, dsh_plane, params, colors_precomp, ranges)
 
 
-def _upstream_checked(dL: torch.Tensor, c: _Call) -> torch.Tensor:
-    if dL.dtype != torch.float32 or not dL.is_cuda or tuple(dL.shape[-3:]) != (3, c.H, c.W):
+def _upstream_checked(dL: torch.Tensor, c: _Call, require_gpu: bool = True) -> torch.Tensor:
+    if not torch.is_tensor(dL) or dL.dtype != torch.float32 or (require_gpu and not dL.is_cuda) or tuple(dL.shape[-3:]) != (3, c.H, c.W):
         raise RuntimeError("upstream must return a float32 GPU tensor [V,3,H,W] or [3,H,W]")
     return dL.contiguous()
 
 
+def _upstream_extras_checked(ret, c, names: Sequence[str], per_view: bool, require_gpu: bool = True) -> tuple:
+    """What an upstream callable returned when ``run_views`` handed it the maps ``names`` (of "alpha", "depth", in that order):
+    a tuple (dL/d images, dL/d map for every name), any of the latter None -> (dL, [gradient or None per name]), contiguous.
+    ``c`` needs H, W and V only; ``require_gpu=False`` checks everything but the device (host tests)."""
+    want = "(dL_dimages, " + ", ".join("dL_d" + n for n in names) + ")"
+    if not isinstance(ret, (tuple, list)) or len(ret) != 1 + len(names):
+        raise RuntimeError(f"upstream must return the tuple {want} when run_views returns {' and '.join(names)} (an entry may be None, the first may not)")
+    dL = _upstream_checked(ret[0], c, require_gpu)
+    shapes = [(1, c.H, c.W)] + ([] if per_view else [(c.V, 1, c.H, c.W)])
+    out = []
+    for name, g in zip(names, ret[1:]):
+        if g is not None:
+            if not torch.is_tensor(g) or g.dtype != torch.float32 or (require_gpu and not g.is_cuda) or tuple(g.shape) not in shapes:
+                raise RuntimeError(f"upstream: dL_d{name} must be None or a float32 GPU tensor " + " or ".join(str(list(sh)) for sh in shapes[::-1]))
+            g = g.contiguous()
+        out.append(g)
+    return dL, out
+
+
 def _of_view(dL: torch.Tensor, v: int) -> torch.Tensor:
-    """View v's part of an upstream gradient ([3,H,W]: the same for every view)."""
-    return dL if dL.dim() == 3 else dL[v]
+    """View v's part of an upstream gradient ([3,H,W] / [1,H,W]: the same for every view; None stays None)."""
+    return dL if (dL is None or dL.dim() == 3) else dL[v]
 
 
 class SyncFreeBatch:
@@ -555,7 +574,7 @@ class SyncFreeBatch:
                   rotations: torch.Tensor, upstream_batch: Optional[Callable[[torch.Tensor], torch.Tensor]], accumulate: bool = True,
                   colors_precomp: Optional[torch.Tensor] = None,
                   upstream_view: Optional[Callable[[int, torch.Tensor], torch.Tensor]] = None, grad_chunks: int = 1,
-                  on_chunk: Optional[Callable[[int, int], None]] = None) -> torch.Tensor:
+                  on_chunk: Optional[Callable[[int, int], None]] = None, return_alpha: bool = False, return_depth: bool = False):
         """Renders the views described by ``settings`` (GaussianRasterizationSettings, same image size, SH degree and scale
         modifier) of one Gaussian model (leaf parameters with allocated ``.grad``, SH colours, scales + rotations), calls
         ``upstream_batch(images[V,3,H,W]) -> dL/d images`` ([V,3,H,W], or [3,H,W] for all views) ONCE, and adds the
@@ -576,7 +595,18 @@ class SyncFreeBatch:
         ``grad_chunks`` / ``on_chunk(first, count)``: the step's one per-Gaussian pass runs as ``grad_chunks`` launches over consecutive
         ranges of Gaussians, and ``on_chunk`` is called right behind each launch (on the calling stream) -- the parameter gradients of
         Gaussians [first, first + count) are final once that launch is: a data-parallel step starts their all-reduce there
-        (``FlatGradients.all_reduce_rows``) while the next range is still being computed."""
+        (``FlatGradients.all_reduce_rows``) while the next range is still being computed.
+
+        ``return_alpha`` / ``return_depth``: the accumulated alpha (1 - final_T) and the expected depth (sum_i T_i alpha_i z_i, not
+        normalised) of every view as well, with gradients -- the outputs of ``rasterize_gaussians(return_alpha=, return_depth=)`` in the
+        whole-batch path.  ``run_views`` then returns ``(images, alpha[V,1,H,W] if asked, depth[V,1,H,W] if asked)`` (views of pooled
+        buffers, like the images), the upstream callables receive the maps as further positional arguments in that order --
+        ``upstream_batch(images, alpha, depth)``, ``upstream_view(v, image, alpha_v[1,H,W], depth_v[1,H,W])`` -- and return the tuple
+        ``(dL/d images, dL/d alpha, dL/d depth)`` in the same order: float32 GPU tensors [V,1,H,W] or [1,H,W] (all views) from the batch
+        callable, [1,H,W] from the view callable.  Any of the extra gradients may be None: that map took no part in the loss and no kernel
+        runs for it.  Both flags False (the default): nothing changes -- the same calls, buffers and return value as before.
+        ``run`` / ``rasterize_accumulate`` / ``DeferredBackward`` do not carry these outputs; feature channels are not part of this path."""
+        names = [n for n, on in (("alpha", return_alpha), ("depth", return_depth)) if on]
         c = _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_batch, upstream_view, colors_precomp, grad_chunks)
         V, P, D, M, precomp = c.V, c.P, c.D, c.M, c.precomp
         dev = means3D.device
@@ -587,19 +617,32 @@ class SyncFreeBatch:
                     t.grad.zero_()
             states = [self._render_view(c, v) for v in range(V)]
             images = torch.stack([s[1] for s in states])
-            dL = upstream_batch(images) if upstream_batch is not None else torch.stack([upstream_view(v, images[v]) for v in range(V)])
+            maps = [torch.stack([self._map_of(c, name, states[v]) for v in range(V)]) for name in names]
+            extra = [None] * V                               # per view: [dL/d map or None, per name]
+            if not names:
+                dL = upstream_batch(images) if upstream_batch is not None else torch.stack([upstream_view(v, images[v]) for v in range(V)])
+            elif upstream_batch is not None:
+                dL, gs = _upstream_extras_checked(upstream_batch(images, *maps), c, names, per_view=False)
+                extra = [[_of_view(g, v) for g in gs] for v in range(V)]
+            else:
+                rets = [_upstream_extras_checked(upstream_view(v, images[v], *[m[v] for m in maps]), c, names, per_view=True) for v in range(V)]
+                if any(r[0].dim() != 3 for r in rets):
+                    raise RuntimeError("upstream_view must return [3,H,W]")
+                dL, extra = torch.stack([r[0] for r in rets]), [r[1] for r in rets]
             gcol = torch.empty((V, P, 3), dtype=torch.float32, device=dev) if precomp else None
             scratch = torch.empty_like(shs) if c.dsh_plane else None
-            self.viewspace_grads = torch.stack([self._backward_view(c, v, states[v], _of_view(dL, v), gcol, scratch) for v in range(V)])
+            self.viewspace_grads = torch.stack([self._backward_view(c, v, states[v], _of_view(dL, v), gcol, scratch, names, extra[v]) for v in range(V)])
             self.color_grads = gcol
             self._learn(max(s[0] for s in states))
             for first, count in (c.ranges if on_chunk is not None else []):
                 on_chunk(first, count)
-            return images
+            return (images, *maps) if names else images
 
-        pool = self._pooled(c, cap)
+        pool = self._pooled(c, cap, names)
         self._fill_views(c, pool)
         arr, images, gcol = pool["arr"], pool["images"], pool["gcol"]
+        xarr, maps = pool.get("xarr"), [pool[name] for name in names]
+        with_depth = False                                  # a view has a depth gradient: the z-path pass follows every range of the per-Gaussian pass
         main = torch.cuda.current_stream(dev)
         lanes = _lanes(main, min(self.streams, V))
         with torch.cuda.device(dev):
@@ -612,11 +655,20 @@ class SyncFreeBatch:
                                  scales.data_ptr(), settings[0].scale_modifier, rotations.data_ptr(), arr, V, prefiltered=settings[0].prefiltered, opt=self.options)
             finally:
                 _C.set_render_streams([])
+            if names:
+                # the maps read what k_render_fwd wrote: on the lane each view composited on, behind it without an event
+                _C.outputs_views([st.cuda_stream for st in ren_lanes], P, arr, xarr, V)
             if upstream_view is None:
                 _join(lanes)
                 ready = [torch.cuda.Event()]                # (the verdicts are in pinned memory once the scans have run: tgs_view_t.host_meta)
                 ready[0].record(main)
-                dL = _upstream_checked(upstream_batch(images), c)
+                if names:
+                    dL, gs = _upstream_extras_checked(upstream_batch(images, *maps), c, names, per_view=False)
+                    for v in range(V):
+                        with_depth |= self._set_extra_grads(pool, v, names, [_of_view(g, v) for g in gs])
+                    self._keep = gs                              # (alive until the next batch)
+                else:
+                    dL = _upstream_checked(upstream_batch(images), c)
                 for v in range(V):
                     arr[v].dL_dpix = _of_view(dL, v).data_ptr()
                 _fork(lanes)
@@ -631,15 +683,25 @@ class SyncFreeBatch:
                 for l, st in enumerate(ren_lanes):
                     with torch.cuda.stream(st):
                         for v in range(l, V, len(ren_lanes)):
-                            g = _upstream_checked(upstream_view(v, images[v]), c)
+                            if names:
+                                g, gs = _upstream_extras_checked(upstream_view(v, images[v], *[m[v] for m in maps]), c, names, per_view=True)
+                            else:
+                                g, gs = _upstream_checked(upstream_view(v, images[v]), c), []
                             if g.dim() != 3:
                                 raise RuntimeError("upstream_view must return [3,H,W]")
-                            g.record_stream(st)
-                            dLs.append((v, g))
-                for v, g in dLs:
+                            for t in [g] + [x for x in gs if x is not None]:
+                                t.record_stream(st)
+                            dLs.append((v, g, gs))
+                for v, g, gs in dLs:
                     arr[v].dL_dpix = g.data_ptr()
+                    if names:
+                        with_depth |= self._set_extra_grads(pool, v, names, gs)
                 self._keep = dLs                                 # (alive until the next batch)
-            _C.backward_render_views([st.cuda_stream for st in (lanes if upstream_view is None else ren_lanes)], P, arr, V, opt=self.options)
+            bwd_lanes = [st.cuda_stream for st in (lanes if upstream_view is None else ren_lanes)]
+            if names:
+                _C.backward_render_views_extras(bwd_lanes, P, arr, xarr, V, opt=self.options)
+            else:
+                _C.backward_render_views(bwd_lanes, P, arr, V, opt=self.options)
             _join(lanes)
             # With on_chunk the verdict is read BEFORE the per-Gaussian pass is enqueued (the GPU still has the per-pixel backwards in its
             # queues): a range may only be handed out as final when no view has to be rendered again.
@@ -651,6 +713,8 @@ class SyncFreeBatch:
                                       settings[0].scale_modifier, rotations.data_ptr(), opacities.grad.data_ptr(), means3D.grad.data_ptr(),
                                       None if precomp else shs.grad.data_ptr(), scales.grad.data_ptr(), rotations.grad.data_ptr(), accumulate, g0, gcount,
                                       dsh_plane_stride=c.dsh_plane)
+                if with_depth:                              # dz . (third row of each view's transform), behind the range's stored / accumulated dL_dmeans3D
+                    _C.backward_batch_depth_raw(main.cuda_stream, P, arr, xarr, V, means3D.grad.data_ptr(), g0, gcount)
                 if eager:
                     on_chunk(g0, gcount)
         self.viewspace_grads = pool["g2d"]
@@ -664,22 +728,38 @@ class SyncFreeBatch:
             states = {v: self._render_view(c, v) for v in redo}
             for v in redo:
                 images[v].copy_(states[v][1])
-            dL2 = upstream_batch(images).contiguous() if upstream_view is None else None    # the gradient images depend on the re-rendered frames
+                for name, m in zip(names, maps):
+                    m[v].copy_(self._map_of(c, name, states[v]))
+            gs2 = [None] * len(names)
+            if upstream_view is not None:
+                dL2 = None
+            elif names:                                     # the gradient images depend on the re-rendered frames (and maps)
+                dL2, gs2 = _upstream_extras_checked(upstream_batch(images, *maps), c, names, per_view=False)
+            else:
+                dL2 = upstream_batch(images).contiguous()
             scratch = torch.empty_like(shs) if c.dsh_plane else None
             for v in redo:
-                g = _of_view(dL2, v) if dL2 is not None else _upstream_checked(upstream_view(v, images[v]), c)
-                pool["g2d"][v].copy_(self._backward_view(c, v, states[v], g, gcol, scratch))
+                gs = [_of_view(g, v) for g in gs2]
+                if dL2 is not None:
+                    g = _of_view(dL2, v)
+                elif names:
+                    g, gs = _upstream_extras_checked(upstream_view(v, images[v], *[m[v] for m in maps]), c, names, per_view=True)
+                else:
+                    g = _upstream_checked(upstream_view(v, images[v]), c)
+                pool["g2d"][v].copy_(self._backward_view(c, v, states[v], g, gcol, scratch, names, gs))
                 seen = max(seen, states[v][0])
         if on_chunk is not None and not eager:
             for first, count in c.ranges:     # the same calls in the same order as on a rank that had nothing to render again (collectives must pair up)
                 on_chunk(first, count)
         self._learn(seen, [max(counts) for counts in zip(*(tiles for _R, _rejected, tiles in rows))])
-        return images
+        return (images, *maps) if names else images
 
-    def _pooled(self, c: _Call, cap: int) -> dict:
-        """The batch's buffers, one tensor per kind for all views, and its tgs_view_t array: kept while the shapes and the capacity stay."""
+    def _pooled(self, c: _Call, cap: int, names: Sequence[str] = ()) -> dict:
+        """The batch's buffers, one tensor per kind for all views, and its tgs_view_t array: kept while the shapes and the capacity stay.
+        ``names`` (of "alpha", "depth"): the extra maps asked for -- their buffers [V,1,H,W], the depth's dz scratch [V, cap] and the
+        tgs_view_extras_t array exist only then, and a call without them keeps the key (and the pool) it always had."""
         dev = c.params["means3D"].device
-        key = (c.P, c.H, c.W, c.V, c.M, cap, dev, c.precomp)
+        key = (c.P, c.H, c.W, c.V, c.M, cap, dev, c.precomp) + ((tuple(names),) if names else ())
         if self._pool is None or self._pool["key"] != key:
             V, P = c.V, c.P
             gb, bb, ib = _C.state_sizes(P, c.W, c.H, not c.precomp, True, cap)
@@ -689,6 +769,10 @@ class SyncFreeBatch:
                               binning=z(V, al(bb), dt=torch.uint8), img=z(V, al(ib), dt=torch.uint8), sizes=(gb, bb, ib), arr=_C.ViewArray(V),
                               gcol=z(V, P, 3) if c.precomp else None,
                               host=torch.empty((V, _C.META_BYTES), dtype=torch.uint8, pin_memory=True))
+            if names:
+                self._pool.update({name: z(V, 1, c.H, c.W) for name in names}, xarr=_C.ViewExtrasArray(V))
+                if "depth" in names:
+                    self._pool["dz"] = z(V, cap)            # one float per instance slot and view (tgs_view_extras_t.dz_scratch)
         return self._pool
 
     def _fill_views(self, c: _Call, pool: dict) -> None:
@@ -710,6 +794,29 @@ class SyncFreeBatch:
             a.host_meta = pool["host"][v].data_ptr()        # k_scan writes the frame's Meta record here itself: no device-to-host copy in the stream
             a.tile_bound = tcap
             a.heavy_bound, a.mid_bound = heavy, mid
+            if "xarr" in pool:                              # the maps' slices; the gradients come later (_set_extra_grads)
+                x = pool["xarr"][v]
+                x.out_alpha = pool["alpha"][v].data_ptr() if "alpha" in pool else None
+                x.out_depth = pool["depth"][v].data_ptr() if "depth" in pool else None
+                x.dL_dalpha = x.dL_ddepth = x.dz_scratch = None
+
+    @staticmethod
+    def _set_extra_grads(pool: dict, v: int, names: Sequence[str], grads: Sequence[Optional[torch.Tensor]]) -> bool:
+        """View v's upstream gradients of the extra maps into the pooled tgs_view_extras_t array; -> whether it has a depth gradient."""
+        x, g = pool["xarr"][v], dict(zip(names, grads))
+        gA, gD = g.get("alpha"), g.get("depth")
+        x.dL_dalpha = gA.data_ptr() if gA is not None else None
+        x.dL_ddepth = gD.data_ptr() if gD is not None else None
+        x.dz_scratch = pool["dz"][v].data_ptr() if gD is not None else None
+        return gD is not None
+
+    @staticmethod
+    def _map_of(c: _Call, name: str, state: tuple) -> torch.Tensor:
+        """The alpha / depth map [1,H,W] of a view from _render_view (the synchronous frame's state)."""
+        R, _color, _radii, geom, binning, img = state[:6]
+        if name == "alpha":
+            return _C.alpha_from_state(img, c.H, c.W)
+        return _C.depth_from_state(geom, binning, img, c.P, c.H, c.W, int(R))
 
     def _render_view(self, c: _Call, v: int) -> tuple:
         """View v through the synchronous forward, buffers sized from the true count: (R, color, radii, geom, binning, img)."""
@@ -719,11 +826,13 @@ class SyncFreeBatch:
                                       e if c.precomp else p["sh"].detach(), c.D, rs.campos, rs.prefiltered, rs.debug, pruning=self._pruning)
 
     def _backward_view(self, c: _Call, v: int, state: tuple, dL: torch.Tensor, gcol: Optional[torch.Tensor],
-                       scratch: Optional[torch.Tensor]) -> torch.Tensor:
+                       scratch: Optional[torch.Tensor], names: Sequence[str] = (), extra: Optional[Sequence] = None) -> torch.Tensor:
         """The backward of a view from _render_view, in place: adds into the parameters' .grad (per-view colours: this view's alone, in gcol[v])
-        and returns dL/d means2D.  The one-view kernel writes dL_dsh by rows: a level-major .grad gets it through the row-major ``scratch``."""
+        and returns dL/d means2D.  The one-view kernel writes dL_dsh by rows: a level-major .grad gets it through the row-major ``scratch``.
+        ``names`` / ``extra``: the view's upstream gradients [1,H,W] (or None) of the extra maps."""
         rs, p, e = c.settings[v], c.params, torch.Tensor([])
-        R, _color, radii, geom, binning, img = state
+        R, _color, radii, geom, binning, img = state[:6]
+        kw = {"grad_out_" + n: g for n, g in zip(names, extra or ()) if g is not None}
         into = {name: t.grad for name, t in p.items()}
         if c.precomp:
             gcol[v].zero_()
@@ -734,7 +843,7 @@ class SyncFreeBatch:
         g2 = _C.rasterize_gaussians_backward_accumulate(rs.bg, p["means3D"].detach(), radii, c.colors[v] if c.precomp else e, p["scales"].detach(),
                                                         p["rotations"].detach(), rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
                                                         dL, e if c.precomp else p["sh"].detach(), c.D, rs.campos, geom, R, binning, img, rs.debug, into,
-                                                        deterministic=self._deterministic)
+                                                        deterministic=self._deterministic, **kw)
         if scratch is not None:
             p["sh"].grad.add_(scratch)
         return g2
