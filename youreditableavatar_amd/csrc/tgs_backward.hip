@@ -12,11 +12,12 @@
 // plain stores into a slab indexed in Gaussian order (row = offsets[g] + ordinal of the tile inside
 // g's rectangle).  k_preprocess_bwd then sums each Gaussian's contiguous rows in a fixed order: no
 // float atomics at all, and gradients are bitwise reproducible run to run (the reference's are not).
-#include "tgs_device.hpp"
+#include "tgs_replay.hpp"
 
 namespace tgs {
 
 constexpr int NACC = 9;        // colour rgb, mean2D xy, conic xx/xy/yy, opacity
+static_assert(NACC == RCOMP, "an entry's nine sums fill the components of wave_reduce36");
 
 // The per-pixel backward visits the first gridDim.x tiles of tile_order -- all tiles, or the caller's bound on the tiles with instances
 // (tgs_options_t::tile_bound).  A bound below the frame's real count would silently drop the remaining tiles' gradients: the first
@@ -60,52 +61,45 @@ __device__ __forceinline__ void render_bwd_det_body(const ImgState& s, const Bin
 
     if (frame_rejected(s)) return;
     check_tile_bound(s);
-    const uint4 td = s.tile_desc[blockIdx.x];
-    const uint32_t tile = td.x;
-    const uint32_t tx = tile % gx, ty = tile / gx;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int px = tx * TILE + (wv & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (wv >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float pixfx = (float)px, pixfy = (float)py;
-    const uint2 rg = make_uint2(td.y, td.z);
-    const uint32_t n = rg.y - rg.x;
+    const ReplayLane ln = replay_lane(s, gx, W, H);
+    const int wv = ln.wv, lane = ln.lane;
+    const uint32_t n = ln.n;
     if (n == 0) return;
     set_wave_priority(n);
-    stamp(s, tile, 2);
-    const size_t pix_id = (size_t)W * py + px, N = (size_t)W * H;
+    stamp(s, ln.tile, 2);
+    const size_t pix_id = ln.pix_id, N = (size_t)W * H;
     if (threadIdx.x == 0) { sA[RNULL] = make_float4(0.f, 0.f, 0.f, 0.f); sB[RNULL] = make_float4(0.f, 0.f, 0.f, 0.f); sC[RNULL] = 0.f; }
 
-    const float T_final = inside ? s.final_T[pix_id] : 0.f;
+    const float T_final = ln.inside ? s.final_T[pix_id] : 0.f;
     float T = T_final;
-    const uint32_t last_contributor = inside ? s.n_contrib[pix_id] : 0u;
+    const uint32_t last_contributor = ln.inside ? s.n_contrib[pix_id] : 0u;
     float dpx0 = 0.f, dpx1 = 0.f, dpx2 = 0.f;
-    if (inside) { dpx0 = dL_dpix[pix_id]; dpx1 = dL_dpix[N + pix_id]; dpx2 = dL_dpix[2 * N + pix_id]; }
+    if (ln.inside) { dpx0 = dL_dpix[pix_id]; dpx1 = dL_dpix[N + pix_id]; dpx2 = dL_dpix[2 * N + pix_id]; }
     float bg_dot_dpixel = 0.f;                              // backward.cu:533-535
     bg_dot_dpixel += bg[0] * dpx0; bg_dot_dpixel += bg[1] * dpx1; bg_dot_dpixel += bg[2] * dpx2;
-    if constexpr (WITH_DALPHA) { if (inside) bg_dot_dpixel -= dL_dalpha_pix[pix_id]; }
+    if constexpr (WITH_DALPHA) { if (ln.inside) bg_dot_dpixel -= dL_dalpha_pix[pix_id]; }
     float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;               // accum_rec
     float last_alpha = 0.f, lc0 = 0.f, lc1 = 0.f, lc2 = 0.f;
     const float ddelx_dx = (float)(0.5 * W), ddely_dy = (float)(0.5 * H);   // backward.cu:460-461
 
     // Entries behind every pixel's last contributor get no gradient (backward.cu:487-488): find the
     // deepest one any pixel of the tile needs and start there.
-    uint32_t mq = wave_max_u32(last_contributor);
-    if (lane == 0) wmax[wv] = mq;
-    __syncthreads();
-    const uint32_t qmax = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+    const uint32_t qmax = tile_deepest(last_contributor, wmax, wv, lane);
 
     // rows of the never-visited tail are zero
     for (uint32_t q = qmax + threadIdx.x; q < n; q += 256) {
-        float4* row = b.slab + (size_t)b.slot[rg.x + q] * SLAB_ROW;
+        float4* row = b.slab + (size_t)b.slot[ln.start + q] * SLAB_ROW;
         row[0] = make_float4(0.f, 0.f, 0.f, 0.f); row[1] = make_float4(0.f, 0.f, 0.f, 0.f); row[2] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 
+    // (Staging, walk, partial store and flush are written out here as in k_depth_bwd / k_feat_bwd, not shared: with the loop bodies handed to
+    // helpers hipcc swaps the operands of `last_alpha * lc + (1 - last_alpha) * acc` and of the two products summed into dL_dalpha in some
+    // unrolled instances; under -ffp-contract=fast the other product is then fused into the FMA and the gradients' last bits change.)
     // register-staged prefetch (slot t of a round = list position qhi-1-t: back to front)
     float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
     float2 rc = make_float2(0.f, 0.f);
     uint32_t rs = 0;
-    if (threadIdx.x < qmax) { const uint32_t pos = rg.x + qmax - 1 - threadIdx.x; ra = b.recA[pos]; rb = b.recB[pos]; rc = b.recC[pos]; rs = b.slot[pos]; }
+    if (threadIdx.x < qmax) { const uint32_t pos = ln.start + qmax - 1 - threadIdx.x; ra = b.recA[pos]; rb = b.recB[pos]; rc = b.recC[pos]; rs = b.slot[pos]; }
 
     for (uint32_t qhi = qmax; qhi > 0; qhi = qhi > RCHUNK ? qhi - RCHUNK : 0) {
         const uint32_t cnt = min((uint32_t)RCHUNK, qhi);
@@ -116,7 +110,7 @@ __device__ __forceinline__ void render_bwd_det_body(const ImgState& s, const Bin
         if (lane < RCHUNK / 64) touched[wv][lane] = 0ull;
         __syncthreads();
         if (qhi > RCHUNK && threadIdx.x < qhi - RCHUNK) {
-            const uint32_t pos = rg.x + qhi - RCHUNK - 1 - threadIdx.x;
+            const uint32_t pos = ln.start + qhi - RCHUNK - 1 - threadIdx.x;
             ra = b.recA[pos]; rb = b.recB[pos]; rc = b.recC[pos]; rs = b.slot[pos];
         }
 
@@ -136,7 +130,7 @@ __device__ __forceinline__ void render_bwd_det_body(const ImgState& s, const Bin
                 bool any = false;
 #pragma unroll
                 for (int u = 0; u < RUNROLL; u++) {
-                    dx[u] = a[u].x - pixfx; dy[u] = a[u].y - pixfy;
+                    dx[u] = a[u].x - ln.pixfx; dy[u] = a[u].y - ln.pixfy;
 #if TGS_FAST_MATH
                     // alpha exactly as k_render_fwd evaluated it (pair_power2 on the conic scaled as stage_conic_* scales it, v_exp_f32): the backward replays
                     // the forward's alpha >= 1/255 decisions, so it must round what the forward rounded (round 6; until then this kernel evaluated the
@@ -153,7 +147,7 @@ __device__ __forceinline__ void render_bwd_det_body(const ImgState& s, const Bin
                     any = any || valid[u];
                 }
                 if (__builtin_amdgcn_ballot_w64(any) == 0) continue;
-                float v[36];
+                float v[RUNROLL * NACC];
 #pragma unroll
                 for (int u = 0; u < RUNROLL; u++) {
 #pragma unroll
@@ -171,16 +165,7 @@ __device__ __forceinline__ void render_bwd_det_body(const ImgState& s, const Bin
                         dL_dalpha *= T;
                         last_alpha = alpha[u];
                         dL_dalpha += tgs_div(-T_final, om) * bg_dot_dpixel;
-                        const float dL_dG = bb[u].y * dL_dalpha;
-                        const float gdx = G[u] * dx[u], gdy = G[u] * dy[u];
-                        const float dG_ddelx = -gdx * a[u].z - gdy * a[u].w;
-                        const float dG_ddely = -gdy * bb[u].x - gdx * a[u].w;
-                        v[u * NACC + 3] = dL_dG * dG_ddelx * ddelx_dx;
-                        v[u * NACC + 4] = dL_dG * dG_ddely * ddely_dy;
-                        v[u * NACC + 5] = -0.5f * gdx * dx[u] * dL_dG;
-                        v[u * NACC + 6] = -0.5f * gdx * dy[u] * dL_dG;
-                        v[u * NACC + 7] = -0.5f * gdy * dy[u] * dL_dG;
-                        v[u * NACC + 8] = G[u] * dL_dalpha;
+                        geometry_terms<NACC, 3>(v, u, a[u], bb[u], dx[u], dy[u], G[u], dL_dalpha, ddelx_dx, ddely_dy);
                     }
                 }
                 float r[NACC];
@@ -221,7 +206,7 @@ __device__ __forceinline__ void render_bwd_det_body(const ImgState& s, const Bin
             row[0] = make_float4(r[0], r[1], r[2], r[3]); row[1] = make_float4(r[4], r[5], r[6], r[7]); row[2] = make_float4(r[8], lo[0], lo[1], lo[2]);
         }
     }
-    stamp(s, tile, 3);
+    stamp(s, ln.tile, 3);
 }
 __global__ __launch_bounds__(256) void k_render_bwd_det(const ImgState s, const BinState b, int W, int H, uint32_t gx,
                                                     const float* __restrict__ bg, const float* __restrict__ dL_dpix)

@@ -11,17 +11,14 @@
 // owns the 8x8-pixel quadrant w and walks only the staged entries whose block mask reaches it.  Which pairs were blended is replayed, not
 // stored: positions 1 .. n_contrib[pixel] that pass the two cut-offs (power > 0, alpha < 1/255), with alpha from the instruction sequence of
 // the render kernels (pair_power2 on the conic scaled as stage_conic_* scales it, v_exp_f32) -- so every pair falls on the side of 1/255 it
-// fell on in the colour frame.  No termination test: n_contrib is the position of the last BLENDED entry.
+// fell on in the colour frame (the plain-function pieces of this are shared: tgs_replay.hpp).  No termination test: n_contrib is the position of the last BLENDED entry.
 // z_i is the high word of the instance's sorted key (k_scatter: bits(GeomState::depth) << 32 | index), which lies beside the records.
 // No float atomics: per-wave sums in DPP, waves in a fixed order through LDS, one writer per row -- two runs give the same bits.
-#include "tgs_device.hpp"
+#include "tgs_replay.hpp"
 
 namespace tgs {
 
-constexpr int DACC = 7;        // mean2D xy, conic xx / xy / yy, opacity, z
-constexpr int DSTRIDE = 9;     // wave_reduce36 sums 4 entries x 9 components: the two spare components stay zero
-
-// (depth_pair_alpha and tile_deepest, the pair replay, live in tgs_device.hpp: tgs_feature.hip shares them)
+constexpr int DACC = 7;        // mean2D xy, conic xx / xy / yy, opacity, z (of wave_reduce36's RCOMP components the two spare ones stay zero)
 
 // ---------------------------------------------------------------------------------------------
 // k_depth_fwd: one workgroup per tile of tile_desc (workgroups behind the tiles with instances return: the output is zero-filled in front
@@ -37,17 +34,10 @@ __global__ __launch_bounds__(256) void k_depth_fwd(const ImgState s, const BinSt
 
     const uint2 ff = frame_flags(s);
     if ((ff.x & META_ERR_CAPACITY) || blockIdx.x >= ff.y) return;
-    const uint4 td = s.tile_desc[blockIdx.x];
-    const uint32_t tile = td.x;
-    const uint32_t tx = tile % gx, ty = tile / gx;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int px = tx * TILE + (wv & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (wv >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float pixfx = (float)px, pixfy = (float)py;
-    const uint32_t start = td.y, n = td.z - td.y;
-    const size_t pix_id = (size_t)W * py + px;
-    const uint32_t last_contributor = inside ? s.n_contrib[pix_id] : 0u;
+    const ReplayLane ln = replay_lane(s, gx, W, H);
+    const int wv = ln.wv, lane = ln.lane;
+    const uint32_t start = ln.start, n = ln.n;
+    const uint32_t last_contributor = ln.inside ? s.n_contrib[ln.pix_id] : 0u;
     const uint32_t qmax = min(tile_deepest(last_contributor, wmax, wv, lane), n);
     if (qmax == 0) return;
     if (threadIdx.x == 0) { sA[RNULL] = make_float4(0.f, 0.f, 0.f, 0.f); sB[RNULL] = make_float4(0.f, 0.f, 0.f, 0.f); sZ[RNULL] = 0.f; }
@@ -79,7 +69,7 @@ __global__ __launch_bounds__(256) void k_depth_fwd(const ImgState s, const BinSt
 #pragma unroll
                 for (int u = 0; u < RUNROLL; u++) {
                     float G; bool cut;
-                    const float alpha = depth_pair_alpha(a[u], bb[u], a[u].x - pixfx, a[u].y - pixfy, G, cut);
+                    const float alpha = replay_pair_alpha(a[u], bb[u], a[u].x - ln.pixfx, a[u].y - ln.pixfy, G, cut);
                     // 1-based list position base + j + 1 <= n_contrib; a padding entry (slot RNULL) has opacity 0 and is cut
                     if (base + j[u] < last_contributor && !cut) {
                         D += z[u] * (alpha * T);
@@ -89,7 +79,7 @@ __global__ __launch_bounds__(256) void k_depth_fwd(const ImgState s, const BinSt
             }
         }
     }
-    if (inside) out_depth[pix_id] = D;
+    if (ln.inside) out_depth[ln.pix_id] = D;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -113,19 +103,12 @@ __global__ __launch_bounds__(256) void k_depth_bwd(const ImgState s, const BinSt
 
     const uint2 ff = frame_flags(s);
     if ((ff.x & META_ERR_CAPACITY) || blockIdx.x >= ff.y) return;
-    const uint4 td = s.tile_desc[blockIdx.x];
-    const uint32_t tile = td.x;
-    const uint32_t tx = tile % gx, ty = tile / gx;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int px = tx * TILE + (wv & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (wv >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float pixfx = (float)px, pixfy = (float)py;
-    const uint32_t start = td.y, n = td.z - td.y;
-    const size_t pix_id = (size_t)W * py + px;
-    float T = inside ? s.final_T[pix_id] : 0.f;
-    const uint32_t last_contributor = inside ? s.n_contrib[pix_id] : 0u;
-    const float g = inside ? dL_ddepth[pix_id] : 0.f;
+    const ReplayLane ln = replay_lane(s, gx, W, H);
+    const int wv = ln.wv, lane = ln.lane;
+    const uint32_t start = ln.start, n = ln.n;
+    float T = ln.inside ? s.final_T[ln.pix_id] : 0.f;
+    const uint32_t last_contributor = ln.inside ? s.n_contrib[ln.pix_id] : 0u;
+    const float g = ln.inside ? dL_ddepth[ln.pix_id] : 0.f;
     const uint32_t qmax = min(tile_deepest(last_contributor, wmax, wv, lane), n);
     if (qmax == 0) return;                                  // (dz_rows is zero-filled in front of the launch: rows behind qmax keep 0)
     if (threadIdx.x == 0) { sA[RNULL] = make_float4(0.f, 0.f, 0.f, 0.f); sB[RNULL] = make_float4(0.f, 0.f, 0.f, 0.f); sZ[RNULL] = 0.f; }
@@ -164,16 +147,16 @@ __global__ __launch_bounds__(256) void k_depth_bwd(const ImgState s, const BinSt
                 bool any = false;
 #pragma unroll
                 for (int u = 0; u < RUNROLL; u++) {
-                    dx[u] = a[u].x - pixfx; dy[u] = a[u].y - pixfy;
+                    dx[u] = a[u].x - ln.pixfx; dy[u] = a[u].y - ln.pixfy;
                     bool cut;
-                    alpha[u] = depth_pair_alpha(a[u], bb[u], dx[u], dy[u], G[u], cut);
+                    alpha[u] = replay_pair_alpha(a[u], bb[u], dx[u], dy[u], G[u], cut);
                     valid[u] = (qhi - 1 - j[u] < last_contributor) && (j[u] < cnt) && !cut;
                     any = any || valid[u];
                 }
                 if (__builtin_amdgcn_ballot_w64(any) == 0) continue;
-                float v[36];
+                float v[RUNROLL * RCOMP];
 #pragma unroll
-                for (int i = 0; i < 36; i++) v[i] = 0.f;
+                for (int i = 0; i < RUNROLL * RCOMP; i++) v[i] = 0.f;
 #pragma unroll
                 for (int u = 0; u < RUNROLL; u++) {
                     if (valid[u]) {
@@ -182,20 +165,11 @@ __global__ __launch_bounds__(256) void k_depth_bwd(const ImgState s, const BinSt
                         acc = last_alpha * last_z + (1.f - last_alpha) * acc;
                         last_z = z[u]; last_alpha = alpha[u];
                         const float dL_dalpha = (z[u] - acc) * g * T;
-                        const float dL_dG = bb[u].y * dL_dalpha;
-                        const float gdx = G[u] * dx[u], gdy = G[u] * dy[u];
-                        const float dG_ddelx = -gdx * a[u].z - gdy * a[u].w;
-                        const float dG_ddely = -gdy * bb[u].x - gdx * a[u].w;
-                        v[u * DSTRIDE + 0] = dL_dG * dG_ddelx * ddelx_dx;
-                        v[u * DSTRIDE + 1] = dL_dG * dG_ddely * ddely_dy;
-                        v[u * DSTRIDE + 2] = -0.5f * gdx * dx[u] * dL_dG;
-                        v[u * DSTRIDE + 3] = -0.5f * gdx * dy[u] * dL_dG;
-                        v[u * DSTRIDE + 4] = -0.5f * gdy * dy[u] * dL_dG;
-                        v[u * DSTRIDE + 5] = G[u] * dL_dalpha;
-                        v[u * DSTRIDE + 6] = g * (alpha[u] * T);
+                        geometry_terms<RCOMP, 0>(v, u, a[u], bb[u], dx[u], dy[u], G[u], dL_dalpha, ddelx_dx, ddely_dy);
+                        v[u * RCOMP + 6] = g * (alpha[u] * T);
                     }
                 }
-                float r[DSTRIDE];
+                float r[RCOMP];
                 wave_reduce36(v, r);                        // row e of r[k]: total of entry e, component k
                 const int row = lane >> 4;
                 const uint32_t jr = row == 0 ? j[0] : row == 1 ? j[1] : row == 2 ? j[2] : j[3];
@@ -229,16 +203,7 @@ __global__ __launch_bounds__(256) void k_depth_bwd(const ImgState s, const BinSt
             }
             if (some) {
                 const uint32_t slot = sSlot[j];
-                float4* row = b.slab + (size_t)slot * SLAB_ROW;
-                float4 r0 = row[0], r1 = row[1], r2 = row[2];
-                // the conic shares lie in the row as hi + lo: add in double, split again
-                const double c5 = ((double)r1.y + (double)r2.y) + rc[0], c6 = ((double)r1.z + (double)r2.z) + rc[1], c7 = ((double)r1.w + (double)r2.w) + rc[2];
-                r0.w += r[0];
-                r1.x += r[1];
-                r1.y = (float)c5; r1.z = (float)c6; r1.w = (float)c7;
-                r2.x += r[5];
-                r2.y = (float)(c5 - (double)r1.y); r2.z = (float)(c6 - (double)r1.z); r2.w = (float)(c7 - (double)r1.w);
-                row[0] = r0; row[1] = r1; row[2] = r2;
+                slab_row_add(b.slab + (size_t)slot * SLAB_ROW, r, rc);
                 dz_rows[slot] = r[6];
             }
         }

@@ -754,32 +754,7 @@ __device__ __forceinline__ void wave_reduce36(const float (&v)[36], float (&r)[9
     }
 }
 
-// ---- pair replay shared by the passes over a finished frame's state (tgs_depth.hip, tgs_feature.hip) ----
-// alpha of one (pixel, entry) pair from the UNSCALED record, rounded as the render kernels round it; G = exp(power)
-__device__ __forceinline__ float depth_pair_alpha(const float4& a, const float4& bb, float dx, float dy, float& G, bool& cut)
-{
-#if TGS_FAST_MATH
-    float4 sa = a, sb = bb;
-    stage_conic_a(sa); stage_conic_b(sb);
-    const float power = pair_power2(sa.z, sa.w, sb.x, dx, dy);
-    G = __builtin_amdgcn_exp2f(power);
-#else
-    const float power = -0.5f * (a.z * dx * dx + bb.x * dy * dy) - a.w * dx * dy;
-    G = tgs_exp(power);
-#endif
-    const float alpha = fminf(0.99f, bb.y * G);
-    cut = (power > 0.0f) || (alpha < 1.0f / 255.0f);
-    return alpha;
-}
-
-// the deepest list position any pixel of the tile blended (the maximum of n_contrib over the workgroup's 256 lanes)
-__device__ __forceinline__ uint32_t tile_deepest(uint32_t last_contributor, uint32_t* wmax, int wv, int lane)
-{
-    const uint32_t mq = wave_max_u32(last_contributor);
-    if (lane == 0) wmax[wv] = mq;
-    __syncthreads();
-    return max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
-}
+// (the pair replay and the rest of the tile-replay skeleton of k_render_bwd_det / k_depth_* / k_feat_*: tgs_replay.hpp)
 
 // ---------------------------------------------------------------------------------------------
 // bitonic network, all comparators ascending ("flip" + "disperse" form): because the larger key

@@ -6,19 +6,18 @@
 //   k_feat_bwd_gauss  per Gaussian: sum of its scratch rows, in row order, into dL_dfeatures[i, :]
 //
 // tgs_depth.hip is the special case "one channel, the feature is z"; geometry, staging and the pair replay are its (256 threads per tile, one
-// lane per pixel, wave w owns the 8x8-pixel quadrant w, depth_pair_alpha / tile_deepest of tgs_device.hpp).  The feature row of a staged entry
+// lane per pixel, wave w owns the 8x8-pixel quadrant w, replay_lane / replay_pair_alpha / tile_deepest / geometry_terms / slab_row_add of tgs_replay.hpp).  The feature row of a staged entry
 // is gathered by the Gaussian index, the low word of the instance's sorted key, and lies in LDS beside the records.
 // Channels travel in groups of at most FGROUP = 8 per launch (C = 9 .. 16: two launches each way).  The through-alpha share is linear in the
 // channels, so each launch adds its own share to the slab rows: launches on one stream are ordered and a row has one writer.  The kernels are
 // compiled for 4 and for 8 channel slots (a group of 1 .. 4 channels takes the narrow one; slots behind the group hold zeros and store nothing).
 // Signed values, nothing clamped, no float atomics: two runs give the same bits.
-#include "tgs_device.hpp"
+#include "tgs_replay.hpp"
 
 namespace tgs {
 
 constexpr int FGROUP = 8;          // channels per launch: 8 channels x 4 entries are one wave_reduce36 call
 constexpr int FGEO = 6;            // mean2D xy, conic xx / xy / yy, opacity
-constexpr int FSTRIDE = 9;         // wave_reduce36 sums 4 entries x 9 components
 // k_feat_bwd stages FCHUNK entries per round, not RCHUNK: the per-wave partial sums are 4 x (6 + 8) x (FCHUNK + 1) floats = 28.9 KB; at 256
 // entries they alone would be 57.6 KB on top of the staging arrays.  (The staging arrays keep RCHUNK + 1 slots: RNULL is the lists' padding.)
 constexpr int FCHUNK = 128;
@@ -52,17 +51,10 @@ __global__ __launch_bounds__(256) void k_feat_fwd(const ImgState s, const BinSta
 
     const uint2 ff = frame_flags(s);
     if ((ff.x & META_ERR_CAPACITY) || blockIdx.x >= ff.y) return;
-    const uint4 td = s.tile_desc[blockIdx.x];
-    const uint32_t tile = td.x;
-    const uint32_t tx = tile % gx, ty = tile / gx;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int px = tx * TILE + (wv & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (wv >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float pixfx = (float)px, pixfy = (float)py;
-    const uint32_t start = td.y, n = td.z - td.y;
-    const size_t pix_id = (size_t)W * py + px;
-    const uint32_t last_contributor = inside ? s.n_contrib[pix_id] : 0u;
+    const ReplayLane ln = replay_lane(s, gx, W, H);
+    const int wv = ln.wv, lane = ln.lane;
+    const uint32_t start = ln.start, n = ln.n;
+    const uint32_t last_contributor = ln.inside ? s.n_contrib[ln.pix_id] : 0u;
     const uint32_t qmax = min(tile_deepest(last_contributor, wmax, wv, lane), n);
     if (qmax == 0) return;
     if (threadIdx.x == 0) {
@@ -102,7 +94,7 @@ __global__ __launch_bounds__(256) void k_feat_fwd(const ImgState s, const BinSta
 #pragma unroll
                 for (int u = 0; u < RUNROLL; u++) {
                     float G; bool cut;
-                    const float alpha = depth_pair_alpha(a[u], bb[u], a[u].x - pixfx, a[u].y - pixfy, G, cut);
+                    const float alpha = replay_pair_alpha(a[u], bb[u], a[u].x - ln.pixfx, a[u].y - ln.pixfy, G, cut);
                     // 1-based list position base + j + 1 <= n_contrib; a padding entry (slot RNULL) has opacity 0 and is cut
                     if (base + j[u] < last_contributor && !cut) {
                         const float w = alpha * T;
@@ -118,10 +110,10 @@ __global__ __launch_bounds__(256) void k_feat_fwd(const ImgState s, const BinSta
             }
         }
     }
-    if (inside) {
+    if (ln.inside) {
         const size_t N = (size_t)W * H;
 #pragma unroll
-        for (int c = 0; c < NC; c++) if (c < nc) out[(size_t)(c0 + c) * N + pix_id] = F[c];
+        for (int c = 0; c < NC; c++) if (c < nc) out[(size_t)(c0 + c) * N + ln.pix_id] = F[c];
     }
 }
 
@@ -151,18 +143,11 @@ __global__ __launch_bounds__(256) void k_feat_bwd(const ImgState s, const BinSta
 
     const uint2 ff = frame_flags(s);
     if ((ff.x & META_ERR_CAPACITY) || blockIdx.x >= ff.y) return;
-    const uint4 td = s.tile_desc[blockIdx.x];
-    const uint32_t tile = td.x;
-    const uint32_t tx = tile % gx, ty = tile / gx;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int px = tx * TILE + (wv & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (wv >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float pixfx = (float)px, pixfy = (float)py;
-    const uint32_t start = td.y, n = td.z - td.y;
-    const size_t pix_id = (size_t)W * py + px;
-    float T = inside ? s.final_T[pix_id] : 0.f;
-    const uint32_t last_contributor = inside ? s.n_contrib[pix_id] : 0u;
+    const ReplayLane ln = replay_lane(s, gx, W, H);
+    const int wv = ln.wv, lane = ln.lane;
+    const uint32_t start = ln.start, n = ln.n;
+    float T = ln.inside ? s.final_T[ln.pix_id] : 0.f;
+    const uint32_t last_contributor = ln.inside ? s.n_contrib[ln.pix_id] : 0u;
     const uint32_t qmax = min(tile_deepest(last_contributor, wmax, wv, lane), n);
     if (qmax == 0) return;                                  // (feat_rows is zero-filled in front of the launches: rows behind qmax keep 0)
     if (threadIdx.x == 0) {
@@ -175,7 +160,7 @@ __global__ __launch_bounds__(256) void k_feat_bwd(const ImgState s, const BinSta
         const size_t N = (size_t)W * H;
 #pragma unroll
         for (int c = 0; c < NC; c++) {
-            g[c] = (inside && c < nc) ? dL_dmap[(size_t)(c0 + c) * N + pix_id] : 0.f;
+            g[c] = (ln.inside && c < nc) ? dL_dmap[(size_t)(c0 + c) * N + ln.pix_id] : 0.f;
             acc[c] = 0.f; last_f[c] = 0.f;
         }
     }
@@ -216,16 +201,16 @@ __global__ __launch_bounds__(256) void k_feat_bwd(const ImgState s, const BinSta
                 bool any = false;
 #pragma unroll
                 for (int u = 0; u < RUNROLL; u++) {
-                    dx[u] = a[u].x - pixfx; dy[u] = a[u].y - pixfy;
+                    dx[u] = a[u].x - ln.pixfx; dy[u] = a[u].y - ln.pixfy;
                     bool cut;
-                    alpha[u] = depth_pair_alpha(a[u], bb[u], dx[u], dy[u], G[u], cut);
+                    alpha[u] = replay_pair_alpha(a[u], bb[u], dx[u], dy[u], G[u], cut);
                     valid[u] = (qhi - 1 - j[u] < last_contributor) && (j[u] < cnt) && !cut;
                     any = any || valid[u];
                 }
                 if (__builtin_amdgcn_ballot_w64(any) == 0) continue;
-                float v[36], vf[36];                        // geometry and channel sums of the 4 entries
+                float v[RUNROLL * RCOMP], vf[RUNROLL * RCOMP];                        // geometry and channel sums of the 4 entries
 #pragma unroll
-                for (int i = 0; i < 36; i++) { v[i] = 0.f; vf[i] = 0.f; }
+                for (int i = 0; i < RUNROLL * RCOMP; i++) { v[i] = 0.f; vf[i] = 0.f; }
 #pragma unroll
                 for (int u = 0; u < RUNROLL; u++) {
                     if (valid[u]) {
@@ -244,23 +229,14 @@ __global__ __launch_bounds__(256) void k_feat_bwd(const ImgState s, const BinSta
                             acc[c] = last_alpha * last_f[c] + (1.f - last_alpha) * acc[c];
                             last_f[c] = fu[c];
                             sum += (fu[c] - acc[c]) * g[c];
-                            vf[u * FSTRIDE + c] = g[c] * w;
+                            vf[u * RCOMP + c] = g[c] * w;
                         }
                         last_alpha = alpha[u];
                         const float dL_dalpha = sum * T;
-                        const float dL_dG = bb[u].y * dL_dalpha;
-                        const float gdx = G[u] * dx[u], gdy = G[u] * dy[u];
-                        const float dG_ddelx = -gdx * a[u].z - gdy * a[u].w;
-                        const float dG_ddely = -gdy * bb[u].x - gdx * a[u].w;
-                        v[u * FSTRIDE + 0] = dL_dG * dG_ddelx * ddelx_dx;
-                        v[u * FSTRIDE + 1] = dL_dG * dG_ddely * ddely_dy;
-                        v[u * FSTRIDE + 2] = -0.5f * gdx * dx[u] * dL_dG;
-                        v[u * FSTRIDE + 3] = -0.5f * gdx * dy[u] * dL_dG;
-                        v[u * FSTRIDE + 4] = -0.5f * gdy * dy[u] * dL_dG;
-                        v[u * FSTRIDE + 5] = G[u] * dL_dalpha;
+                        geometry_terms<RCOMP, 0>(v, u, a[u], bb[u], dx[u], dy[u], G[u], dL_dalpha, ddelx_dx, ddely_dy);
                     }
                 }
-                float r[FSTRIDE], rf[FSTRIDE];
+                float r[RCOMP], rf[RCOMP];
                 wave_reduce36(v, r);                        // row e of r[k]: total of entry e, component k
                 wave_reduce36(vf, rf);
                 const int row = lane >> 4;
@@ -298,16 +274,7 @@ __global__ __launch_bounds__(256) void k_feat_bwd(const ImgState s, const BinSta
             }
             if (some) {
                 const uint32_t slot = sSlot[j];
-                float4* row = b.slab + (size_t)slot * SLAB_ROW;
-                float4 r0 = row[0], r1 = row[1], r2 = row[2];
-                // the conic shares lie in the row as hi + lo: add in double, split again
-                const double c5 = ((double)r1.y + (double)r2.y) + rc[0], c6 = ((double)r1.z + (double)r2.z) + rc[1], c7 = ((double)r1.w + (double)r2.w) + rc[2];
-                r0.w += r[0];
-                r1.x += r[1];
-                r1.y = (float)c5; r1.z = (float)c6; r1.w = (float)c7;
-                r2.x += r[5];
-                r2.y = (float)(c5 - (double)r1.y); r2.z = (float)(c6 - (double)r1.z); r2.w = (float)(c7 - (double)r1.w);
-                row[0] = r0; row[1] = r1; row[2] = r2;
+                slab_row_add(b.slab + (size_t)slot * SLAB_ROW, r, rc);
                 float* fr = feat_rows + (size_t)slot * C + c0;
 #pragma unroll
                 for (int c = 0; c < NC; c++) if (c < nc) fr[c] = r[FGEO + c];
