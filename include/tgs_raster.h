@@ -294,8 +294,11 @@ int tgs_backward_depth_opt(const tgs_options_t* opt, int accumulate, void* strea
  *                      colour's share (added to it) and on through the unchanged per-Gaussian pass;
  *   dL_dcolor / dL_dsh get nothing from it.
  * Channels travel in groups of 8 per launch (C = 9 .. 16: two launches each way).  No float atomics: two runs give the same bits.
- * Feature channels are NOT part of the whole-batch path (tgs_*_views, tgs_backward_batch; alpha and depth are: tgs_view_extras_t) -- the
- * descriptor there is sized by its struct_size field so that they can be appended.
+ * Part of the whole-batch path since tgs_view_features_t (below, behind tgs_backward_batch_depth_range): the feature map of every view of a
+ * batch and its gradients, in a third array beside tgs_view_t and tgs_view_extras_t (the latter keeps its six fields: nothing is appended to
+ * it).  What is still NOT part of the whole-batch path: median / mode depth, more than 16 channels, half-precision features, and
+ * tgs_backward_batch without ranges (the features' per-Gaussian pass exists as tgs_backward_batch_features_range only; first = 0, count = P
+ * is the whole model).
  *
  * tgs_features: out[C*H*W] of a finished forward (P, width, height as given to it, R as it returned or was given), enqueued on `stream`: a
  * pass of its own over the frame's state, the render kernels are not involved.  P == 0 or R == 0: nothing was blended, nothing is launched
@@ -540,7 +543,8 @@ int tgs_backward_batch_range_planes(void* stream, int P, int D, int M, int n_vie
 /* ---- alpha and depth in the whole-batch path ----
  * tgs_view_t is frozen (its size is part of ABI 3), so what a view needs for the two extra outputs travels in a SECOND array beside it: same
  * length, same index.  struct_size is the sizeof of the caller's build and the stride of the caller's array; fields beyond it read as NULL,
- * and every element of one array carries the same value.  Any pointer may be NULL: that output / gradient then takes no part and no kernel
+ * and every element of one array carries the same value (the struct keeps these six fields: feature channels have an array of their own,
+ * tgs_view_features_t below).  Any pointer may be NULL: that output / gradient then takes no part and no kernel
  * is launched for it.  extras == NULL: no view has any. */
 typedef struct {
     uint32_t struct_size;     /* sizeof(tgs_view_extras_t) of the caller's build: fields beyond it read as NULL */
@@ -578,6 +582,50 @@ int tgs_backward_render_views_extras_opt(const tgs_options_t* opt, void* const* 
  * order: two runs give the same bits. */
 int tgs_backward_batch_depth_range(void* stream, int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras, float* dL_dmean3D,
                                    int first, int count);
+
+/* ---- feature channels in the whole-batch path ----
+ * tgs_view_t and tgs_view_extras_t are frozen (their sizes are checked by every binding), so what a view needs for the feature map travels in
+ * a THIRD array beside them: same length, same index, its own struct_size -- the sizeof of the caller's build and the stride of the caller's
+ * array; fields beyond it read as NULL / 0, and every element of one array carries the same value.  The features are the model's (normals,
+ * masks, labels): every element that takes part -- one with features, out_features or dL_dfeature_map -- carries the same C and the same
+ * features pointer.  out_features / dL_dfeature_map may be NULL: that output / gradient then takes no part and no kernel is launched for
+ * it.  feats == NULL: no view has any.  Definitions: tgs_features above. */
+typedef struct {
+    uint32_t struct_size;          /* sizeof(tgs_view_features_t) of the caller's build: fields beyond it read as NULL / 0 */
+    int32_t  C;                    /* 1 .. TGS_FEATURE_MAX_CHANNELS */
+    const float* features;         /* [P*C], the model's */
+    float* out_features;           /* [C*H*W] or NULL */
+    const float* dL_dfeature_map;  /* [C*H*W] or NULL */
+    float* feature_scratch;        /* views[k].R * C floats of the caller's (contents on entry do not matter), required with dL_dfeature_map */
+} tgs_view_features_t;             /* 40 bytes */
+size_t tgs_sizeof_view_features(void);
+
+/* tgs_features into feats[k].out_features for every view of a finished tgs_forward_views call, from the view's state (views[k]: width,
+ * height, R, the three buffers).  View k is enqueued on streams[k % n_streams].  WHICH streams: the rule written above tgs_outputs_views --
+ * the pass reads n_contrib, which k_render_fwd writes, so pass the streams the views' k_render_fwd ran on: the streams of tgs_forward_views
+ * itself, or the render streams when tgs_set_render_streams was in force.  A frame the sync-free forward rejected, a frame without instances
+ * (R == 0) and an empty model (P == 0) give a zero map. */
+int tgs_features_views(void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_features_t* feats);
+
+/* tgs_backward_render_views_extras_opt (extras may be NULL) and, per view with feats[k].dL_dfeature_map, the features' per-pixel backward
+ * behind the depth's share on the same stream -- the order of the one-view call: colour + alpha, then depth, then features.  feature_scratch
+ * is zero-filled, then the through-alpha share is ADDED into the slab rows the colour's backward has just written (the rows tgs_backward_batch
+ * reads) and the channel sums of every instance are left in feature_scratch for tgs_backward_batch_features_range.  feats == NULL, or no
+ * dL_dfeature_map in any view: exactly the launches of tgs_backward_render_views_extras_opt. */
+int tgs_backward_render_views_features_opt(const tgs_options_t* opt, void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views,
+                                           const tgs_view_extras_t* extras, const tgs_view_features_t* feats);
+
+/* The gradient of the features for all views in one pass: for Gaussians [first, first + count) (the rule of tgs_backward_batch_range)
+ *     dL_dfeatures[p*C + c] (= | +=, with `accumulate`) sum over the views k with dL_dfeature_map and R > 0, ascending, of
+ *                                                       (sum of p's feature_scratch rows of view k, in row order)[c].
+ * accumulate == 0 leaves every row of the range defined: a Gaussian that is live in no such view gets an exact zero row, and with no such
+ * view at all the range is zero-filled (as long as an element that takes part names C).  accumulate != 0 with no such view launches nothing.
+ * Rejected frames and Gaussians culled in a view contribute nothing.  One launch per 8 such views (the first of a call honours `accumulate`,
+ * the later ones add); no float atomics, a fixed order: two runs give the same bits.  It writes a buffer the per-Gaussian pass does not touch,
+ * so it is independent of tgs_backward_batch_range; it runs on `stream` like that pass, behind the join of the streams of
+ * tgs_backward_render_views_features_opt.  NULL dL_dfeatures with a view that has dL_dfeature_map is an error. */
+int tgs_backward_batch_features_range(void* stream, int P, int n_views, const tgs_view_t* views, const tgs_view_features_t* feats,
+                                      float* dL_dfeatures, int accumulate, int first, int count);
 
 /* ---- "next" row 2: the trainers' photometric loss ----
  * loss = (1 - dssim_factor) * l1_loss(img, gt) + dssim_factor * (1 - ssim(img, gt)), window 11, sigma 1.5, zero padding

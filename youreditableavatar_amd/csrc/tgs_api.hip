@@ -36,6 +36,7 @@ void launch_feat_fwd(hipStream_t, const ImgState&, const BinState&, int W, int H
 void launch_feat_bwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t tiles, size_t R, int P, int C, const float* features,
                      const float* dL_dmap, float* feat_rows);
 void launch_feat_bwd_gauss(hipStream_t, int P, int C, const Meta* meta, const int* radii, const GeomState&, const float* feat_rows, float* dL_dfeatures, int accumulate);
+void launch_feat_bwd_gauss_views(hipStream_t, int first, int count, int C, const FeatViews&, float* dL_dfeatures, int accumulate, bool vec);
 }  // namespace tgs
 
 using namespace tgs;
@@ -568,8 +569,9 @@ static int backward_impl(bool strict, const Opts& opt, int accumulate, hipStream
 }
 
 // tgs_backward_render[_views]: the view's own fields (tgs_backward_render packs its arguments into one)
+// feat (tgs_backward_render_views_features_opt): C, features, dL_dfeat_map and feat_scratch of the view, the only fields looked at
 static int backward_render_impl(const Opts& opt, hipStream_t st, int P, const tgs_view_t& w, const float* dL_dalpha = nullptr, const float* dL_ddepth = nullptr,
-                                float* dz_scratch = nullptr)
+                                float* dz_scratch = nullptr, const BwdArgs* feat = nullptr)
 {
     g_err[0] = 0;
     if (P == 0) return TGS_OK;
@@ -578,7 +580,7 @@ static int backward_render_impl(const Opts& opt, hipStream_t st, int P, const tg
     if (dL_ddepth && !dz_scratch) return fail(TGS_ERR_INVALID, "NULL required pointer");
     const ViewArgs v = view_args(w);
     return enqueue_render_bwd(opt, st, 0, carve_frame(GeomShape{(size_t)P, false, false}, v, w.R, nullptr, w.binning_buffer, w.img_buffer), v, w.R, w.dL_dpix, dL_dalpha,
-                              dL_ddepth, dz_scratch);
+                              dL_ddepth, dz_scratch, feat, P);
 }
 
 // element k of a caller's tgs_view_extras_t array (stride and valid prefix: the array's struct_size); fields beyond the caller's build read as NULL
@@ -603,6 +605,43 @@ static int check_extras_call(int P, int n_views, const tgs_view_t* views, const 
     tgs_view_extras_t x;
     for (int k = 0; k < n_views && extras; k++)
         if (int r = read_extras(extras, k, x)) return r;
+    return TGS_OK;
+}
+
+// element k of a caller's tgs_view_features_t array, as read_extras reads the extras; an element TAKES PART when it has features, out_features
+// or dL_dfeature_map
+static bool feats_part(const tgs_view_features_t& x) { return x.features || x.out_features || x.dL_dfeature_map; }
+static int read_feats(const tgs_view_features_t* base, int k, tgs_view_features_t& out)
+{
+    memset(&out, 0, sizeof(out));
+    if (!base) return TGS_OK;
+    const size_t stride = base->struct_size;
+    if (stride < offsetof(tgs_view_features_t, features) + sizeof(base->features))
+        return fail(TGS_ERR_INVALID, "tgs_view_features_t: struct_size %zu is smaller than the end of the features field", stride);
+    memcpy(&out, (const char*)base + (size_t)k * stride, stride < sizeof(out) ? stride : sizeof(out));
+    if (out.struct_size != stride) return fail(TGS_ERR_INVALID, "view %d: tgs_view_features_t.struct_size %u differs from the array's %zu", k, out.struct_size, stride);
+    if (!feats_part(out)) return TGS_OK;
+    if (out.C < 1 || out.C > TGS_FEATURE_MAX_CHANNELS) return fail(TGS_ERR_INVALID, "view %d: bad channel count C=%d (1 .. %d)", k, out.C, TGS_FEATURE_MAX_CHANNELS);
+    if (!out.features) return fail(TGS_ERR_INVALID, "view %d: out_features / dL_dfeature_map without features", k);
+    if (out.dL_dfeature_map && !out.feature_scratch) return fail(TGS_ERR_INVALID, "view %d: dL_dfeature_map without feature_scratch", k);
+    return TGS_OK;
+}
+// the arguments the three *_views feature entry points share, checked before anything is enqueued; -> C and features of the elements that take
+// part (the model's: the same in all of them; C = 0: none takes part)
+static int check_feats_call(int P, int n_views, const tgs_view_t* views, const tgs_view_features_t* feats, int& C, const float*& features)
+{
+    g_err[0] = 0;
+    C = 0; features = nullptr;
+    if (P < 0 || n_views < 0) return fail(TGS_ERR_INVALID, "bad sizes P=%d n_views=%d", P, n_views);
+    if (n_views > 0 && !views) return fail(TGS_ERR_INVALID, "NULL required pointer (views)");
+    tgs_view_features_t x;
+    for (int k = 0; k < n_views && feats; k++) {
+        if (int r = read_feats(feats, k, x)) return r;
+        if (!feats_part(x)) continue;
+        if (C == 0) { C = x.C; features = x.features; }
+        else if (x.C != C || x.features != features)
+            return fail(TGS_ERR_INVALID, "view %d: C=%d / features differ from an earlier view's (C=%d): the features are the model's, one tensor for all views", k, x.C, C);
+    }
     return TGS_OK;
 }
 
@@ -1030,6 +1069,113 @@ int tgs_backward_batch_depth_range(void* stream, int P, int n_views, const tgs_v
         DepthView& d = dv.v[dv.n++];
         d.meta = fb.s.meta; d.radii = w.radii; d.tiles_touched = fb.g.tiles_touched; d.offsets = fb.g.offsets; d.dz_rows = x.dz_scratch; d.view = w.viewmatrix;
         if (dv.n == BATCH_VIEWS)
+            if (int r = flush()) return named(fn, r);
+    }
+    return named(fn, flush());
+}
+
+size_t tgs_sizeof_view_features(void) { return sizeof(tgs_view_features_t); }
+
+int tgs_features_views(void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_features_t* feats)
+{
+    static const char* fn = "tgs_features_views";
+    int C; const float* features;
+    if (int r = check_feats_call(P, n_views, views, feats, C, features)) return named(fn, r);
+    if ((n_views > 0 && !streams) || n_streams <= 0) return named(fn, fail(TGS_ERR_INVALID, "bad arguments (streams, n_streams=%d)", n_streams));
+    if (!feats) return TGS_OK;
+    for (int k = 0; k < n_views; k++) {
+        tgs_view_features_t x;
+        if (int r = read_feats(feats, k, x)) return named(fn, r);
+        if (!x.out_features) continue;
+        const tgs_view_t& w = views[k];
+        hipStream_t st = (hipStream_t)streams[k % n_streams];
+        if (w.width <= 0 || w.height <= 0 || w.R < 0) return named(fn, fail(TGS_ERR_INVALID, "view %d: bad sizes", k));
+        const ViewArgs v = view_args(w);
+        if (v.gx() > 65535u || v.gy() > 65535u) return named(fn, fail(TGS_ERR_INVALID, "view %d: image too large", k));
+        if (P == 0 || w.R == 0) {                           // nothing was blended (an empty model writes no image state at all)
+            HIP_TRY(hipMemsetAsync(x.out_features, 0, (size_t)x.C * v.N() * sizeof(float), st));
+            continue;
+        }
+        if (!w.img_buffer || !w.geom_buffer || !w.binning_buffer) return named(fn, fail(TGS_ERR_INVALID, "view %d: NULL required pointer", k));
+        const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, w.R, w.geom_buffer, w.binning_buffer, w.img_buffer);
+        launch_feat_fwd(st, fb.s, fb.b, w.width, w.height, v.gx(), (uint32_t)v.T(), P, x.C, x.features, x.out_features);   // (zero-fills the map first)
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(TGS_ERR_HIP, "%s: view %d: %s", fn, k, hipGetErrorString(e));
+    }
+    return TGS_OK;
+}
+
+int tgs_backward_render_views_features_opt(const tgs_options_t* o, void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views,
+                                           const tgs_view_extras_t* extras, const tgs_view_features_t* feats)
+{
+    static const char* fn = "tgs_backward_render_views_features_opt";
+    int C; const float* features;
+    if (int r = check_extras_call(P, n_views, views, extras)) return named(fn, r);
+    if (int r = check_feats_call(P, n_views, views, feats, C, features)) return named(fn, r);
+    if ((n_views > 0 && !streams) || n_streams <= 0) return named(fn, fail(TGS_ERR_INVALID, "bad arguments (streams, n_streams=%d)", n_streams));
+    const Opts opt0 = resolve_options(o, true);
+    for (int k = 0; k < n_views; k++) {
+        tgs_view_extras_t x;
+        tgs_view_features_t f;
+        if (int r = read_extras(extras, k, x)) return named(fn, r);
+        if (int r = read_feats(feats, k, f)) return named(fn, r);
+        BwdArgs fa{};
+        fa.C = f.C; fa.features = f.features; fa.dL_dfeat_map = f.dL_dfeature_map; fa.feat_scratch = f.feature_scratch;
+        const int r = backward_render_impl(view_options(opt0, views[k]), (hipStream_t)streams[k % n_streams], P, views[k], x.dL_dalpha, x.dL_ddepth, x.dz_scratch,
+                                           f.dL_dfeature_map ? &fa : nullptr);
+        if (r < 0) return named(fn, r);
+    }
+    return TGS_OK;
+}
+
+int tgs_backward_batch_features_range(void* stream, int P, int n_views, const tgs_view_t* views, const tgs_view_features_t* feats, float* dL_dfeatures,
+                                      int accumulate, int first, int count)
+{
+    static const char* fn = "tgs_backward_batch_features_range";
+    hipStream_t st = (hipStream_t)stream;
+    int C; const float* features;
+    if (int r = check_feats_call(P, n_views, views, feats, C, features)) return named(fn, r);
+    if (P == 0 || n_views == 0 || count == 0 || !feats || C == 0) return TGS_OK;
+    if (first < 0 || count < 0 || first % PRE_BLOCK != 0 || (long long)first + count > P || ((first + count) % PRE_BLOCK != 0 && first + count != P))
+        return fail(TGS_ERR_INVALID, "%s: Gaussian range [%d, %d + %d) must start and end on multiples of %d (or end at P = %d)", fn, first, first, count, PRE_BLOCK, P);
+    if ((unsigned long long)count * (unsigned)((C + 3) / 4) > 0xffffff00ull) return fail(TGS_ERR_INVALID, "%s: range of %d Gaussians x %d channels is too large for one call", fn, count, C);
+    // the views that take part: a gradient of the map, and instances (R == 0: the per-pixel backward launched nothing and the scratch was not filled)
+    int n_part = 0;
+    for (int k = 0; k < n_views; k++) {
+        tgs_view_features_t x;
+        if (int r = read_feats(feats, k, x)) return named(fn, r);
+        const tgs_view_t& w = views[k];
+        if (!x.dL_dfeature_map) continue;
+        if (!dL_dfeatures) return fail(TGS_ERR_INVALID, "%s: view %d has dL_dfeature_map but dL_dfeatures is NULL", fn, k);
+        if (w.R <= 0) continue;
+        if (!w.geom_buffer || !w.img_buffer || !w.radii || w.width <= 0 || w.height <= 0) return fail(TGS_ERR_INVALID, "%s: view %d: bad sizes or NULL required pointer", fn, k);
+        n_part++;
+    }
+    if (n_part == 0) {                                      // store: the range is defined all the same; accumulate: nothing to add
+        if (!accumulate && dL_dfeatures) HIP_TRY(hipMemsetAsync(dL_dfeatures + (size_t)first * C, 0, (size_t)count * C * sizeof(float), st));
+        return TGS_OK;
+    }
+    FeatViews fv;
+    memset(&fv, 0, sizeof(fv));
+    bool vec = C % 4 == 0 && (uintptr_t)dL_dfeatures % 16 == 0;
+    int acc = accumulate ? 1 : 0;                           // the first launch of the call honours `accumulate`, the later ones add
+    auto flush = [&]() -> int {
+        if (fv.n == 0) return TGS_OK;
+        const int r = stage(st, TGS_STAGE_PREPROCESS_BWD, "feat_bwd_gauss_views", 0, [&] { launch_feat_bwd_gauss_views(st, first, count, C, fv, dL_dfeatures, acc, vec); });
+        fv.n = 0; acc = 1;
+        vec = C % 4 == 0 && (uintptr_t)dL_dfeatures % 16 == 0;
+        return r;
+    };
+    for (int k = 0; k < n_views; k++) {
+        tgs_view_features_t x;
+        if (int r = read_feats(feats, k, x)) return named(fn, r);
+        const tgs_view_t& w = views[k];
+        if (!x.dL_dfeature_map || w.R <= 0) continue;
+        const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, view_args(w), w.R, w.geom_buffer, nullptr, w.img_buffer);
+        FeatView& d = fv.v[fv.n++];
+        d.meta = fb.s.meta; d.radii = w.radii; d.tiles_touched = fb.g.tiles_touched; d.offsets = fb.g.offsets; d.rows = x.feature_scratch;
+        vec = vec && (uintptr_t)x.feature_scratch % 16 == 0;
+        if (fv.n == BATCH_VIEWS)
             if (int r = flush()) return named(fn, r);
     }
     return named(fn, flush());

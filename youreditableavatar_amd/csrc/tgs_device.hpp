@@ -1035,5 +1035,14 @@ struct DepthView {
     const float* view;       // the flat view matrix: d z / d mean = (view[2], view[6], view[10])
 };
 struct DepthViews { int n; DepthView v[BATCH_VIEWS]; };
+// One view of a batch for k_feat_bwd_gauss_views (tgs_feature.hip): where the channel sums of its instances lie (kernel argument)
+struct FeatView {
+    const Meta* meta;
+    const int* radii;
+    const uint32_t* tiles_touched;
+    const uint32_t* offsets;
+    const float* rows;       // the view's feature scratch (k_feat_bwd), C floats per instance slot
+};
+struct FeatViews { int n; FeatView v[BATCH_VIEWS]; };
 
 }  // namespace tgs

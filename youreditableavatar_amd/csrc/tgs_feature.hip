@@ -4,6 +4,7 @@
 //   k_feat_bwd        back to front: the gradient of those sums through alpha_i (added into the slab rows the colour's per-pixel backward has
 //                     written, as k_depth_bwd adds its share) and through features[i, c] (a per-instance scratch row of C floats)
 //   k_feat_bwd_gauss  per Gaussian: sum of its scratch rows, in row order, into dL_dfeatures[i, :]
+//   k_feat_bwd_gauss_views  the same for every view of a batch in one pass (tgs_backward_batch_features_range)
 //
 // tgs_depth.hip is the special case "one channel, the feature is z"; geometry, staging and the pair replay are its (256 threads per tile, one
 // lane per pixel, wave w owns the 8x8-pixel quadrant w, replay_lane / replay_pair_alpha / tile_deepest / geometry_terms / slab_row_add of tgs_replay.hpp).  The feature row of a staged entry
@@ -304,6 +305,79 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_feat_bwd_gauss(int P, int C, cons
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_feat_bwd_gauss_views: k_feat_bwd_gauss for the views of a batch (read the comment of k_depth_bwd_gauss_views in tgs_depth.hip first: the
+// same pass with a row of C floats where dz stands and no matrix).  One lane per (Gaussian, channel quad): Q = ceil(C / 4) neighbouring lanes
+// share a Gaussian, lane q owns channels 4q .. 4q + 3, so a lane carries four sums whatever C is (no array indexed at run time: no scratch
+// memory, and no LDS), a wave's loads of one row step are Q * 16 contiguous bytes per Gaussian and its stores cover whole rows of dL_dfeatures.
+// Per channel: the rows of a view in row order into a sum of the view's own, the views of the chunk in ascending index, then ONE store
+// (accumulate == 0: every row of the range is written, a Gaussian live in no view gets exact zeros) or one read-modify-write (a Gaussian live
+// in no view is left alone) per Gaussian and chunk.  No atomics, a fixed order: two runs give the same bits, and so do the two load widths.
+// Load-latency bound like the depth kernel: the first step of EVERY view of the chunk (radii / tiles_touched / offsets; the Q lanes of a
+// Gaussian read the same words, one request) is issued before any row is read, and a view's rows are fetched four at a time in front of
+// their four additions.  A Gaussian's rows in a view are tiles * C contiguous floats (offsets is a prefix sum, the row stride is C).
+// VEC: C % 4 == 0 and the scratch of every view of the chunk and dL_dfeatures 16-byte aligned (the host checks): one 16-byte access per lane
+// and row; otherwise scalar accesses, the channels behind C - 1 read as 0 and are not stored.  A view's meta word is uniform.
+// ---------------------------------------------------------------------------------------------
+template <bool VEC>
+__device__ __forceinline__ float4 load_quad(const float* __restrict__ p, int n)
+{
+    if (VEC) return *reinterpret_cast<const float4*>(p);
+    return make_float4(p[0], n > 1 ? p[1] : 0.f, n > 2 ? p[2] : 0.f, n > 3 ? p[3] : 0.f);
+}
+__device__ __forceinline__ void add_quad(float4& s, const float4 x) { s.x += x.x; s.y += x.y; s.z += x.z; s.w += x.w; }
+
+template <bool VEC>
+__global__ __launch_bounds__(PRE_BLOCK) void k_feat_bwd_gauss_views(int first, int end, int C, uint32_t Q, const FeatViews fv, float* __restrict__ dL_dfeatures,
+                                                                    int accumulate)
+{
+    const uint32_t t = blockIdx.x * (uint32_t)PRE_BLOCK + threadIdx.x;      // (the host keeps count * Q below 2^32)
+    const uint32_t g = t / Q;
+    if (g >= (uint32_t)(end - first)) return;
+    const int idx = first + (int)g, c0 = 4 * (int)(t - g * Q), nq = C - c0;
+    uint32_t tiles[BATCH_VIEWS], off[BATCH_VIEWS];
+#pragma unroll
+    for (int k = 0; k < BATCH_VIEWS; k++) {
+        tiles[k] = 0; off[k] = 0;
+        if (k < fv.n) {
+            const FeatView& w = fv.v[k];
+            // a rejected frame contributes nothing (and its offsets may point past its capacity: they are not followed)
+            const bool live = !(__builtin_nontemporal_load(&w.meta->error) & META_ERR_CAPACITY) && w.radii[idx] > 0;
+            if (live) { tiles[k] = w.tiles_touched[idx]; off[k] = w.offsets[idx]; }
+        }
+    }
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < BATCH_VIEWS; k++) {
+        if (k < fv.n && tiles[k] > 0) {
+            const float* row = fv.v[k].rows + (size_t)off[k] * C + c0;
+            const uint32_t n = tiles[k];
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+            uint32_t r = 0;
+            for (; r + 4 <= n; r += 4, row += 4 * (size_t)C) {
+                const float4 x0 = load_quad<VEC>(row, nq), x1 = load_quad<VEC>(row + C, nq), x2 = load_quad<VEC>(row + 2 * (size_t)C, nq),
+                             x3 = load_quad<VEC>(row + 3 * (size_t)C, nq);
+                add_quad(s, x0); add_quad(s, x1); add_quad(s, x2); add_quad(s, x3);
+            }
+            for (; r < n; r++, row += C) add_quad(s, load_quad<VEC>(row, nq));
+            add_quad(acc, s);
+            any = true;
+        }
+    }
+    if (!any && accumulate) return;
+    float* o = dL_dfeatures + (size_t)idx * C + c0;
+    if (VEC) {
+        float4 v = acc;
+        if (accumulate) { v = *reinterpret_cast<const float4*>(o); add_quad(v, acc); }
+        *reinterpret_cast<float4*>(o) = v;
+    } else {
+        const float a[4] = {acc.x, acc.y, acc.z, acc.w};
+#pragma unroll
+        for (int c = 0; c < 4; c++) if (c < nq) o[c] = accumulate ? o[c] + a[c] : a[c];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host launchers: one launch per group of FGROUP channels, the narrow kernel for a group of 1 .. 4
 // ---------------------------------------------------------------------------------------------
 // out[C * N] <- 0, then the tiles with instances (at most T workgroups have work)
@@ -332,6 +406,15 @@ void launch_feat_bwd(hipStream_t st, const ImgState& s, const BinState& b, int W
 void launch_feat_bwd_gauss(hipStream_t st, int P, int C, const Meta* meta, const int* radii, const GeomState& g, const float* feat_rows, float* dL_dfeatures, int accumulate)
 {
     hipLaunchKernelGGL(k_feat_bwd_gauss, dim3((unsigned)n_blocks((size_t)P)), dim3(PRE_BLOCK), 0, st, P, C, meta, radii, g, feat_rows, dL_dfeatures, accumulate);
+}
+// Gaussians [first, first + count) of P, the views of one chunk; vec: the 16-byte accesses are allowed (C % 4 == 0, everything 16-byte aligned)
+void launch_feat_bwd_gauss_views(hipStream_t st, int first, int count, int C, const FeatViews& fv, float* dL_dfeatures, int accumulate, bool vec)
+{
+    if (count <= 0 || fv.n <= 0) return;
+    const uint32_t Q = (uint32_t)(C + 3) / 4;
+    const dim3 grid((unsigned)n_blocks((size_t)count * Q)), blk(PRE_BLOCK);
+    if (vec) hipLaunchKernelGGL(k_feat_bwd_gauss_views<true>, grid, blk, 0, st, first, first + count, C, Q, fv, dL_dfeatures, accumulate);
+    else hipLaunchKernelGGL(k_feat_bwd_gauss_views<false>, grid, blk, 0, st, first, first + count, C, Q, fv, dL_dfeatures, accumulate);
 }
 
 }  // namespace tgs

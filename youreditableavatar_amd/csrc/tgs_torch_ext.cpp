@@ -329,4 +329,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("abi_version", []() { return tgs_abi_version(); });
     m.def("compiled_abi_version", []() { return TGS_ABI_VERSION; });      // the header THIS module was compiled against
     m.def("sizeof_view", []() { return sizeof(tgs_view_t); });
+    m.def("sizeof_view_features", []() { return sizeof(tgs_view_features_t); });      // the third per-view array of the whole-batch path, as THIS module sees it
 }

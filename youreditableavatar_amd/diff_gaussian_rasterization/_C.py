@@ -80,6 +80,16 @@ def _load() -> C.CDLL:
     lib.tgs_backward_batch_depth_range.argtypes = [vp, it, it, vp, vp, vp, it, it]
     lib.tgs_backward_depth_opt.restype = it
     lib.tgs_backward_depth_opt.argtypes = lib.tgs_backward_opt.argtypes[:27] + [vp, vp, vp] + [vp] * 9 + [it]
+    # feature channels in the whole-batch path (tgs_view_features_t), and the one-view backward that carries them
+    lib.tgs_sizeof_view_features.restype = C.c_size_t
+    lib.tgs_features_views.restype = it
+    lib.tgs_features_views.argtypes = [vp, it, it, it, vp, vp]
+    lib.tgs_backward_render_views_features_opt.restype = it
+    lib.tgs_backward_render_views_features_opt.argtypes = [vp, vp, it, it, it, vp, vp, vp]
+    lib.tgs_backward_batch_features_range.restype = it
+    lib.tgs_backward_batch_features_range.argtypes = [vp, it, it, vp, vp, vp, it, it, it]
+    lib.tgs_backward_features_opt.restype = it
+    lib.tgs_backward_features_opt.argtypes = lib.tgs_backward_opt.argtypes[:27] + [vp, vp, vp] + [it, vp, vp, vp, vp] + [vp] * 9 + [it]
     lib.tgs_state_field.restype = C.c_int64
     lib.tgs_state_field.argtypes = [vp, C.c_char_p, it, it, it, C.c_int64, it, it, vp, vp, vp, vp, C.c_size_t]
     lib.tgs_set_sort_lds_cap.restype = it
@@ -284,12 +294,15 @@ def rasterize_gaussians_backward_accumulate(background, means3D, radii, colors, 
                                             viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                             geomBuffer, R, binningBuffer, imageBuffer, debug, into, tile_bound: int = 0,
                                             deterministic: Optional[bool] = None, mid_bound: int = 0, *,
-                                            grad_out_alpha: Optional[torch.Tensor] = None, grad_out_depth: Optional[torch.Tensor] = None):
+                                            grad_out_alpha: Optional[torch.Tensor] = None, grad_out_depth: Optional[torch.Tensor] = None,
+                                            grad_out_features: Optional[torch.Tensor] = None, features: Optional[torch.Tensor] = None):
     """Multi-view extension (tgs_backward_accumulate): parameter gradients are ADDED into the fp32 tensors of ``into``
     (keys: means3D, opacities, and sh|colors_precomp, scales+rotations|cov3D_precomp; contiguous, on the device).
     Returns dL_dmeans2D[P,3], the only per-view gradient.  ``grad_out_alpha`` / ``grad_out_depth`` ([1,H,W]): upstream gradients of the
     frame's accumulated alpha / expected depth as well (tgs_backward_depth_opt with accumulate = 1; the dz scratch of R floats is
-    allocated here); both None: today's call (tgs_backward_opt), bit for bit."""
+    allocated here); both None: today's call (tgs_backward_opt), bit for bit.  ``grad_out_features`` ([C,H,W]) with ``features`` ([P,C],
+    float32, 1 <= C <= 16): the upstream gradient of the frame's feature map as well (tgs_backward_features_opt with accumulate = 1; the
+    scratch of R * C floats is allocated here); dL/d features is ADDED into ``into["features"]`` ([P,C]), which is required then."""
     dev = _require_gpu(means3D)
     P = int(means3D.size(0))
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
@@ -323,7 +336,21 @@ def rasterize_gaussians_backward_accumulate(background, means3D, radii, colors, 
             dA, dD = _dev_f32(grad_out_alpha, dev, "grad_out_alpha"), _dev_f32(grad_out_depth, dev, "grad_out_depth")
             dz = torch.empty((max(int(R), 1),), dtype=torch.float32, device=dev) if dD is not None else None
             extras = [_p(dA), _p(dD), _p(dz)]
-        r = (_lib.tgs_backward_depth_opt if extras else _lib.tgs_backward_opt)(
+        fn = _lib.tgs_backward_depth_opt if extras else _lib.tgs_backward_opt
+        if grad_out_features is not None:
+            F = _dev_f32(features, dev, "features")
+            if F is None or F.dim() != 2 or int(F.size(0)) != P or not 1 <= int(F.size(1)) <= FEATURE_MAX_CHANNELS:
+                raise RuntimeError(f"grad_out_features needs features of shape [P,C], 1 <= C <= {FEATURE_MAX_CHANNELS}")
+            Cf = int(F.size(1))
+            if grad_out_features.numel() != Cf * H * W:
+                raise RuntimeError("grad_out_features must have C*H*W elements ([C,H,W])")
+            if into.get("features") is None:
+                raise RuntimeError("grad_out_features: into[\"features\"] ([P,C]) is required")
+            dF = _dev_f32(grad_out_features, dev, "grad_out_features")
+            fscratch = torch.empty((max(int(R), 1) * Cf,), dtype=torch.float32, device=dev)
+            extras = (extras or [None, None, None]) + [Cf, _p(F), _p(dF), _p(fscratch), dst("features", (P, Cf))]
+            fn = _lib.tgs_backward_features_opt
+        r = fn(
             C.byref(opt), 1, torch.cuda.current_stream(dev).cuda_stream, P, int(degree), M, int(R), _p(t["bg"]), W, H, _p(t["means"]), _p(t["sh"]), _p(t["colors"]),
             _p(t["scales"]), float(scale_modifier), _p(t["rots"]), _p(t["cov"]), _p(t["view"]), _p(t["proj"]), _p(t["campos"]),
             float(tan_fovx), float(tan_fovy), radii.contiguous().data_ptr(), geomBuffer.data_ptr(), binningBuffer.data_ptr(),
@@ -369,6 +396,25 @@ def ViewExtrasArray(n: int):
     arr = (_ViewExtrasT * n)()
     for x in arr:
         x.struct_size = C.sizeof(_ViewExtrasT)
+    return arr
+
+
+class _ViewFeaturesT(C.Structure):
+    """tgs_view_features_t (include/tgs_raster.h): the feature map and its gradient of one view, beside its tgs_view_t and tgs_view_extras_t"""
+    _fields_ = [("struct_size", C.c_uint32), ("C", C.c_int32), ("features", C.c_void_p), ("out_features", C.c_void_p),
+                ("dL_dfeature_map", C.c_void_p), ("feature_scratch", C.c_void_p)]
+
+
+if _lib.tgs_sizeof_view_features() != C.sizeof(_ViewFeaturesT) or _ext.sizeof_view_features() != C.sizeof(_ViewFeaturesT):
+    raise ImportError(f"tgs_view_features_t: the library says {_lib.tgs_sizeof_view_features()} bytes, this binding declares {C.sizeof(_ViewFeaturesT)} "
+                      "-- a stale library or binding")
+
+
+def ViewFeaturesArray(n: int):
+    """n zeroed tgs_view_features_t with struct_size set (C = 0 and every pointer NULL: nothing asked of any view)"""
+    arr = (_ViewFeaturesT * n)()
+    for x in arr:
+        x.struct_size = C.sizeof(_ViewFeaturesT)
     return arr
 
 
@@ -426,6 +472,35 @@ def backward_batch_depth_raw(stream, P, views, extras, n_views, dL_dmean3D, firs
     [first, first + count) -- behind the backward_batch_raw call of the same range, on the same stream."""
     r = _lib.tgs_backward_batch_depth_range(stream, int(P), int(n_views), C.cast(views, C.c_void_p), C.cast(extras, C.c_void_p), dL_dmean3D,
                                             int(first), int(P - first if count is None else count))
+    if r < 0:
+        raise _err(int(r))
+
+
+def features_views(stream_handles, P, views, feats, n_views) -> None:
+    """tgs_features_views: the feature map of every view into feats[k].out_features; ``stream_handles``: as for ``outputs_views``, the streams
+    the views' k_render_fwd ran on."""
+    arr = (C.c_void_p * len(stream_handles))(*stream_handles)
+    r = _lib.tgs_features_views(arr, len(stream_handles), int(P), int(n_views), C.cast(views, C.c_void_p), C.cast(feats, C.c_void_p))
+    if r < 0:
+        raise _err(int(r))
+
+
+def backward_render_views_features(stream_handles, P, views, extras, feats, n_views, opt: Optional[_OptionsT] = None) -> None:
+    """tgs_backward_render_views_features_opt: backward_render_views_extras (``extras`` may be None) with feats[k].dL_dfeature_map entering
+    view k's per-pixel backward behind the depth's share; the channel sums stay in feats[k].feature_scratch."""
+    arr = (C.c_void_p * len(stream_handles))(*stream_handles)
+    r = _lib.tgs_backward_render_views_features_opt(C.byref(opt) if opt is not None else None, arr, len(stream_handles), int(P), int(n_views),
+                                                    C.cast(views, C.c_void_p), C.cast(extras, C.c_void_p) if extras is not None else None,
+                                                    C.cast(feats, C.c_void_p) if feats is not None else None)
+    if r < 0:
+        raise _err(int(r))
+
+
+def backward_batch_features_raw(stream, P, views, feats, n_views, dL_dfeatures, accumulate, first: int = 0, count: Optional[int] = None) -> None:
+    """tgs_backward_batch_features_range: dL/d features of all views, stored (``accumulate`` false) or added into dL_dfeatures (a device
+    pointer, [P,C]) for Gaussians [first, first + count) -- on the stream of the backward_batch_raw call of the same range."""
+    r = _lib.tgs_backward_batch_features_range(stream, int(P), int(n_views), C.cast(views, C.c_void_p), C.cast(feats, C.c_void_p), dL_dfeatures,
+                                               1 if accumulate else 0, int(first), int(P - first if count is None else count))
     if r < 0:
         raise _err(int(r))
 

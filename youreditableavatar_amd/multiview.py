@@ -475,23 +475,38 @@ def _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_b
     return _Call(settings, V, P, H, W, D, M, precomp, dsh_plane, params, colors_precomp, ranges)
 
 
+def _check_features(features, c: _Call) -> int:
+    """``run_views(features=)``: [P, C] float32, contiguous, on the model's device, 1 <= C <= 16; with requires_grad a leaf with an allocated
+    ``.grad`` of the same shape (the rule of the parameters) -> C"""
+    dev = c.params["means3D"].device
+    if not (torch.is_tensor(features) and features.dim() == 2 and int(features.size(0)) == c.P and features.dtype == torch.float32 and
+            features.device == dev and features.is_contiguous() and 1 <= int(features.size(1)) <= _C.FEATURE_MAX_CHANNELS):
+        raise RuntimeError(f"run_views: features must be a contiguous float32 tensor [P,C] on the model's device, 1 <= C <= {_C.FEATURE_MAX_CHANNELS}")
+    if features.requires_grad and not (features.is_leaf and features.grad is not None and features.grad.shape == features.shape and
+                                       features.grad.dtype == torch.float32 and features.grad.device == dev and features.grad.is_contiguous()):
+        raise RuntimeError("run_views: features that require a gradient must be a leaf with an allocated contiguous .grad [P,C] (see FlatGradients)")
+    return int(features.size(1))
+
+
 def _upstream_checked(dL: torch.Tensor, c: _Call, require_gpu: bool = True) -> torch.Tensor:
     if not torch.is_tensor(dL) or dL.dtype != torch.float32 or (require_gpu and not dL.is_cuda) or tuple(dL.shape[-3:]) != (3, c.H, c.W):
         raise RuntimeError("upstream must return a float32 GPU tensor [V,3,H,W] or [3,H,W]")
     return dL.contiguous()
 
 
-def _upstream_extras_checked(ret, c, names: Sequence[str], per_view: bool, require_gpu: bool = True) -> tuple:
-    """What an upstream callable returned when ``run_views`` handed it the maps ``names`` (of "alpha", "depth", in that order):
+def _upstream_extras_checked(ret, c, names: Sequence[str], per_view: bool, require_gpu: bool = True, channels: Optional[dict] = None) -> tuple:
+    """What an upstream callable returned when ``run_views`` handed it the maps ``names`` (of "alpha", "depth", "features", in that order):
     a tuple (dL/d images, dL/d map for every name), any of the latter None -> (dL, [gradient or None per name]), contiguous.
+    ``channels``: the channel count of a map by its name (absent: 1, which alpha and depth have; "features": the C of the call).
     ``c`` needs H, W and V only; ``require_gpu=False`` checks everything but the device (host tests)."""
     want = "(dL_dimages, " + ", ".join("dL_d" + n for n in names) + ")"
     if not isinstance(ret, (tuple, list)) or len(ret) != 1 + len(names):
         raise RuntimeError(f"upstream must return the tuple {want} when run_views returns {' and '.join(names)} (an entry may be None, the first may not)")
     dL = _upstream_checked(ret[0], c, require_gpu)
-    shapes = [(1, c.H, c.W)] + ([] if per_view else [(c.V, 1, c.H, c.W)])
     out = []
     for name, g in zip(names, ret[1:]):
+        ch = int((channels or {}).get(name, 1))
+        shapes = [(ch, c.H, c.W)] + ([] if per_view else [(c.V, ch, c.H, c.W)])
         if g is not None:
             if not torch.is_tensor(g) or g.dtype != torch.float32 or (require_gpu and not g.is_cuda) or tuple(g.shape) not in shapes:
                 raise RuntimeError(f"upstream: dL_d{name} must be None or a float32 GPU tensor " + " or ".join(str(list(sh)) for sh in shapes[::-1]))
@@ -501,7 +516,7 @@ def _upstream_extras_checked(ret, c, names: Sequence[str], per_view: bool, requi
 
 
 def _of_view(dL: torch.Tensor, v: int) -> torch.Tensor:
-    """View v's part of an upstream gradient ([3,H,W] / [1,H,W]: the same for every view; None stays None)."""
+    """View v's part of an upstream gradient ([3,H,W] / [1,H,W] / [C,H,W]: the same for every view; None stays None)."""
     return dL if (dL is None or dL.dim() == 3) else dL[v]
 
 
@@ -574,7 +589,8 @@ class SyncFreeBatch:
                   rotations: torch.Tensor, upstream_batch: Optional[Callable[[torch.Tensor], torch.Tensor]], accumulate: bool = True,
                   colors_precomp: Optional[torch.Tensor] = None,
                   upstream_view: Optional[Callable[[int, torch.Tensor], torch.Tensor]] = None, grad_chunks: int = 1,
-                  on_chunk: Optional[Callable[[int, int], None]] = None, return_alpha: bool = False, return_depth: bool = False):
+                  on_chunk: Optional[Callable[[int, int], None]] = None, return_alpha: bool = False, return_depth: bool = False,
+                  features: Optional[torch.Tensor] = None):
         """Renders the views described by ``settings`` (GaussianRasterizationSettings, same image size, SH degree and scale
         modifier) of one Gaussian model (leaf parameters with allocated ``.grad``, SH colours, scales + rotations), calls
         ``upstream_batch(images[V,3,H,W]) -> dL/d images`` ([V,3,H,W], or [3,H,W] for all views) ONCE, and adds the
@@ -605,9 +621,30 @@ class SyncFreeBatch:
         ``(dL/d images, dL/d alpha, dL/d depth)`` in the same order: float32 GPU tensors [V,1,H,W] or [1,H,W] (all views) from the batch
         callable, [1,H,W] from the view callable.  Any of the extra gradients may be None: that map took no part in the loss and no kernel
         runs for it.  Both flags False (the default): nothing changes -- the same calls, buffers and return value as before.
-        ``run`` / ``rasterize_accumulate`` / ``DeferredBackward`` do not carry these outputs; feature channels are not part of this path."""
-        names = [n for n, on in (("alpha", return_alpha), ("depth", return_depth)) if on]
+
+        ``features`` [P,C] (float32, contiguous, on the model's device, 1 <= C <= 16; anything else raises RuntimeError): per-Gaussian
+        feature channels -- normals, keep / edit masks, labels: properties of the model, so one tensor for all views -- composited like the
+        colour, the output of ``rasterize_gaussians(features=)`` in the whole-batch path: feature_map[v, c] = sum_i T_i alpha_i features[i, c]
+        over the pairs view v's colour frame blended (signed, not clamped, not normalised).  ``run_views`` then returns
+        ``(images, alpha if asked, depth if asked, feature_map[V,C,H,W])``, the upstream callables receive the feature map as the LAST
+        positional argument -- ``upstream_batch(images, ..., fmap)``, ``upstream_view(v, image, ..., fmap_v[C,H,W])`` -- and return its gradient
+        as the last entry of the tuple: [V,C,H,W] or [C,H,W] (all views) from the batch callable, [C,H,W] from the view callable, or None:
+        the map took no part in that view's loss, no feature kernel runs for the view and it adds nothing to dL/d features.  If
+        ``features.requires_grad`` it must be a leaf with an allocated ``.grad`` [P,C], the rule of the parameters, and dL/d features of all
+        views is stored there (``accumulate=False``) or added; if not, ``.grad`` is not touched and only the through-alpha share of the
+        gradient flows, to opacities, means, scales and rotations.  Memory: once a view has a feature gradient the pool holds a scratch of
+        V * capacity * C * 4 bytes (capacity: the batch's bound on the tile instances of a view) -- large at C = 16: 8 views of a million
+        instances are 512 MB.  ``features=None`` (the default) is the step of before: the same calls, buffers and return value.
+
+        ``run`` / ``rasterize_accumulate`` / ``DeferredBackward`` carry none of these outputs (alpha, depth, feature channels); per-view
+        features [V,P,C], more than 16 channels and half precision are not part of this path either."""
+        xnames = [n for n, on in (("alpha", return_alpha), ("depth", return_depth)) if on]      # the maps of tgs_view_extras_t
         c = _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_batch, upstream_view, colors_precomp, grad_chunks)
+        Cf = _check_features(features, c) if features is not None else 0
+        names = xnames + (["features"] if Cf else [])      # every extra map, in the order of the return value and of the callables' tuples
+        F = features.detach() if Cf else None
+        fgrad = features.grad if (Cf and features.requires_grad) else None
+        checked = lambda ret, per_view: _upstream_extras_checked(ret, c, names, per_view=per_view, channels={"features": Cf})
         V, P, D, M, precomp = c.V, c.P, c.D, c.M, c.precomp
         dev = means3D.device
         cap = self.capacity()
@@ -615,34 +652,37 @@ class SyncFreeBatch:
             if not accumulate:
                 for t in c.params.values():
                     t.grad.zero_()
+                if fgrad is not None:
+                    fgrad.zero_()
             states = [self._render_view(c, v) for v in range(V)]
             images = torch.stack([s[1] for s in states])
-            maps = [torch.stack([self._map_of(c, name, states[v]) for v in range(V)]) for name in names]
+            maps = [torch.stack([self._map_of(c, name, states[v], F) for v in range(V)]) for name in names]
             extra = [None] * V                               # per view: [dL/d map or None, per name]
             if not names:
                 dL = upstream_batch(images) if upstream_batch is not None else torch.stack([upstream_view(v, images[v]) for v in range(V)])
             elif upstream_batch is not None:
-                dL, gs = _upstream_extras_checked(upstream_batch(images, *maps), c, names, per_view=False)
+                dL, gs = checked(upstream_batch(images, *maps), False)
                 extra = [[_of_view(g, v) for g in gs] for v in range(V)]
             else:
-                rets = [_upstream_extras_checked(upstream_view(v, images[v], *[m[v] for m in maps]), c, names, per_view=True) for v in range(V)]
+                rets = [checked(upstream_view(v, images[v], *[m[v] for m in maps]), True) for v in range(V)]
                 if any(r[0].dim() != 3 for r in rets):
                     raise RuntimeError("upstream_view must return [3,H,W]")
                 dL, extra = torch.stack([r[0] for r in rets]), [r[1] for r in rets]
             gcol = torch.empty((V, P, 3), dtype=torch.float32, device=dev) if precomp else None
             scratch = torch.empty_like(shs) if c.dsh_plane else None
-            self.viewspace_grads = torch.stack([self._backward_view(c, v, states[v], _of_view(dL, v), gcol, scratch, names, extra[v]) for v in range(V)])
+            self.viewspace_grads = torch.stack([self._backward_view(c, v, states[v], _of_view(dL, v), gcol, scratch, names, extra[v], F, fgrad) for v in range(V)])
             self.color_grads = gcol
             self._learn(max(s[0] for s in states))
             for first, count in (c.ranges if on_chunk is not None else []):
                 on_chunk(first, count)
             return (images, *maps) if names else images
 
-        pool = self._pooled(c, cap, names)
-        self._fill_views(c, pool)
+        pool = self._pooled(c, cap, names, Cf)
+        self._fill_views(c, pool, F)
         arr, images, gcol = pool["arr"], pool["images"], pool["gcol"]
-        xarr, maps = pool.get("xarr"), [pool[name] for name in names]
+        xarr, farr, maps = pool.get("xarr"), pool.get("farr"), [pool[name] for name in names]
         with_depth = False                                  # a view has a depth gradient: the z-path pass follows every range of the per-Gaussian pass
+        with_feat = False                                   # a view has a feature gradient: dL/d features follows every range as well
         main = torch.cuda.current_stream(dev)
         lanes = _lanes(main, min(self.streams, V))
         with torch.cuda.device(dev):
@@ -655,17 +695,21 @@ class SyncFreeBatch:
                                  scales.data_ptr(), settings[0].scale_modifier, rotations.data_ptr(), arr, V, prefiltered=settings[0].prefiltered, opt=self.options)
             finally:
                 _C.set_render_streams([])
-            if names:
+            if xnames:
                 # the maps read what k_render_fwd wrote: on the lane each view composited on, behind it without an event
                 _C.outputs_views([st.cuda_stream for st in ren_lanes], P, arr, xarr, V)
+            if Cf:
+                _C.features_views([st.cuda_stream for st in ren_lanes], P, arr, farr, V)
             if upstream_view is None:
                 _join(lanes)
                 ready = [torch.cuda.Event()]                # (the verdicts are in pinned memory once the scans have run: tgs_view_t.host_meta)
                 ready[0].record(main)
                 if names:
-                    dL, gs = _upstream_extras_checked(upstream_batch(images, *maps), c, names, per_view=False)
+                    dL, gs = checked(upstream_batch(images, *maps), False)
                     for v in range(V):
-                        with_depth |= self._set_extra_grads(pool, v, names, [_of_view(g, v) for g in gs])
+                        gv = [_of_view(g, v) for g in gs]
+                        with_depth |= bool(xnames) and self._set_extra_grads(pool, v, names, gv)
+                        with_feat |= bool(Cf) and self._set_feature_grad(pool, v, gv[-1])
                     self._keep = gs                              # (alive until the next batch)
                 else:
                     dL = _upstream_checked(upstream_batch(images), c)
@@ -684,7 +728,7 @@ class SyncFreeBatch:
                     with torch.cuda.stream(st):
                         for v in range(l, V, len(ren_lanes)):
                             if names:
-                                g, gs = _upstream_extras_checked(upstream_view(v, images[v], *[m[v] for m in maps]), c, names, per_view=True)
+                                g, gs = checked(upstream_view(v, images[v], *[m[v] for m in maps]), True)
                             else:
                                 g, gs = _upstream_checked(upstream_view(v, images[v]), c), []
                             if g.dim() != 3:
@@ -695,10 +739,13 @@ class SyncFreeBatch:
                 for v, g, gs in dLs:
                     arr[v].dL_dpix = g.data_ptr()
                     if names:
-                        with_depth |= self._set_extra_grads(pool, v, names, gs)
+                        with_depth |= bool(xnames) and self._set_extra_grads(pool, v, names, gs)
+                        with_feat |= bool(Cf) and self._set_feature_grad(pool, v, gs[-1])
                 self._keep = dLs                                 # (alive until the next batch)
             bwd_lanes = [st.cuda_stream for st in (lanes if upstream_view is None else ren_lanes)]
-            if names:
+            if Cf:                                          # colour + alpha, then depth, then the features' share, per view on its lane
+                _C.backward_render_views_features(bwd_lanes, P, arr, xarr, farr, V, opt=self.options)
+            elif names:
                 _C.backward_render_views_extras(bwd_lanes, P, arr, xarr, V, opt=self.options)
             else:
                 _C.backward_render_views(bwd_lanes, P, arr, V, opt=self.options)
@@ -715,6 +762,8 @@ class SyncFreeBatch:
                                       dsh_plane_stride=c.dsh_plane)
                 if with_depth:                              # dz . (third row of each view's transform), behind the range's stored / accumulated dL_dmeans3D
                     _C.backward_batch_depth_raw(main.cuda_stream, P, arr, xarr, V, means3D.grad.data_ptr(), g0, gcount)
+                if fgrad is not None and (with_feat or not accumulate):      # (store mode without any gradient: the range's rows are zeroed)
+                    _C.backward_batch_features_raw(main.cuda_stream, P, arr, farr, V, fgrad.data_ptr(), accumulate, g0, gcount)
                 if eager:
                     on_chunk(g0, gcount)
         self.viewspace_grads = pool["g2d"]
@@ -729,12 +778,12 @@ class SyncFreeBatch:
             for v in redo:
                 images[v].copy_(states[v][1])
                 for name, m in zip(names, maps):
-                    m[v].copy_(self._map_of(c, name, states[v]))
+                    m[v].copy_(self._map_of(c, name, states[v], F))
             gs2 = [None] * len(names)
             if upstream_view is not None:
                 dL2 = None
             elif names:                                     # the gradient images depend on the re-rendered frames (and maps)
-                dL2, gs2 = _upstream_extras_checked(upstream_batch(images, *maps), c, names, per_view=False)
+                dL2, gs2 = checked(upstream_batch(images, *maps), False)
             else:
                 dL2 = upstream_batch(images).contiguous()
             scratch = torch.empty_like(shs) if c.dsh_plane else None
@@ -743,10 +792,10 @@ class SyncFreeBatch:
                 if dL2 is not None:
                     g = _of_view(dL2, v)
                 elif names:
-                    g, gs = _upstream_extras_checked(upstream_view(v, images[v], *[m[v] for m in maps]), c, names, per_view=True)
+                    g, gs = checked(upstream_view(v, images[v], *[m[v] for m in maps]), True)
                 else:
                     g = _upstream_checked(upstream_view(v, images[v]), c)
-                pool["g2d"][v].copy_(self._backward_view(c, v, states[v], g, gcol, scratch, names, gs))
+                pool["g2d"][v].copy_(self._backward_view(c, v, states[v], g, gcol, scratch, names, gs, F, fgrad))
                 seen = max(seen, states[v][0])
         if on_chunk is not None and not eager:
             for first, count in c.ranges:     # the same calls in the same order as on a rank that had nothing to render again (collectives must pair up)
@@ -754,12 +803,14 @@ class SyncFreeBatch:
         self._learn(seen, [max(counts) for counts in zip(*(tiles for _R, _rejected, tiles in rows))])
         return (images, *maps) if names else images
 
-    def _pooled(self, c: _Call, cap: int, names: Sequence[str] = ()) -> dict:
+    def _pooled(self, c: _Call, cap: int, names: Sequence[str] = (), Cf: int = 0) -> dict:
         """The batch's buffers, one tensor per kind for all views, and its tgs_view_t array: kept while the shapes and the capacity stay.
-        ``names`` (of "alpha", "depth"): the extra maps asked for -- their buffers [V,1,H,W], the depth's dz scratch [V, cap] and the
-        tgs_view_extras_t array exist only then, and a call without them keeps the key (and the pool) it always had."""
+        ``names`` (of "alpha", "depth", "features"): the extra maps asked for -- their buffers [V,1,H,W], the depth's dz scratch [V, cap] and
+        the tgs_view_extras_t array exist only then, and a call without them keeps the key (and the pool) it always had.  ``Cf`` > 0 (with
+        "features" in ``names``): the feature map's buffer [V,Cf,H,W] and the tgs_view_features_t array; the feature scratch [V, cap * Cf]
+        comes with the first feature gradient (_set_feature_grad)."""
         dev = c.params["means3D"].device
-        key = (c.P, c.H, c.W, c.V, c.M, cap, dev, c.precomp) + ((tuple(names),) if names else ())
+        key = (c.P, c.H, c.W, c.V, c.M, cap, dev, c.precomp) + ((tuple(names),) if names else ()) + ((Cf,) if Cf else ())
         if self._pool is None or self._pool["key"] != key:
             V, P = c.V, c.P
             gb, bb, ib = _C.state_sizes(P, c.W, c.H, not c.precomp, True, cap)
@@ -769,13 +820,16 @@ class SyncFreeBatch:
                               binning=z(V, al(bb), dt=torch.uint8), img=z(V, al(ib), dt=torch.uint8), sizes=(gb, bb, ib), arr=_C.ViewArray(V),
                               gcol=z(V, P, 3) if c.precomp else None,
                               host=torch.empty((V, _C.META_BYTES), dtype=torch.uint8, pin_memory=True))
-            if names:
-                self._pool.update({name: z(V, 1, c.H, c.W) for name in names}, xarr=_C.ViewExtrasArray(V))
+            xnames = [name for name in names if name != "features"]
+            if Cf:
+                self._pool.update(features=z(V, Cf, c.H, c.W), farr=_C.ViewFeaturesArray(V), fscratch=None, fscratch_shape=(V, cap * Cf))
+            if xnames:
+                self._pool.update({name: z(V, 1, c.H, c.W) for name in xnames}, xarr=_C.ViewExtrasArray(V))
                 if "depth" in names:
                     self._pool["dz"] = z(V, cap)            # one float per instance slot and view (tgs_view_extras_t.dz_scratch)
         return self._pool
 
-    def _fill_views(self, c: _Call, pool: dict) -> None:
+    def _fill_views(self, c: _Call, pool: dict, F: Optional[torch.Tensor] = None) -> None:
         """The pooled tgs_view_t array: each view's camera, its slices of the pooled buffers and its grid bounds (dL_dpix comes later)."""
         gb, bb, ib = pool["sizes"]
         tcap = self.tile_capacity()
@@ -799,6 +853,10 @@ class SyncFreeBatch:
                 x.out_alpha = pool["alpha"][v].data_ptr() if "alpha" in pool else None
                 x.out_depth = pool["depth"][v].data_ptr() if "depth" in pool else None
                 x.dL_dalpha = x.dL_ddepth = x.dz_scratch = None
+            if "farr" in pool:                              # the model's features and the map's slice; the gradient comes later (_set_feature_grad)
+                f = pool["farr"][v]
+                f.C, f.features, f.out_features = int(F.size(1)), F.data_ptr(), pool["features"][v].data_ptr()
+                f.dL_dfeature_map = f.feature_scratch = None
 
     @staticmethod
     def _set_extra_grads(pool: dict, v: int, names: Sequence[str], grads: Sequence[Optional[torch.Tensor]]) -> bool:
@@ -811,11 +869,27 @@ class SyncFreeBatch:
         return gD is not None
 
     @staticmethod
-    def _map_of(c: _Call, name: str, state: tuple) -> torch.Tensor:
-        """The alpha / depth map [1,H,W] of a view from _render_view (the synchronous frame's state)."""
+    def _set_feature_grad(pool: dict, v: int, g: Optional[torch.Tensor]) -> bool:
+        """View v's upstream gradient [C,H,W] of the feature map (or None) into the pooled tgs_view_features_t array; -> whether it has one.
+        The scratch [V, cap * C] (C floats per instance slot and view) is allocated with the first gradient the pool sees."""
+        f = pool["farr"][v]
+        if g is None:
+            f.dL_dfeature_map = f.feature_scratch = None
+            return False
+        if pool["fscratch"] is None:
+            pool["fscratch"] = torch.empty(pool["fscratch_shape"], dtype=torch.float32, device=g.device)
+        f.dL_dfeature_map, f.feature_scratch = g.data_ptr(), pool["fscratch"][v].data_ptr()
+        return True
+
+    @staticmethod
+    def _map_of(c: _Call, name: str, state: tuple, F: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The alpha / depth map [1,H,W] or the feature map [C,H,W] (of the features ``F``) of a view from _render_view (the synchronous
+        frame's state)."""
         R, _color, _radii, geom, binning, img = state[:6]
         if name == "alpha":
             return _C.alpha_from_state(img, c.H, c.W)
+        if name == "features":
+            return _C.features_from_state(geom, binning, img, F, c.P, c.H, c.W, int(R))
         return _C.depth_from_state(geom, binning, img, c.P, c.H, c.W, int(R))
 
     def _render_view(self, c: _Call, v: int) -> tuple:
@@ -826,14 +900,20 @@ class SyncFreeBatch:
                                       e if c.precomp else p["sh"].detach(), c.D, rs.campos, rs.prefiltered, rs.debug, pruning=self._pruning)
 
     def _backward_view(self, c: _Call, v: int, state: tuple, dL: torch.Tensor, gcol: Optional[torch.Tensor],
-                       scratch: Optional[torch.Tensor], names: Sequence[str] = (), extra: Optional[Sequence] = None) -> torch.Tensor:
+                       scratch: Optional[torch.Tensor], names: Sequence[str] = (), extra: Optional[Sequence] = None,
+                       F: Optional[torch.Tensor] = None, fgrad: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The backward of a view from _render_view, in place: adds into the parameters' .grad (per-view colours: this view's alone, in gcol[v])
         and returns dL/d means2D.  The one-view kernel writes dL_dsh by rows: a level-major .grad gets it through the row-major ``scratch``.
-        ``names`` / ``extra``: the view's upstream gradients [1,H,W] (or None) of the extra maps."""
+        ``names`` / ``extra``: the view's upstream gradients [1,H,W] / [C,H,W] (or None) of the extra maps; with one of the feature map, ``F``
+        are the features and dL/d features is added into ``fgrad`` (None: features that need no gradient -- it goes to a buffer of its own
+        that is dropped, the through-alpha share still reaches the parameters)."""
         rs, p, e = c.settings[v], c.params, torch.Tensor([])
         R, _color, radii, geom, binning, img = state[:6]
         kw = {"grad_out_" + n: g for n, g in zip(names, extra or ()) if g is not None}
         into = {name: t.grad for name, t in p.items()}
+        if "grad_out_features" in kw:
+            kw["features"] = F
+            into["features"] = fgrad if fgrad is not None else torch.zeros_like(F)
         if c.precomp:
             gcol[v].zero_()
             into["colors_precomp"] = gcol[v]
