@@ -254,7 +254,8 @@ int tgs_backward_render_alpha_opt(const tgs_options_t* opt, void* stream, int P,
  *                     to dL_dopacity, dL_dconic, dL_dmean2D and on through the unchanged per-Gaussian pass;
  *   dL_dcolor / dL_dsh get nothing from it.
  * Part of the whole-batch path since tgs_view_extras_t (below, behind tgs_backward_batch_range_planes): alpha and depth of every view of a
- * batch and their gradients, beside the frozen tgs_view_t.  No median / mode depth; normals and feature channels are tgs_features below.
+ * batch and their gradients, beside the frozen tgs_view_t.  The median depth of one view is tgs_median below; the whole-batch path has no
+ * median depth, and there is no mode depth anywhere; normals and feature channels are tgs_features below.
  *
  * tgs_depth: out_depth[H*W] of a finished forward (any of the forward entry points; P, width, height as given to it, R as it returned or was
  * given), enqueued on `stream`: a pass of its own over the frame's state, the render kernels are not involved.  P == 0 or R == 0: nothing
@@ -299,6 +300,7 @@ int tgs_backward_depth_opt(const tgs_options_t* opt, int accumulate, void* strea
  * it).  What is still NOT part of the whole-batch path: median / mode depth, more than 16 channels, half-precision features, and
  * tgs_backward_batch without ranges (the features' per-Gaussian pass exists as tgs_backward_batch_features_range only; first = 0, count = P
  * is the whole model).
+ * (The median depth of ONE view exists: tgs_median below.)
  *
  * tgs_features: out[C*H*W] of a finished forward (P, width, height as given to it, R as it returned or was given), enqueued on `stream`: a
  * pass of its own over the frame's state, the render kernels are not involved.  P == 0 or R == 0: nothing was blended, nothing is launched
@@ -324,6 +326,37 @@ int tgs_backward_features_opt(const tgs_options_t* opt, int accumulate, void* st
                               float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                               float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                               int debug);
+
+/* ---- median depth and surface index (an extension: the depth of the front surface and the splat that is that surface) ----
+ * Definition: take the (pixel, entry) pairs the colour frame blended, front to back -- the lists, the two cut-offs (power > 0,
+ * alpha < 1/255), the min(0.99, .) clamp and the n_contrib bound of tgs_depth.  Start from T = 1 and set T <- T * (1 - alpha_i) after each
+ * blended pair, in fp32.  The median entry m(p) of pixel p is the FIRST blended pair after which T < 0.5 (strict).
+ *     median_depth[H*W]  = z_m, the view-space z of that entry's mean (the value the forward stores and sorts by); not weighted, not normalised
+ *     median_index[H*W]  = the Gaussian index of that entry, int32 in 0 .. P-1
+ *     median_pos[H*W]    = its 1-based position in the tile's sorted list (int32; what tgs_backward_median reads: nothing is replayed there)
+ * A pixel whose transmittance never falls below 0.5 has median_depth 0, median_index -1 and median_pos 0, exactly: accumulated alpha <= 0.5,
+ * a tile without instances, a frame without visible Gaussians, a frame the sync-free forward rejected, an empty model.  Termination plays no
+ * part (T < 1e-4 lies far behind T < 0.5).  Expected depth (tgs_depth) averages everything along the ray and lands between two surfaces at
+ * a silhouette; the median is a point ON the front surface, and median_index says which splat (and so which mesh face, which group) it is.
+ * Gradient: median_depth is piecewise constant in every alpha; its only derivative is d median_depth(p) / d z_m(p) = 1.  Under an upstream
+ * g[H*W]: dL/dz_i = sum over the pixels p with m(p) = i of g(p), which reaches dL_dmean3D through the third row of the view transform
+ * (m[2], m[6], m[10]) as the z-path of tgs_depth does.  Opacities, mean2D, scales, rotations, colours and SH get NOTHING from it: a loss on
+ * the median depth moves positions; the expected depth is the one that moves opacities.  median_index is an integer output without a gradient.
+ * One view only: the *_views entry points have no median.  No quantile other than one half.
+ *
+ * tgs_median: the three maps of a finished forward (any of the forward entry points; P, width, height as given to it, R as it returned or
+ * was given), enqueued on `stream`: the maps are filled with 0 / -1 / 0, then one pass over the frame's state writes the pixels that have a
+ * median entry.  P == 0 or R == 0: nothing was blended, nothing is launched and the maps are not written (the caller fills them). */
+int tgs_median(void* stream, int P, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
+               float* out_depth, int32_t* out_index, int32_t* out_pos);
+
+/* ADDS the median's share into a dL_dmean3D[P*3] that tgs_backward* has already written or accumulated on the same stream -- a call of its
+ * own behind the main backward.  median_pos: the map tgs_median wrote for THIS frame's state; dL_dmedian_depth[H*W]: the upstream gradient;
+ * dz_scratch: R floats of the caller's (contents on entry do not matter); viewmatrix and radii as given to / returned by the forward.
+ * Two kernels, no float atomics, a fixed order: two runs give the same bits.  P == 0 or R == 0: nothing is launched. */
+int tgs_backward_median(void* stream, int P, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer,
+                        const void* img_buffer, const float* viewmatrix, const int* radii, const int32_t* median_pos,
+                        const float* dL_dmedian_depth, float* dz_scratch, float* dL_dmean3D);
 
 /* present[P]: 1 byte per Gaussian, 1 iff view-space z > 0.2 (auxiliary.h:154). */
 int tgs_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix,

@@ -37,6 +37,10 @@ void launch_feat_bwd(hipStream_t, const ImgState&, const BinState&, int W, int H
                      const float* dL_dmap, float* feat_rows);
 void launch_feat_bwd_gauss(hipStream_t, int P, int C, const Meta* meta, const int* radii, const GeomState&, const float* feat_rows, float* dL_dfeatures, int accumulate);
 void launch_feat_bwd_gauss_views(hipStream_t, int first, int count, int C, const FeatViews&, float* dL_dfeatures, int accumulate, bool vec);
+// tgs_median.hip
+void launch_median_fwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t T, float* out_depth, int* out_index, int* out_pos);
+void launch_median_bwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t T, size_t R, const int* median_pos, const float* dL_dmedian,
+                       float* dz_rows);
 }  // namespace tgs
 
 using namespace tgs;
@@ -1232,6 +1236,42 @@ int tgs_depth(void* stream, int P, int width, int height, int64_t R, const void*
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(TGS_ERR_HIP, "tgs_depth: %s", hipGetErrorString(e));
     return TGS_OK;
+}
+
+int tgs_median(void* stream, int P, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
+               float* out_depth, int32_t* out_index, int32_t* out_pos)
+{
+    g_err[0] = 0;
+    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "tgs_median: bad sizes P=%d W=%d H=%d R=%lld", P, width, height, (long long)R);
+    if (P == 0 || R == 0) return TGS_OK;                    // nothing was blended: no pixel has a median entry and nothing is launched (the caller's 0 / -1 / 0 stand)
+    if (!geom_buffer || !binning_buffer || !img_buffer || !out_depth || !out_index || !out_pos) return fail(TGS_ERR_INVALID, "tgs_median: NULL required pointer");
+    const ViewArgs v{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
+    if (v.gx() > 65535u || v.gy() > 65535u) return fail(TGS_ERR_INVALID, "tgs_median: image too large");
+    const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, R, geom_buffer, binning_buffer, img_buffer);
+    launch_median_fwd((hipStream_t)stream, fb.s, fb.b, width, height, v.gx(), (uint32_t)v.T(), out_depth, out_index, out_pos);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(TGS_ERR_HIP, "tgs_median: %s", hipGetErrorString(e));
+    return TGS_OK;
+}
+
+int tgs_backward_median(void* stream, int P, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
+                        const float* viewmatrix, const int* radii, const int32_t* median_pos, const float* dL_dmedian_depth, float* dz_scratch, float* dL_dmean3D)
+{
+    hipStream_t st = (hipStream_t)stream;
+    g_err[0] = 0;
+    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "tgs_backward_median: bad sizes P=%d W=%d H=%d R=%lld", P, width, height, (long long)R);
+    if (P == 0 || R == 0) return TGS_OK;                    // no pixel has a median entry: nothing to add
+    if (!geom_buffer || !binning_buffer || !img_buffer || !viewmatrix || !radii || !median_pos || !dL_dmedian_depth || !dz_scratch || !dL_dmean3D)
+        return fail(TGS_ERR_INVALID, "tgs_backward_median: NULL required pointer");
+    const ViewArgs v{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
+    if (v.gx() > 65535u || v.gy() > 65535u) return fail(TGS_ERR_INVALID, "tgs_backward_median: image too large");
+    const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, R, geom_buffer, binning_buffer, img_buffer);
+    if (int r = stage(st, TGS_STAGE_RENDER_BWD, "median_bwd", 0, [&] {
+            launch_median_bwd(st, fb.s, fb.b, width, height, v.gx(), (uint32_t)v.T(), (size_t)R, median_pos, dL_dmedian_depth, dz_scratch); }))
+        return named("tgs_backward_median", r);
+    // dz . (third row of the view transform), added behind whatever the main backward stored or accumulated on this stream
+    return named("tgs_backward_median", stage(st, TGS_STAGE_PREPROCESS_BWD, "median_bwd_gauss", 0, [&] {
+        launch_depth_bwd_gauss(st, P, fb.s.meta, radii, fb.g, viewmatrix, dz_scratch, dL_dmean3D); }));
 }
 
 int tgs_features(void* stream, int P, int C, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,

@@ -124,8 +124,12 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
                                        bool with_conic, int64_t tile_bound, c10::optional<bool> deterministic, int64_t mid_bound, c10::optional<bool> light_tiles,
                                        bool need_colors, bool need_cov3D, const c10::optional<torch::Tensor>& grad_out_alpha,
                                        const c10::optional<torch::Tensor>& grad_out_depth, const c10::optional<torch::Tensor>& grad_out_features,
-                                       const c10::optional<torch::Tensor>& features)
+                                       const c10::optional<torch::Tensor>& features, const c10::optional<torch::Tensor>& grad_out_median,
+                                       const c10::optional<torch::Tensor>& median_pos)
 {
+    // grad_out_median (extension keyword): upstream gradient of the median depth (median_from_state), [1,H,W] or [H,W], with median_pos, the int32 map
+    // [1,H,W] that median_from_state returned for this frame; None launches no median kernel, a tensor runs tgs_backward_median behind the main call
+    // (whichever of the four it is) and adds its share into the returned dL_dmeans3D.  No other gradient gets anything from it.
     // grad_out_features (extension keyword): upstream gradient of the feature map (features_from_state), [C,H,W], with features [P,C]; None launches no
     // feature kernel and returns today's tuple, a tensor goes to tgs_backward_features_opt (with grad_out_alpha / grad_out_depth or without) together with
     // a scratch of R * C floats allocated here, and dL_dfeatures[P,C] is appended to the tuple.
@@ -172,6 +176,15 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
         const torch::Tensor dz_scratch = with_depth ? torch::empty({R > 0 ? R : 1}, dL_dmeans3D.options()) : torch::Tensor();
         const Arg dF(with_feat ? *grad_out_features : torch::Tensor(), dev, "grad_out_features"), feat(with_feat ? *features : torch::Tensor(), dev, "features");
         const torch::Tensor feat_scratch = with_feat ? torch::empty({R > 0 ? R * C : 1}, dL_dmeans3D.options()) : torch::Tensor();
+        const bool with_median = grad_out_median.has_value() && grad_out_median->defined();
+        torch::Tensor mpos;
+        if (with_median) {
+            if (grad_out_median->numel() != (int64_t)H * W) throw std::runtime_error("grad_out_median must have H*W elements ([1,H,W])");
+            if (!median_pos.has_value() || !median_pos->defined() || median_pos->numel() != (int64_t)H * W || median_pos->scalar_type() != torch::kInt32)
+                throw std::runtime_error("grad_out_median needs median_pos, the int32 map [1,H,W] of median_from_state");
+            mpos = (median_pos->device() == dev ? *median_pos : median_pos->to(dev)).contiguous();
+        }
+        const Arg dM(with_median ? *grad_out_median : torch::Tensor(), dev, "grad_out_median");
         const torch::Tensor radii_c = radii.contiguous();
         void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         const tgs_options_t opt = make_options(tile_bound, c10::nullopt, deterministic, 0, mid_bound, light_tiles);
@@ -209,6 +222,13 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
                                  want_col ? dL_dcolors.data_ptr<float>() : nullptr, dL_dmeans3D.data_ptr<float>(), want_cov ? dL_dcov3D.data_ptr<float>() : nullptr,
                                  M ? dL_dsh.data_ptr<float>() : nullptr,
                                  has_sr ? dL_dscales.data_ptr<float>() : nullptr, has_sr ? dL_drotations.data_ptr<float>() : nullptr, debug);
+            // the median's share: a call of its own behind the main one, added into dL_dmeans3D (the depth's dz scratch is free again by then:
+            // the same stream)
+            if (r >= 0 && with_median && R > 0) {
+                const torch::Tensor mz = with_depth ? dz_scratch : torch::empty({R}, dL_dmeans3D.options());
+                r = tgs_backward_median(stream, P, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), view.p, radii_c.data_ptr<int>(),
+                                        mpos.data_ptr<int>(), dM.p, mz.data_ptr<float>(), dL_dmeans3D.data_ptr<float>());
+            }
         }
         if (r < 0) raise_last(r);
     }
@@ -258,6 +278,32 @@ torch::Tensor depth_from_state(const torch::Tensor& geomBuffer, const torch::Ten
     const int r = tgs_depth(stream, P, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), depth.data_ptr<float>());
     if (r < 0) raise_last(r);
     return depth;
+}
+
+// The median depth of a finished forward (tgs_median): (median_depth[1,H,W] f32, median_index[1,H,W] i32, median_pos[1,H,W] i32) -- z and Gaussian
+// index of the first blended pair after which T < 0.5, and its 1-based position in the tile's list (what the backward reads).  Pixels without
+// such a pair, an empty model and a frame without instances: 0 / -1 / 0, and for the latter two nothing is launched.
+py::tuple median_from_state(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, int P, int H, int W, int64_t R)
+{
+    if (!imageBuffer.is_cuda()) throw std::runtime_error("median_from_state: the state buffers must be those of a forward, on a HIP device");
+    if (P < 0 || H <= 0 || W <= 0 || R < 0) throw std::runtime_error("median_from_state: bad sizes");
+    const c10::Device dev = imageBuffer.device();
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
+    const auto i32 = f32.dtype(torch::kInt32);
+    if (P == 0 || R == 0) return py::make_tuple(torch::zeros({1, H, W}, f32), torch::full({1, H, W}, -1, i32), torch::zeros({1, H, W}, i32));
+    size_t sizes[3];
+    tgs_state_sizes(P, W, H, 0, 0, R, sizes);
+    const auto bytes = [](const torch::Tensor& t) { return (size_t)t.numel() * t.element_size(); };
+    if (!geomBuffer.is_cuda() || !binningBuffer.is_cuda() || bytes(geomBuffer) < sizes[TGS_BUF_GEOM] || bytes(binningBuffer) < sizes[TGS_BUF_BINNING] ||
+        bytes(imageBuffer) < sizes[TGS_BUF_IMAGE])
+        throw std::runtime_error("median_from_state: state buffers smaller than a frame of these sizes");
+    torch::Tensor depth = torch::empty({1, H, W}, f32), index = torch::empty({1, H, W}, i32), pos = torch::empty({1, H, W}, i32);
+    void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+    const int r = tgs_median(stream, P, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), depth.data_ptr<float>(), index.data_ptr<int>(),
+                             pos.data_ptr<int>());
+    if (r < 0) raise_last(r);
+    return py::make_tuple(depth, index, pos);
 }
 
 // The feature map of a finished forward (tgs_features): [C,H,W] = sum_i T_i alpha_i features[i, :] over the pairs the colour frame blended.
@@ -320,7 +366,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"), py::arg("_with_conic") = false, py::arg("tile_bound") = 0,
           py::arg("deterministic") = py::none(), py::arg("mid_bound") = 0, py::arg("light_tiles") = py::none(), py::arg("need_colors") = true,
           py::arg("need_cov3D") = true, py::arg("grad_out_alpha") = py::none(), py::arg("grad_out_depth") = py::none(),
-          py::arg("grad_out_features") = py::none(), py::arg("features") = py::none());
+          py::arg("grad_out_features") = py::none(), py::arg("features") = py::none(), py::arg("grad_out_median") = py::none(), py::arg("median_pos") = py::none());
+    m.def("median_from_state", &median_from_state, py::arg("geomBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("P"), py::arg("H"), py::arg("W"), py::arg("R"));
     m.def("features_from_state", &features_from_state, py::arg("geomBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("features"), py::arg("P"),
           py::arg("H"), py::arg("W"), py::arg("R"));
     m.def("depth_from_state", &depth_from_state, py::arg("geomBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("P"), py::arg("H"), py::arg("W"), py::arg("R"));

@@ -90,6 +90,11 @@ def _load() -> C.CDLL:
     lib.tgs_backward_batch_features_range.argtypes = [vp, it, it, vp, vp, vp, it, it, it]
     lib.tgs_backward_features_opt.restype = it
     lib.tgs_backward_features_opt.argtypes = lib.tgs_backward_opt.argtypes[:27] + [vp, vp, vp] + [it, vp, vp, vp, vp] + [vp] * 9 + [it]
+    # median depth of one view: the map and the call that adds its share behind a backward
+    lib.tgs_median.restype = it
+    lib.tgs_median.argtypes = [vp, it, it, it, C.c_int64, vp, vp, vp, vp, vp, vp]
+    lib.tgs_backward_median.restype = it
+    lib.tgs_backward_median.argtypes = [vp, it, it, it, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tgs_state_field.restype = C.c_int64
     lib.tgs_state_field.argtypes = [vp, C.c_char_p, it, it, it, C.c_int64, it, it, vp, vp, vp, vp, C.c_size_t]
     lib.tgs_set_sort_lds_cap.restype = it
@@ -295,14 +300,18 @@ def rasterize_gaussians_backward_accumulate(background, means3D, radii, colors, 
                                             geomBuffer, R, binningBuffer, imageBuffer, debug, into, tile_bound: int = 0,
                                             deterministic: Optional[bool] = None, mid_bound: int = 0, *,
                                             grad_out_alpha: Optional[torch.Tensor] = None, grad_out_depth: Optional[torch.Tensor] = None,
-                                            grad_out_features: Optional[torch.Tensor] = None, features: Optional[torch.Tensor] = None):
+                                            grad_out_features: Optional[torch.Tensor] = None, features: Optional[torch.Tensor] = None,
+                                            grad_out_median: Optional[torch.Tensor] = None, median_pos: Optional[torch.Tensor] = None):
     """Multi-view extension (tgs_backward_accumulate): parameter gradients are ADDED into the fp32 tensors of ``into``
     (keys: means3D, opacities, and sh|colors_precomp, scales+rotations|cov3D_precomp; contiguous, on the device).
     Returns dL_dmeans2D[P,3], the only per-view gradient.  ``grad_out_alpha`` / ``grad_out_depth`` ([1,H,W]): upstream gradients of the
     frame's accumulated alpha / expected depth as well (tgs_backward_depth_opt with accumulate = 1; the dz scratch of R floats is
     allocated here); both None: today's call (tgs_backward_opt), bit for bit.  ``grad_out_features`` ([C,H,W]) with ``features`` ([P,C],
     float32, 1 <= C <= 16): the upstream gradient of the frame's feature map as well (tgs_backward_features_opt with accumulate = 1; the
-    scratch of R * C floats is allocated here); dL/d features is ADDED into ``into["features"]`` ([P,C]), which is required then."""
+    scratch of R * C floats is allocated here); dL/d features is ADDED into ``into["features"]`` ([P,C]), which is required then.
+    ``grad_out_median`` ([1,H,W]) with ``median_pos`` (the int32 map [1,H,W] of ``median_from_state`` for this frame): the upstream gradient
+    of the frame's median depth as well -- tgs_backward_median behind the main call adds its share into ``into["means3D"]`` (a scratch of R
+    floats is allocated here); no other gradient gets anything from it.  None: today's calls and today's kernels."""
     dev = _require_gpu(means3D)
     P = int(means3D.size(0))
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
@@ -360,6 +369,19 @@ def rasterize_gaussians_backward_accumulate(background, means3D, radii, colors, 
             int(bool(debug)))
         if r < 0:
             raise _err(int(r))
+        if grad_out_median is not None:
+            if grad_out_median.numel() != H * W:
+                raise RuntimeError("grad_out_median must have H*W elements ([1,H,W])")
+            if median_pos is None or median_pos.numel() != H * W or median_pos.dtype != torch.int32:
+                raise RuntimeError("grad_out_median needs median_pos, the int32 map [1,H,W] of median_from_state")
+            if int(R) > 0:
+                dM, mpos = _dev_f32(grad_out_median, dev, "grad_out_median"), median_pos.to(dev).contiguous()
+                mz = torch.empty((int(R),), dtype=torch.float32, device=dev)
+                r = _lib.tgs_backward_median(torch.cuda.current_stream(dev).cuda_stream, P, W, H, int(R), geomBuffer.data_ptr(), binningBuffer.data_ptr(),
+                                             imageBuffer.data_ptr(), _p(t["view"]), radii.contiguous().data_ptr(), mpos.data_ptr(), _p(dM), mz.data_ptr(),
+                                             dst("means3D", (P, 3)))
+                if r < 0:
+                    raise _err(int(r))
     return dL_dmeans2D
 
 
@@ -616,7 +638,7 @@ def state_field(name: str, P: int, width: int, height: int, R: int, has_sh: bool
 
 
 # The reference's three exports (ext.cpp:15-19): the compiled module's functions, positional signatures of rasterize_points.h:18-67
-# (+ the keyword-only extensions r_capacity / r_guess / _with_conic / grad_out_alpha / grad_out_depth / grad_out_features + features documented in csrc/tgs_torch_ext.cpp).
+# (+ the keyword-only extensions r_capacity / r_guess / _with_conic / grad_out_alpha / grad_out_depth / grad_out_features + features / grad_out_median + median_pos documented in csrc/tgs_torch_ext.cpp).
 rasterize_gaussians = _ext.rasterize_gaussians
 rasterize_gaussians_backward = _ext.rasterize_gaussians_backward
 mark_visible = _ext.mark_visible
@@ -626,4 +648,8 @@ depth_from_state = _ext.depth_from_state
 # (geomBuffer, binningBuffer, imageBuffer, features[P,C], P, H, W, R) -> the frame's feature map [C,H,W] = sum_i T_i alpha_i features[i, :]
 # (tgs_features; an extension, 1 <= C <= 16)
 features_from_state = _ext.features_from_state
+# (geomBuffer, binningBuffer, imageBuffer, P, H, W, R) -> (median_depth[1,H,W] f32, median_index[1,H,W] i32, median_pos[1,H,W] i32): z and Gaussian
+# index of the first blended pair after which T < 0.5 (0 / -1 where there is none) and its 1-based list position, which the backward's
+# grad_out_median / median_pos keywords take (tgs_median; an extension)
+median_from_state = _ext.median_from_state
 FEATURE_MAX_CHANNELS = 16      # TGS_FEATURE_MAX_CHANNELS

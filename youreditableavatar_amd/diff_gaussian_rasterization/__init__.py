@@ -183,9 +183,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         return _RasterizeGaussians.native_backward(ctx, grad_out_color, None)
 
     @staticmethod
-    def native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth=None, grad_out_features=None, features=None):
-        """grad_out_alpha / grad_out_depth / grad_out_features None: today's native call, today's kernels; a tensor: the extension keyword of
-        the same call.  With grad_out_features (and the forward's features) the gradient of the features follows the nine of today."""
+    def native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth=None, grad_out_features=None, features=None, grad_out_median=None, median_pos=None):
+        """grad_out_alpha / grad_out_depth / grad_out_features / grad_out_median None: today's native call, today's kernels; a tensor: the
+        extension keyword of the same call.  With grad_out_features (and the forward's features) the gradient of the features follows the nine
+        of today; grad_out_median travels with the forward's median_pos and adds to the means' gradient alone."""
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:                           # the image did not take part in the loss (gradients not materialised, see forward)
@@ -206,6 +207,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             extra["grad_out_depth"] = grad_out_depth
         if grad_out_features is not None:
             extra["grad_out_features"], extra["features"] = grad_out_features, features
+        if grad_out_median is not None:
+            extra["grad_out_median"], extra["median_pos"] = grad_out_median, median_pos
         (g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rots, *g_feat) = _call_native(
             lambda *a: _C.rasterize_gaussians_backward(*a, tile_bound=bound, mid_bound=mid, light_tiles=ctx.light, need_colors=need_col, need_cov3D=need_cov, **extra),
             args, rs.debug, "snapshot_bw.dump", "backward")
@@ -220,6 +223,8 @@ class _RasterizeGaussiansExt(torch.autograd.Function):
     rasterizer has neither):
       alpha [1,H,W] = 1 - final_T of the frame, so that ``color == C_premultiplied + (1 - alpha) * bg``;
       depth [1,H,W] = sum_i T_i alpha_i z_i over the pairs the colour frame blended (expected depth, not normalised; z = view-space z);
+      median_depth [1,H,W], median_index [1,H,W] (int32, non-differentiable) = view-space z and Gaussian index of the first blended pair after
+      which the transmittance falls below one half (0 and -1 where it never does); the gradient of median_depth reaches the positions alone;
       feature_map [C,H,W] = sum_i T_i alpha_i features[i, :] over the same pairs, for per-Gaussian features [P,C] (1 <= C <= 16; signed, not
       clamped, not normalised, background 0) -- a real autograd input: its gradient is None when it does not need one.
     Same native forward and backward; the upstream gradients of the extra outputs travel with the colour's in ONE backward call.
@@ -227,7 +232,8 @@ class _RasterizeGaussiansExt(torch.autograd.Function):
     gradient launches exactly the kernels of a frame without that output."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, want_alpha, want_depth, features=None):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, want_alpha, want_depth, features=None,
+                want_median=False):
         rs = raster_settings
         color, radii, img, geom, binning = _RasterizeGaussians.native_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs,
                                                                               with_state=True)
@@ -244,6 +250,14 @@ class _RasterizeGaussiansExt(torch.autograd.Function):
                 out.append(torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device))
             else:
                 out.append(_C.depth_from_state(geom, binning, img, P, H, W, int(ctx.num_rendered)))
+        ctx.want_median = bool(want_median)
+        if want_median:
+            if P == 0:                                          # zeros and -1 without a native call
+                md, mi, ctx.median_pos = torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device), torch.full((1, H, W), -1, dtype=torch.int32, device=means3D.device), None
+            else:
+                md, mi, ctx.median_pos = _C.median_from_state(geom, binning, img, P, H, W, int(ctx.num_rendered))      # (median_pos: kept for the backward)
+            ctx.mark_non_differentiable(radii, mi)
+            out += [md, mi]
         ctx.want_features = features is not None
         if features is not None:
             ctx.features = features                             # (an input: held as save_for_backward holds the others, without a second call of it)
@@ -258,11 +272,17 @@ class _RasterizeGaussiansExt(torch.autograd.Function):
         extra = list(extra)
         grad_out_alpha = extra.pop(0) if ctx.want_alpha else None
         grad_out_depth = extra.pop(0) if ctx.want_depth else None
+        med = {}
+        if ctx.want_median:
+            grad_out_median, _grad_index = extra.pop(0), extra.pop(0)
+            # a median depth the loss did not use, or an empty model: no median kernel runs
+            if grad_out_median is not None and ctx.median_pos is not None:
+                med = dict(grad_out_median=grad_out_median, median_pos=ctx.median_pos)
         grad_out_features = extra.pop(0) if ctx.want_features else None
         if grad_out_features is None:                       # no feature map, or one the loss did not use: no feature kernel runs
-            return _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth) + (None, None, None)
-        g = _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth, grad_out_features, ctx.features)
-        return g[:-1] + (None, None, g[-1] if ctx.needs_input_grad[11] else None)
+            return _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth, **med) + (None, None, None, None)
+        g = _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth, grad_out_features, ctx.features, **med)
+        return g[:-1] + (None, None, g[-1] if ctx.needs_input_grad[11] else None, None)
 
 
 _RasterizeGaussiansAlpha = _RasterizeGaussiansExt           # (the name of the node when it had one extra output)
@@ -280,13 +300,18 @@ def _check_features(features, means3D):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, return_alpha=False,
-                        return_depth=False, features=None):
-    """``return_alpha=True`` / ``return_depth=True`` / ``features=F[P,C]`` (extensions): -> (color[3,H,W], radii[P]), then alpha[1,H,W] if
-    asked, then depth[1,H,W] if asked, then feature_map[C,H,W] if ``features`` is given -- the differentiable accumulated alpha, expected
-    depth and composited per-Gaussian features (sum_i T_i alpha_i F[i, :]; float32, 1 <= C <= 16) of the same compositing."""
-    if return_alpha or return_depth or features is not None:
+                        return_depth=False, features=None, return_median=False):
+    """``return_alpha=True`` / ``return_depth=True`` / ``return_median=True`` / ``features=F[P,C]`` (extensions): -> (color[3,H,W], radii[P]),
+    then alpha[1,H,W] if asked, then depth[1,H,W] if asked, then median_depth[1,H,W], median_index[1,H,W] if asked, then feature_map[C,H,W] if
+    ``features`` is given (it stays last) -- the differentiable accumulated alpha, expected depth and composited per-Gaussian features
+    (sum_i T_i alpha_i F[i, :]; float32, 1 <= C <= 16) of the same compositing, and its median: the view-space z (float32) and the Gaussian
+    index (int32, no gradient) of the first blended splat after which the transmittance falls below one half -- a point on the front
+    surface and the splat that is that surface; 0 and -1 where the transmittance stays at or above one half.  The gradient of median_depth
+    goes to the positions alone (d median_depth / d z of the median splat = 1): a loss on it moves means3D, not opacities."""
+    if return_alpha or return_depth or return_median or features is not None:
         return _RasterizeGaussiansExt.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                                            bool(return_alpha), bool(return_depth), None if features is None else _check_features(features, means3D))
+                                            bool(return_alpha), bool(return_depth), None if features is None else _check_features(features, means3D),
+                                            bool(return_median))
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
 
 
@@ -302,7 +327,7 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, return_alpha=False, return_depth=False,
-                features=None):
+                features=None, return_median=False):
         rs = self.raster_settings
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -319,4 +344,4 @@ class GaussianRasterizer(nn.Module):
             absent if scales is None else scales,
             absent if rotations is None else rotations,
             absent if cov3D_precomp is None else cov3D_precomp,
-            rs, return_alpha=return_alpha, return_depth=return_depth, features=features)
+            rs, return_alpha=return_alpha, return_depth=return_depth, features=features, return_median=return_median)
