@@ -616,3 +616,408 @@ def test_small_entry_point_rejections(abi):
     _check(lib, failures, "tgs_state_field: dst too small", field(b"means2D", 10, 5, 79), INVALID, "dst too small for means2D")
     _check(lib, failures, "tgs_state_field: nothing to copy", field(b"point_list", 10, 0, 0), 0, "")
     assert not failures, "\n".join(failures)
+
+
+# ---- the extension entry points (alpha, depth, median, features; one view and whole batch): the same mechanism, further rows ----
+class _Extras(ctypes.Structure):            # tgs_view_extras_t
+    _fields_ = [("struct_size", ctypes.c_uint32), ("out_alpha", _vp), ("out_depth", _vp), ("dL_dalpha", _vp), ("dL_ddepth", _vp), ("dz_scratch", _vp)]
+
+
+class _Feats(ctypes.Structure):             # tgs_view_features_t
+    _fields_ = [("struct_size", ctypes.c_uint32), ("C", ctypes.c_int32), ("features", _vp), ("out_features", _vp), ("dL_dfeature_map", _vp), ("feature_scratch", _vp)]
+
+
+def _after(base, key, extra):
+    """`base` with the entries of `extra` put in behind `key` (the dicts carry the order of the C signatures)"""
+    out = {}
+    for k, v in base.items():
+        out[k] = v
+        if k == key:
+            out.update(extra)
+    return out
+
+
+def _types_after(types, n, extra):
+    return types[:n] + extra + types[n:]
+
+
+BWD_A = _after(BWD, "dL_dpix", dict(dL_dalpha=X))
+BWD_D = _after(BWD, "dL_dpix", dict(dL_dalpha=X, dL_ddepth=X, dz_scratch=X))
+BWD_F = _after(BWD, "dL_dpix", dict(dL_dalpha=X, dL_ddepth=X, dz_scratch=X, C=4, features=X, dL_dfeature_map=X, feature_scratch=X, dL_dfeatures=X))
+FRAME = dict(stream=None, P=10, width=64, height=64, R=5, geom_buffer=X, binning_buffer=X, img_buffer=X)
+MSG_CHANNELS = "bad channel count C=%d (1 .. 16)"
+MSG_STREAMS = "bad arguments (streams, n_streams=%d)"
+MSG_X_SMALL = "tgs_view_extras_t: struct_size %d is smaller than the first pointer field"
+MSG_X_MIXED = "view %d: tgs_view_extras_t.struct_size %d differs from the array's %d"
+MSG_F_SMALL = "tgs_view_features_t: struct_size %d is smaller than the end of the features field"
+MSG_F_MIXED = "view %d: tgs_view_features_t.struct_size %d differs from the array's %d"
+MSG_F_DIFFER = "view %d: C=%d / features differ from an earlier view's (C=%d): the features are the model's, one tensor for all views"
+
+
+@pytest.fixture(scope="module")
+def ext_abi(abi):
+    lib = abi
+    opt_types = [_vp, _it] + BWD_TYPES
+    views = [_vp, _it, _it, _it, _vp, _vp]              # streams, n_streams, P, n_views, views, one array
+    for name, types in (
+            ("tgs_alpha", [_vp, _it, _it, _vp, _vp]), ("tgs_depth", [_vp, _it, _it, _it, _i64, _vp, _vp, _vp, _vp]),
+            ("tgs_median", [_vp, _it, _it, _it, _i64] + [_vp] * 6), ("tgs_backward_median", [_vp, _it, _it, _it, _i64] + [_vp] * 9),
+            ("tgs_features", [_vp, _it, _it, _it, _it, _i64] + [_vp] * 5),
+            ("tgs_backward_alpha_opt", _types_after(opt_types, 27, [_vp])), ("tgs_backward_depth_opt", _types_after(opt_types, 27, [_vp] * 3)),
+            ("tgs_backward_features_opt", _types_after(opt_types, 27, [_vp] * 3 + [_it] + [_vp] * 4)),
+            ("tgs_backward_render_alpha_opt", [_vp, _vp, _it, _i64, _vp, _it, _it, _vp, _vp, _vp, _vp]),
+            ("tgs_outputs_views", views), ("tgs_features_views", views), ("tgs_backward_render_views_extras_opt", [_vp] + views),
+            ("tgs_backward_render_views_features_opt", [_vp] + views + [_vp]),
+            ("tgs_backward_batch_depth_range", [_vp, _it, _it, _vp, _vp, _vp, _it, _it]),
+            ("tgs_backward_batch_features_range", [_vp, _it, _it, _vp, _vp, _vp, _it, _it, _it])):
+        getattr(lib, name).restype, getattr(lib, name).argtypes = _it, types
+    return lib
+
+
+def test_backward_extension_rejections(ext_abi):
+    """tgs_backward_alpha_opt, tgs_backward_depth_opt, tgs_backward_features_opt: the checks of tgs_backward_opt behind the entry point's name,
+    then what the extra arguments ask.  tgs_backward_features_opt without a map IS the depth call and names itself so."""
+    lib, failures = ext_abi, []
+    entries = [("tgs_backward_alpha_opt", "tgs_backward_alpha_opt", BWD_A, {}, lambda acc, a: lib.tgs_backward_alpha_opt(None, acc, *a)),
+               ("tgs_backward_alpha_opt, no dL_dalpha", "tgs_backward_alpha_opt", BWD_A, dict(dL_dalpha=None), lambda acc, a: lib.tgs_backward_alpha_opt(None, acc, *a)),
+               ("tgs_backward_depth_opt", "tgs_backward_depth_opt", BWD_D, {}, lambda acc, a: lib.tgs_backward_depth_opt(None, acc, *a)),
+               ("tgs_backward_depth_opt, no upstream", "tgs_backward_depth_opt", BWD_D, dict(dL_dalpha=None, dL_ddepth=None, dz_scratch=None),
+                lambda acc, a: lib.tgs_backward_depth_opt(None, acc, *a)),
+               ("tgs_backward_features_opt", "tgs_backward_features_opt", BWD_F, {}, lambda acc, a: lib.tgs_backward_features_opt(None, acc, *a)),
+               ("tgs_backward_features_opt, no map", "tgs_backward_depth_opt", BWD_F, dict(dL_dfeature_map=None), lambda acc, a: lib.tgs_backward_features_opt(None, acc, *a)),
+               ("tgs_backward_features_opt, no map, nothing else", "tgs_backward_depth_opt", BWD_F,
+                dict(dL_dalpha=None, dL_ddepth=None, dz_scratch=None, C=0, features=None, dL_dfeature_map=None, feature_scratch=None, dL_dfeatures=None),
+                lambda acc, a: lib.tgs_backward_features_opt(None, acc, *a))]
+    for ename, prefix, base, fixed, call in entries:
+        for acc in (0, 1):
+            for label, over, strict_only, _only_acc, text in BACKWARD_TABLE:
+                if not strict_only:
+                    _check(lib, failures, f"{ename} ({acc}): {label}", call(acc, _args(base, {**fixed, **over})), INVALID, f"{prefix}: {text}")
+            _check(lib, failures, f"{ename} ({acc}): P == 0", call(acc, _args(base, {**fixed, **dict(P=0, R=-1, width=0, colors_precomp=None, radii=None)})), 0, "")
+    depth = lambda over, acc=0: lib.tgs_backward_depth_opt(None, acc, *_args(BWD_D, over))
+    feat = lambda over, acc=0: lib.tgs_backward_features_opt(None, acc, *_args(BWD_F, over))
+    D, F = "tgs_backward_depth_opt: ", "tgs_backward_features_opt: "
+    for name, call, prefix in (("depth", depth, D), ("features", feat, F), ("features, no map", lambda over: feat(dict(over, dL_dfeature_map=None)), D)):
+        _check(lib, failures, f"{name}: dL_ddepth without dz_scratch", call(dict(dz_scratch=None)), INVALID, prefix + MSG_NULL)
+        _check(lib, failures, f"{name}: dL_ddepth without viewmatrix", call(dict(viewmatrix=None)), INVALID, prefix + MSG_NULL)
+        _check(lib, failures, f"{name}: the model wins over dz_scratch", call(dict(dz_scratch=None, cov3D_precomp=X)), INVALID, prefix + MSG_SR)
+        _check(lib, failures, f"{name}: sizes win over dz_scratch", call(dict(dz_scratch=None, R=-1)), INVALID, prefix + "bad sizes")
+        _check(lib, failures, f"{name}: P == 0 with dL_ddepth and no scratch", call(dict(P=0, dz_scratch=None)), 0, "")
+    for p in ("features", "feature_scratch", "dL_dfeatures"):
+        _check(lib, failures, f"features: {p} NULL", feat({p: None}), INVALID, F + MSG_NULL)
+        _check(lib, failures, f"features, accumulate: {p} NULL", feat({p: None}, 1), INVALID, F + MSG_NULL)
+    for c in (0, -1, 17):
+        _check(lib, failures, f"features: C = {c}", feat(dict(C=c)), INVALID, F + MSG_CHANNELS % c)
+        _check(lib, failures, f"features: a NULL pointer wins over C = {c}", feat(dict(C=c, features=None)), INVALID, F + MSG_NULL)
+        _check(lib, failures, f"features: the model wins over C = {c}", feat(dict(C=c, colors_precomp=None)), INVALID, F + MSG_COLOR)
+        _check(lib, failures, f"features: sizes win over C = {c}", feat(dict(C=c, height=0)), INVALID, F + "bad sizes")
+        _check(lib, failures, f"features: P == 0 with C = {c}", feat(dict(C=c, P=0, features=None)), 0, "")
+    assert not failures, "\n".join(failures)
+
+
+def test_backward_render_alpha_rejections(ext_abi):
+    lib, failures = ext_abi, []
+    base = dict(stream=None, P=10, R=5, background=X, width=64, height=64, binning_buffer=X, img_buffer=X, dL_dpix=X, dL_dalpha=X)
+    pre = "tgs_backward_render_alpha_opt: "
+    rows = [(f"{k} = {v}", {k: v}, INVALID, pre + "bad sizes") for k, v in (("P", -1), ("R", -1), ("width", 0), ("height", -1))] + \
+           [(f"{p} NULL", {p: None}, INVALID, pre + MSG_NULL) for p in ("background", "binning_buffer", "img_buffer", "dL_dpix")] + \
+           [("sizes win over NULL pointers", dict(R=-2, dL_dpix=None), INVALID, pre + "bad sizes"), ("P == 0", dict(P=0, R=-1, dL_dpix=None), 0, ""),
+            ("P < 0 wins over the view", dict(P=-1, width=0, dL_dpix=None), INVALID, pre + "bad sizes"), ("R == 0: nothing to launch", dict(R=0), 0, "")]
+    for label, over, code, text in rows:
+        for dA in (X, None):
+            a = _args(base, {**over, "dL_dalpha": dA})
+            _check(lib, failures, f"{label} (dL_dalpha {dA})", lib.tgs_backward_render_alpha_opt(None, *a), code, text)
+            _check(lib, failures, f"options: {label} (dL_dalpha {dA})", lib.tgs_backward_render_alpha_opt(ctypes.byref(_options(tile_bound=3)), *a), code, text)
+    assert not failures, "\n".join(failures)
+
+
+def test_frame_output_rejections(ext_abi):
+    """tgs_alpha, tgs_depth, tgs_median, tgs_backward_median, tgs_features: sizes, (the channel count,) the frame in which nothing was blended,
+    NULL pointers, the grid limit -- in this order.  tgs_alpha has neither P / R nor a grid limit."""
+    lib, failures = ext_abi, []
+    alpha = lambda **o: lib.tgs_alpha(*_args(dict(stream=None, width=64, height=64, img_buffer=X, out_alpha=X), o))
+    _check(lib, failures, "tgs_alpha: W == 0", alpha(width=0), INVALID, "tgs_alpha: bad sizes W=0 H=64")
+    _check(lib, failures, "tgs_alpha: H < 0", alpha(height=-1), INVALID, "tgs_alpha: bad sizes W=64 H=-1")
+    _check(lib, failures, "tgs_alpha: sizes win over NULL", alpha(width=0, img_buffer=None), INVALID, "tgs_alpha: bad sizes W=0 H=64")
+    _check(lib, failures, "tgs_alpha: img_buffer NULL", alpha(img_buffer=None), INVALID, "tgs_alpha: NULL required pointer")
+    _check(lib, failures, "tgs_alpha: out_alpha NULL", alpha(out_alpha=None), INVALID, "tgs_alpha: NULL required pointer")
+    _check(lib, failures, "tgs_alpha: no image-size limit (the NULL pointer is what is wrong)", alpha(width=BIG, height=16, out_alpha=None), INVALID, "tgs_alpha: NULL required pointer")
+    entries = [("tgs_depth", {**FRAME, "out_depth": X}, lambda a: lib.tgs_depth(*a)),
+               ("tgs_median", {**FRAME, "out_depth": X, "out_index": X, "out_pos": X}, lambda a: lib.tgs_median(*a)),
+               ("tgs_backward_median", {**FRAME, "viewmatrix": X, "radii": X, "median_pos": X, "dL_dmedian_depth": X, "dz_scratch": X, "dL_dmean3D": X},
+                lambda a: lib.tgs_backward_median(*a)),
+               ("tgs_features", {**_after(FRAME, "P", dict(C=4)), "features": X, "out": X}, lambda a: lib.tgs_features(*a))]
+    for fn, base, call in entries:
+        run = lambda label, code, text, **over: _check(lib, failures, f"{fn}: {label}", call(_args(base, over)), code, text)
+        sizes = lambda **o: f"{fn}: bad sizes P=%d W=%d H=%d R=%d" % tuple({**base, **o}[k] for k in ("P", "width", "height", "R"))
+        for over in (dict(P=-1), dict(R=-1), dict(width=0), dict(height=-2), dict(P=-3, width=0, height=0, R=-(1 << 40))):
+            run(f"{over}", INVALID, sizes(**over), **over)
+        run("sizes win over the empty model", INVALID, sizes(P=0, width=0), P=0, width=0)
+        run("sizes win over the empty frame", INVALID, sizes(R=0, height=-1), R=0, height=-1)
+        run("sizes win over NULL pointers", INVALID, sizes(R=-1), R=-1, img_buffer=None)
+        pointers = [k for k, v in base.items() if v == X]
+        nothing = {p: None for p in pointers}
+        run("P == 0: nothing was blended", 0, "", P=0)
+        run("R == 0: nothing was blended", 0, "", R=0)
+        run("P == 0 looks at no pointer and at no grid limit", 0, "", P=0, width=BIG, **nothing)
+        run("R == 0 looks at no pointer and at no grid limit", 0, "", R=0, height=BIG, **nothing)
+        for p in pointers:
+            run(f"{p} NULL", INVALID, f"{fn}: NULL required pointer", **{p: None})
+            run(f"{p} NULL wins over the image size", INVALID, f"{fn}: NULL required pointer", **{p: None, "width": BIG})
+        run("image too wide", INVALID, f"{fn}: image too large", width=BIG, height=16)
+        run("image too high", INVALID, f"{fn}: image too large", width=16, height=BIG)
+        if fn == "tgs_features":
+            for c in (0, -2, 17):
+                run(f"C = {c}", INVALID, f"{fn}: " + MSG_CHANNELS % c, C=c)
+                run(f"C = {c} is checked before the empty model", INVALID, f"{fn}: " + MSG_CHANNELS % c, C=c, P=0)
+                run(f"C = {c} is checked before the empty frame", INVALID, f"{fn}: " + MSG_CHANNELS % c, C=c, R=0)
+                run(f"C = {c} wins over NULL pointers and the image size", INVALID, f"{fn}: " + MSG_CHANNELS % c, C=c, features=None, width=BIG)
+                run(f"sizes win over C = {c}", INVALID, sizes(P=-1), C=c, P=-1)
+            run("P == 0, C = 16", 0, "", P=0, C=16)
+    assert not failures, "\n".join(failures)
+
+
+def _extras(n, struct_size=None, **fields):
+    arr = (_Extras * n)()
+    for x in arr:
+        x.struct_size = ctypes.sizeof(_Extras) if struct_size is None else struct_size
+        for k, v in fields.items():
+            setattr(x, k, v)
+    return arr
+
+
+def _feats(n, struct_size=None, C=5, **fields):
+    arr = (_Feats * n)()
+    for x in arr:
+        x.struct_size, x.C = ctypes.sizeof(_Feats) if struct_size is None else struct_size, C
+        for k, v in fields.items():
+            setattr(x, k, v)
+    return arr
+
+
+def _ptr(arr):
+    return ctypes.cast(arr, _vp) if arr is not None else None
+
+
+def _extras_array_rows(run):
+    """what every call that takes a tgs_view_extras_t array says of it, before it looks at anything else but P, n_views and views;
+    run(label, code, text, extras=..., **over)"""
+    run("extras: P < 0", INVALID, "bad sizes P=-1 n_views=2", P=-1)
+    run("extras: n_views < 0", INVALID, "bad sizes P=10 n_views=-1", n_views=-1)
+    run("extras: views NULL", INVALID, "NULL required pointer (views)", views=None)
+    run("extras: sizes win over the array", INVALID, "bad sizes P=-1 n_views=2", P=-1, extras=_extras(2, struct_size=8))
+    run("extras: views NULL wins over the array", INVALID, "NULL required pointer (views)", views=None, extras=_extras(2, struct_size=8))
+    for n in (0, 4, 8, 15):
+        run(f"extras: struct_size {n}", INVALID, MSG_X_SMALL % n, extras=_extras(2, struct_size=n))
+    mixed = _extras(2); mixed[1].struct_size = 40
+    run("extras: mixed struct_size", INVALID, MSG_X_MIXED % (1, 40, 48), extras=mixed)
+    mixed = _extras(2, dL_ddepth=X); mixed[1].struct_size = 56
+    run("extras: view 0's fields before view 1's struct_size", INVALID, "view 0: dL_ddepth without dz_scratch", extras=mixed)
+    x = _extras(2, dL_ddepth=X, dz_scratch=X); x[1].dz_scratch = None
+    run("extras: view 1: dL_ddepth without dz_scratch", INVALID, "view 1: dL_ddepth without dz_scratch", extras=x)
+    run("extras: the array is checked for an empty model as well", INVALID, "view 0: dL_ddepth without dz_scratch", P=0, extras=_extras(2, dL_ddepth=X))
+    # a caller built against a shorter struct: the stride is its struct_size and the fields beyond it read as NULL
+    run("extras: fields beyond struct_size read as NULL", INVALID, "view 0: dL_ddepth without dz_scratch", n_views=1, extras=_extras(1, struct_size=40, dL_ddepth=X, dz_scratch=X))
+
+
+def _feats_array_rows(run):
+    """the same for a tgs_view_features_t array; run(label, code, text, feats=..., **over)"""
+    full = dict(features=X, out_features=X, dL_dfeature_map=X, feature_scratch=X)
+    run("feats: P < 0", INVALID, "bad sizes P=-1 n_views=2", P=-1)
+    run("feats: n_views < 0", INVALID, "bad sizes P=10 n_views=-1", n_views=-1)
+    run("feats: views NULL", INVALID, "NULL required pointer (views)", views=None)
+    run("feats: sizes win over the array", INVALID, "bad sizes P=-1 n_views=2", P=-1, feats=_feats(2, struct_size=8, **full))
+    for n in (0, 8, 15):
+        run(f"feats: struct_size {n}", INVALID, MSG_F_SMALL % n, feats=_feats(2, struct_size=n, **full))
+    mixed = _feats(2, **full); mixed[1].struct_size = 32
+    run("feats: mixed struct_size", INVALID, MSG_F_MIXED % (1, 32, 40), feats=mixed)
+    for c in (0, -3, 17):
+        run(f"feats: C = {c}", INVALID, "view 0: " + MSG_CHANNELS % c, feats=_feats(2, C=c, **full))
+        run(f"feats: C = {c} with features alone", INVALID, "view 0: " + MSG_CHANNELS % c, feats=_feats(2, C=c, features=X))
+        run(f"feats: C = {c} wins over missing features", INVALID, "view 0: " + MSG_CHANNELS % c, feats=_feats(2, C=c, out_features=X))
+    run("feats: out_features without features", INVALID, "view 0: out_features / dL_dfeature_map without features", feats=_feats(2, out_features=X))
+    run("feats: dL_dfeature_map without features", INVALID, "view 0: out_features / dL_dfeature_map without features", feats=_feats(2, dL_dfeature_map=X, feature_scratch=X))
+    run("feats: dL_dfeature_map without feature_scratch", INVALID, "view 0: dL_dfeature_map without feature_scratch", feats=_feats(2, features=X, dL_dfeature_map=X))
+    f = _feats(2, **full); f[1].C = 4
+    run("feats: C differs", INVALID, MSG_F_DIFFER % (1, 4, 5), feats=f)
+    f = _feats(2, **full); f[1].features = 2 * X
+    run("feats: features differ", INVALID, MSG_F_DIFFER % (1, 5, 5), feats=f)
+    f = _feats(2, **full); f[0].features = f[0].out_features = f[0].dL_dfeature_map = None; f[0].C = 0; f[1].dL_dfeature_map = X; f[1].feature_scratch = None
+    run("feats: view 0 takes no part, view 1 has no scratch", INVALID, "view 1: dL_dfeature_map without feature_scratch", feats=f)
+    run("feats: the array is checked for an empty model as well", INVALID, "view 0: " + MSG_CHANNELS % 0, P=0, feats=_feats(2, C=0, **full))
+    run("feats: fields beyond struct_size read as NULL", INVALID, "view 0: dL_dfeature_map without feature_scratch", n_views=1, feats=_feats(1, struct_size=32, **full))
+
+
+def test_outputs_views_rejections(ext_abi):
+    """tgs_outputs_views, tgs_features_views: the array, then the streams, then view by view (sizes, grid limit, the frame's buffers).  A view
+    with P == 0 or R == 0 is zero-filled -- a device call -- so the views in front of a failing one ask for nothing here."""
+    lib, failures = ext_abi, []
+    streams = (_vp * 2)(None, None)
+    base = dict(streams=ctypes.cast(streams, _vp), n_streams=2, P=10, n_views=2, views=None, arr=None)
+    for fn, make, key, wants, needs in (("tgs_outputs_views", _extras, "extras", dict(out_alpha=X, out_depth=X), ("img_buffer", "geom_buffer", "binning_buffer")),
+                                        ("tgs_features_views", _feats, "feats", dict(features=X, out_features=X), ("img_buffer", "geom_buffer", "binning_buffer"))):
+        def run(label, code, text, vs=None, **over):
+            arr = over.pop(key, make(2, **wants))
+            a = {**base, "views": _ptr(_views(2) if vs is None else vs), "arr": _ptr(arr), **over}
+            _check(lib, failures, f"{fn}: {label}", getattr(lib, fn)(*a.values()), code, None if text is None else (f"{fn}: {text}" if code else text))
+        (_extras_array_rows if key == "extras" else _feats_array_rows)(run)
+        for over, n in ((dict(streams=None), 2), (dict(n_streams=0), 0), (dict(n_streams=-2), -2), (dict(n_streams=0, n_views=0, views=None), 0)):
+            run(f"streams: {over}", INVALID, MSG_STREAMS % n, **over)
+        run("streams: bad arguments win over a bad view", INVALID, MSG_STREAMS % 0, vs=_views(2, width=0), n_streams=0)
+        run("no views", 0, "", n_views=0, views=None, streams=None, **{key: None})
+        run("no array", 0, "", **{key: None})
+        run("no array: the views are not looked at", 0, "", vs=_views(2, width=0, img_buffer=None), **{key: None})
+        run("no view asks for anything", 0, "", vs=_views(2, width=0, img_buffer=None), **{key: make(2)})
+        if key == "feats":
+            run("features alone ask for nothing", 0, "", vs=_views(2, width=0), feats=_feats(2, features=X))
+            run("a gradient alone asks for nothing here", 0, "", vs=_views(2, width=0), feats=_feats(2, features=X, dL_dfeature_map=X, feature_scratch=X))
+        else:
+            run("gradients alone ask for nothing here", 0, "", vs=_views(2, width=0), extras=_extras(2, dL_dalpha=X, dL_ddepth=X, dz_scratch=X))
+            x = _extras(2, out_alpha=X, out_depth=X, dL_ddepth=X)
+            run("the array before the streams", INVALID, "view 0: dL_ddepth without dz_scratch", streams=None, n_streams=0, extras=x)
+        for k in (0, 1):                    # view 1 behind a view 0 that asks for nothing
+            arr = make(2, **wants)
+            if k == 1:
+                for f in ("out_alpha", "out_depth") if key == "extras" else ("out_features",):
+                    setattr(arr[0], f, None)
+            for f, bad in (("width", 0), ("height", -1), ("R", -1)):
+                vs = _views(2); setattr(vs[k], f, bad)
+                run(f"view {k}: {f} = {bad}", INVALID, f"view {k}: bad sizes", vs=vs, **{key: arr})
+            vs = _views(2); vs[k].R = -1; vs[k].img_buffer = None; vs[k].width = BIG
+            run(f"view {k}: sizes win", INVALID, f"view {k}: bad sizes", vs=vs, **{key: arr})
+            for f in ("width", "height"):
+                vs = _views(2); setattr(vs[k], f, BIG)
+                run(f"view {k}: {f} too large", INVALID, f"view {k}: image too large", vs=vs, **{key: arr})
+            vs = _views(2); vs[k].width = BIG; vs[k].img_buffer = None
+            run(f"view {k}: the image size wins over NULL pointers", INVALID, f"view {k}: image too large", vs=vs, **{key: arr})
+            for f in needs:
+                vs = _views(2); setattr(vs[k], f, None)
+                run(f"view {k}: {f} NULL", INVALID, f"view {k}: NULL required pointer", vs=vs, **{key: arr})
+        if key == "extras":
+            vs = _views(2); vs[0].img_buffer = None
+            run("alpha alone needs the image buffer", INVALID, "view 0: NULL required pointer", vs=vs, extras=_extras(2, out_alpha=X))
+    assert not failures, "\n".join(failures)
+
+
+def test_backward_render_views_extension_rejections(ext_abi):
+    """tgs_backward_render_views_extras_opt, tgs_backward_render_views_features_opt: the arrays (extras first), the streams, then the checks of
+    tgs_backward_render_views_opt behind the entry point's name -- without a view index, as there."""
+    lib, failures = ext_abi, []
+    streams = (_vp * 2)(None, None)
+    for fn, with_feats in (("tgs_backward_render_views_extras_opt", False), ("tgs_backward_render_views_features_opt", True)):
+        def run(label, code, text, vs=None, opt=None, **over):
+            extras, feats = over.pop("extras", None), over.pop("feats", None)
+            a = dict(streams=ctypes.cast(streams, _vp), n_streams=2, P=10, n_views=2, views=_ptr(_views(2, R=0) if vs is None else vs))
+            a.update(over)
+            tail = (_ptr(extras), _ptr(feats)) if with_feats else (_ptr(extras),)
+            got = getattr(lib, fn)(ctypes.byref(opt) if opt is not None else None, *a.values(), *tail)
+            _check(lib, failures, f"{fn}: {label}", got, code, None if text is None else (f"{fn}: {text}" if code else text))
+        _extras_array_rows(run)
+        if with_feats:
+            _feats_array_rows(run)
+            run("the extras are checked before the feats", INVALID, "view 0: dL_ddepth without dz_scratch", extras=_extras(2, dL_ddepth=X), feats=_feats(2, struct_size=8))
+        for over, n in ((dict(streams=None), 2), (dict(n_streams=0), 0), (dict(n_streams=-1), -1), (dict(n_streams=0, n_views=0, views=None), 0)):
+            run(f"streams: {over}", INVALID, MSG_STREAMS % n, **over)
+        run("streams: bad arguments win over a bad view", INVALID, MSG_STREAMS % 0, vs=_views(2, width=0), n_streams=0)
+        run("no views", 0, "", n_views=0, views=None, streams=None)
+        run("P == 0", 0, "", P=0, vs=_views(2, width=0, dL_dpix=None))
+        run("P == 0, with gradients", 0, "", P=0, vs=_views(2, width=0), extras=_extras(2, dL_dalpha=X, dL_ddepth=X, dz_scratch=X))
+        run("views without instances", 0, "", extras=_extras(2, dL_dalpha=X, dL_ddepth=X, dz_scratch=X))
+        run("views without instances, no arrays, options", 0, "", opt=_options(tile_bound=3))
+        arrays = [("no arrays", {}), ("extras", dict(extras=_extras(3, dL_dalpha=X, dL_ddepth=X, dz_scratch=X)))]
+        if with_feats:
+            arrays.append(("feats", dict(feats=_feats(3, features=X, dL_dfeature_map=X, feature_scratch=X))))
+            run("views without instances, feats", 0, "", feats=_feats(2, features=X, dL_dfeature_map=X, feature_scratch=X))
+        for aname, arrs in arrays:
+            for f, bad, text in [("R", -1, "bad sizes"), ("width", 0, "bad sizes"), ("height", 0, "bad sizes")] + [(p, None, MSG_NULL) for p in ("background", "binning_buffer", "img_buffer", "dL_dpix")]:
+                for k in (0, 2):            # (R == 0: a view without instances launches nothing, so later views are reached)
+                    vs = _views(3, R=0); setattr(vs[k], f, bad)
+                    run(f"{aname}: view {k}: {f}", INVALID, text, vs=vs, n_views=3, **arrs)
+            vs = _views(3, R=0); vs[0].R = -1; vs[0].dL_dpix = None
+            run(f"{aname}: sizes win over NULL pointers", INVALID, "bad sizes", vs=vs, n_views=3, **arrs)
+    assert not failures, "\n".join(failures)
+
+
+MSG_VIEW_RANGE = "view %d: bad sizes or NULL required pointer"
+
+
+def test_backward_batch_extension_range_rejections(ext_abi):
+    """tgs_backward_batch_depth_range, tgs_backward_batch_features_range: the array, the no-ops, the Gaussian range (behind the entry point's
+    name), then the views that take part.  Nothing is launched before every view has been read."""
+    lib, failures = ext_abi, []
+    # depth
+    fn = "tgs_backward_batch_depth_range"
+    on = dict(dL_ddepth=X, dz_scratch=X)
+
+    def run(label, code, text, vs=None, first=0, count=None, dL_dmean3D=X, **over):
+        extras = over.pop("extras", _extras(2, **on))
+        a = dict(stream=None, P=1000, n_views=2, views=_ptr(_views(2) if vs is None else vs))
+        a.update(over)
+        count = max(a["P"], 0) - first if count is None else count
+        got = lib.tgs_backward_batch_depth_range(*a.values(), _ptr(extras), dL_dmean3D, first, count)
+        _check(lib, failures, f"{fn}: {label}", got, code, None if text is None else (f"{fn}: {text}" if code else text))
+    _extras_array_rows(lambda label, code, text, **over: run(label, code, text.replace("P=10 ", "P=1000 "), **over) if "P" not in over or over["P"] else None)
+    run("extras: P < 0", INVALID, "bad sizes P=-1 n_views=2", P=-1, count=0)
+    run("the array is checked for an empty model as well", INVALID, "view 0: dL_ddepth without dz_scratch", P=0, extras=_extras(2, dL_ddepth=X))
+    run("P == 0", 0, "", P=0, dL_dmean3D=None)
+    run("no views", 0, "", n_views=0, views=None, first=3)
+    run("empty range", 0, "", first=3, count=0)
+    run("no array", 0, "", extras=None, first=3)
+    run("no view has dL_ddepth", 0, "", extras=_extras(2, dL_dalpha=X, out_depth=X), vs=_views(2, width=0, geom_buffer=None), dL_dmean3D=None)
+    run("no view has instances", 0, "", vs=_views(2, R=0, geom_buffer=None), dL_dmean3D=None)
+    run("rejected frames (R < 0) take no part", 0, "", vs=_views(2, R=-1, width=0))
+    for first, count in ((-256, 256), (0, -1), (100, 900), (256, 1000), (0, 300), (512, 300), (768, 233), (0, 1001)):
+        run(f"range {first} + {count}", INVALID, MSG_RANGE % (first, first, count, 1000), first=first, count=count)
+    run("the range wins over the views", INVALID, MSG_RANGE % (0, 0, 300, 1000), count=300, vs=_views(2, geom_buffer=None), dL_dmean3D=None)
+    run("the range is checked without a view that takes part", INVALID, MSG_RANGE % (0, 0, 300, 1000), count=300, extras=_extras(2))
+    for k in (0, 1):                        # (view 0 takes part and is in order: nothing is launched before the last view has been read)
+        for f, bad in [("width", 0), ("height", -1)] + [(p, None) for p in ("geom_buffer", "img_buffer", "radii", "viewmatrix")]:
+            vs = _views(2); setattr(vs[k], f, bad)
+            run(f"view {k}: {f}", INVALID, MSG_VIEW_RANGE % k, vs=vs)
+            run(f"view {k}: {f}, a range", INVALID, MSG_VIEW_RANGE % k, vs=vs, first=256, count=744)
+    run("dL_dmean3D NULL", INVALID, MSG_VIEW_RANGE % 0, dL_dmean3D=None)
+    x = _extras(2, **on); x[0].dL_ddepth = None
+    run("dL_dmean3D NULL: the first view that takes part", INVALID, MSG_VIEW_RANGE % 1, dL_dmean3D=None, extras=x)
+    # features
+    fn = "tgs_backward_batch_features_range"
+    on = dict(features=X, dL_dfeature_map=X, feature_scratch=X)
+
+    def runf(label, code, text, vs=None, first=0, count=None, dL_dfeatures=X, accumulate=0, **over):
+        feats = over.pop("feats", _feats(2, **on))
+        a = dict(stream=None, P=1000, n_views=2, views=_ptr(_views(2) if vs is None else vs))
+        a.update(over)
+        count = max(a["P"], 0) - first if count is None else count
+        got = lib.tgs_backward_batch_features_range(*a.values(), _ptr(feats), dL_dfeatures, accumulate, first, count)
+        _check(lib, failures, f"{fn}: {label}", got, code, None if text is None else (f"{fn}: {text}" if code else text))
+    _feats_array_rows(lambda label, code, text, **over: runf(label, code, text.replace("P=10 ", "P=1000 "), **over) if "P" not in over or over["P"] else None)
+    runf("the array is checked for an empty model as well", INVALID, "view 0: " + MSG_CHANNELS % 0, P=0, feats=_feats(2, C=0, **on))
+    runf("P == 0", 0, "", P=0, dL_dfeatures=None)
+    runf("no views", 0, "", n_views=0, views=None, first=3)
+    runf("empty range", 0, "", first=3, count=0)
+    runf("no array", 0, "", feats=None, first=3)
+    runf("no view takes part: not even C is known", 0, "", feats=_feats(2, C=0), first=3)
+    for acc, d in ((1, X), (1, None), (0, None)):       # (stored into a non-NULL dL_dfeatures, the range is zero-filled: a device call)
+        runf(f"no view has a gradient ({acc}, {d})", 0, "", feats=_feats(2, features=X, out_features=X), vs=_views(2, width=0, geom_buffer=None), accumulate=acc, dL_dfeatures=d)
+    runf("no view has instances", 0, "", vs=_views(2, R=0, geom_buffer=None), accumulate=1)
+    runf("rejected frames (R < 0) take no part", 0, "", vs=_views(2, R=-1, width=0), accumulate=1)
+    for first, count in ((-256, 256), (0, -1), (100, 900), (256, 1000), (0, 300), (512, 300), (768, 233), (0, 1001)):
+        runf(f"range {first} + {count}", INVALID, MSG_RANGE % (first, first, count, 1000), first=first, count=count)
+    runf("the range wins over dL_dfeatures", INVALID, MSG_RANGE % (0, 0, 300, 1000), count=300, dL_dfeatures=None)
+    runf("the range is checked without a gradient", INVALID, MSG_RANGE % (0, 0, 300, 1000), count=300, feats=_feats(2, features=X))
+    big = (1 << 31) - 1
+    runf("too large for one call", INVALID, f"range of {big} Gaussians x 16 channels is too large for one call", P=big, feats=_feats(2, C=16, **on))
+    runf("too large for one call, 13 channels", INVALID, f"range of {big} Gaussians x 13 channels is too large for one call", P=big, feats=_feats(2, C=13, **on))
+    runf("too large wins over dL_dfeatures", INVALID, f"range of {big} Gaussians x 16 channels is too large for one call", P=big, feats=_feats(2, C=16, **on), dL_dfeatures=None)
+    for acc in (0, 1):
+        runf(f"dL_dfeatures NULL ({acc})", INVALID, "view 0 has dL_dfeature_map but dL_dfeatures is NULL", dL_dfeatures=None, accumulate=acc)
+        runf(f"dL_dfeatures NULL, no instances ({acc})", INVALID, "view 0 has dL_dfeature_map but dL_dfeatures is NULL", dL_dfeatures=None, accumulate=acc, vs=_views(2, R=0))
+    f = _feats(2, **on); f[0].dL_dfeature_map = None
+    runf("dL_dfeatures NULL: the first view with a gradient", INVALID, "view 1 has dL_dfeature_map but dL_dfeatures is NULL", dL_dfeatures=None, feats=f)
+    for k in (0, 1):
+        for fld, bad in [("width", 0), ("height", -1)] + [(p, None) for p in ("geom_buffer", "img_buffer", "radii")]:
+            vs = _views(2); setattr(vs[k], fld, bad)
+            runf(f"view {k}: {fld}", INVALID, MSG_VIEW_RANGE % k, vs=vs)
+            runf(f"view {k}: {fld}, accumulate, a range", INVALID, MSG_VIEW_RANGE % k, vs=vs, first=256, count=744, accumulate=1)
+    vs = _views(2); vs[1].viewmatrix = vs[1].binning_buffer = None; vs[1].geom_buffer = None
+    runf("view 1: only what the pass reads is asked for", INVALID, MSG_VIEW_RANGE % 1, vs=vs)
+    assert not failures, "\n".join(failures)

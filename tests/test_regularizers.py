@@ -476,11 +476,14 @@ def test_gpu_three_training_steps_with_the_regulariser(gpu_device):
     L = {"points": t(cloud["means3D"]), "all_densities": t(np.log(op / (1 - op))), "scales": raw0.clone(), "quaternions": t(cloud["rotations"])}
     for p in L.values():
         p.requires_grad_(True)
-    colors = torch.rand(P, 3, device=dev)
+    # colours and target from a generator of the test's own (the cloud's seed): drawn from torch's global state they were whatever the tests
+    # before this one left, and for some states (2 of 40 tried) a gradient of the flat axis lands in (0, 1e-18), outside the bar's condition below
+    gen = torch.Generator(device=dev).manual_seed(21)
+    colors = torch.rand(P, 3, device=dev, generator=gen)
     lrs = {"points": 1.6e-4, "all_densities": 0.05, "scales": 0.005, "quaternions": 0.001}
     opt = FusedAdam([{"params": [p], "lr": lrs[n], "name": n} for n, p in L.items()], lr=0.0, eps=1e-15)
     cams = [scenes.orbit_camera(W, H, azimuth_deg=a) for a in (10.0, 130.0, 250.0)]
-    gt = torch.rand(3, H, W, device=dev)
+    gt = torch.rand(3, H, W, device=dev, generator=gen)
     recorded, selected, raw_grads = [], [], []
     for c in cams:
         rs = GaussianRasterizationSettings(image_height=H, image_width=W, tanfovx=c.tanfovx, tanfovy=c.tanfovy, bg=t(c.bg), scale_modifier=1.0, viewmatrix=t(c.viewmatrix),

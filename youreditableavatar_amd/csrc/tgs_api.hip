@@ -587,64 +587,169 @@ static int backward_render_impl(const Opts& opt, hipStream_t st, int P, const tg
                               dL_ddepth, dz_scratch, feat, P);
 }
 
-// element k of a caller's tgs_view_extras_t array (stride and valid prefix: the array's struct_size); fields beyond the caller's build read as NULL
-static int read_extras(const tgs_view_extras_t* base, int k, tgs_view_extras_t& out)
+// Element k of a caller's array of tgs_view_extras_t / tgs_view_features_t: the array's struct_size (its first element's) is the stride and the
+// valid prefix of every element; fields beyond the caller's build read as NULL / 0.  `min_size`: the end of the first field a caller must
+// have, `min_what` names it.  base == NULL: no view has any, every field reads as NULL.
+template <class T>
+static int read_element(const T* base, int k, T& out, const char* type, size_t min_size, const char* min_what)
 {
     memset(&out, 0, sizeof(out));
     if (!base) return TGS_OK;
     const size_t stride = base->struct_size;
-    if (stride < offsetof(tgs_view_extras_t, out_alpha) + sizeof(base->out_alpha))
-        return fail(TGS_ERR_INVALID, "tgs_view_extras_t: struct_size %zu is smaller than the first pointer field", stride);
+    if (stride < min_size) return fail(TGS_ERR_INVALID, "%s: struct_size %zu is smaller than %s", type, stride, min_what);
     memcpy(&out, (const char*)base + (size_t)k * stride, stride < sizeof(out) ? stride : sizeof(out));
-    if (out.struct_size != stride) return fail(TGS_ERR_INVALID, "view %d: tgs_view_extras_t.struct_size %u differs from the array's %zu", k, out.struct_size, stride);
+    if (out.struct_size != stride) return fail(TGS_ERR_INVALID, "view %d: %s.struct_size %u differs from the array's %zu", k, type, out.struct_size, stride);
+    return TGS_OK;
+}
+static int read_extras(const tgs_view_extras_t* base, int k, tgs_view_extras_t& out)
+{
+    if (int r = read_element(base, k, out, "tgs_view_extras_t", offsetof(tgs_view_extras_t, out_alpha) + sizeof(out.out_alpha), "the first pointer field")) return r;
     if (out.dL_ddepth && !out.dz_scratch) return fail(TGS_ERR_INVALID, "view %d: dL_ddepth without dz_scratch", k);
     return TGS_OK;
 }
-// the arguments the three *_views extras entry points share, checked before anything is enqueued
-static int check_extras_call(int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras)
-{
-    g_err[0] = 0;
-    if (P < 0 || n_views < 0) return fail(TGS_ERR_INVALID, "bad sizes P=%d n_views=%d", P, n_views);
-    if (n_views > 0 && !views) return fail(TGS_ERR_INVALID, "NULL required pointer (views)");
-    tgs_view_extras_t x;
-    for (int k = 0; k < n_views && extras; k++)
-        if (int r = read_extras(extras, k, x)) return r;
-    return TGS_OK;
-}
-
-// element k of a caller's tgs_view_features_t array, as read_extras reads the extras; an element TAKES PART when it has features, out_features
-// or dL_dfeature_map
+// an element TAKES PART when it has features, out_features or dL_dfeature_map
 static bool feats_part(const tgs_view_features_t& x) { return x.features || x.out_features || x.dL_dfeature_map; }
 static int read_feats(const tgs_view_features_t* base, int k, tgs_view_features_t& out)
 {
-    memset(&out, 0, sizeof(out));
-    if (!base) return TGS_OK;
-    const size_t stride = base->struct_size;
-    if (stride < offsetof(tgs_view_features_t, features) + sizeof(base->features))
-        return fail(TGS_ERR_INVALID, "tgs_view_features_t: struct_size %zu is smaller than the end of the features field", stride);
-    memcpy(&out, (const char*)base + (size_t)k * stride, stride < sizeof(out) ? stride : sizeof(out));
-    if (out.struct_size != stride) return fail(TGS_ERR_INVALID, "view %d: tgs_view_features_t.struct_size %u differs from the array's %zu", k, out.struct_size, stride);
+    if (int r = read_element(base, k, out, "tgs_view_features_t", offsetof(tgs_view_features_t, features) + sizeof(out.features), "the end of the features field")) return r;
     if (!feats_part(out)) return TGS_OK;
     if (out.C < 1 || out.C > TGS_FEATURE_MAX_CHANNELS) return fail(TGS_ERR_INVALID, "view %d: bad channel count C=%d (1 .. %d)", k, out.C, TGS_FEATURE_MAX_CHANNELS);
     if (!out.features) return fail(TGS_ERR_INVALID, "view %d: out_features / dL_dfeature_map without features", k);
     if (out.dL_dfeature_map && !out.feature_scratch) return fail(TGS_ERR_INVALID, "view %d: dL_dfeature_map without feature_scratch", k);
     return TGS_OK;
 }
-// the arguments the three *_views feature entry points share, checked before anything is enqueued; -> C and features of the elements that take
-// part (the model's: the same in all of them; C = 0: none takes part)
-static int check_feats_call(int P, int n_views, const tgs_view_t* views, const tgs_view_features_t* feats, int& C, const float*& features)
+
+// The arguments the entry points with a tgs_view_extras_t and / or a tgs_view_features_t array share, checked before anything is enqueued: the
+// sizes and the views, then every element of the extras, then every element of the feats (an array the call does not take: NULL).
+// -> C of the elements that take part (the features are the model's: C and the pointer are the same in all of them; 0: none takes part)
+static int check_views_call(int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras, const tgs_view_features_t* feats, int& C)
 {
     g_err[0] = 0;
-    C = 0; features = nullptr;
+    C = 0;
     if (P < 0 || n_views < 0) return fail(TGS_ERR_INVALID, "bad sizes P=%d n_views=%d", P, n_views);
     if (n_views > 0 && !views) return fail(TGS_ERR_INVALID, "NULL required pointer (views)");
-    tgs_view_features_t x;
+    tgs_view_extras_t x;
+    for (int k = 0; k < n_views && extras; k++)
+        if (int r = read_extras(extras, k, x)) return r;
+    tgs_view_features_t c;
+    const float* features = nullptr;
     for (int k = 0; k < n_views && feats; k++) {
-        if (int r = read_feats(feats, k, x)) return r;
-        if (!feats_part(x)) continue;
-        if (C == 0) { C = x.C; features = x.features; }
-        else if (x.C != C || x.features != features)
-            return fail(TGS_ERR_INVALID, "view %d: C=%d / features differ from an earlier view's (C=%d): the features are the model's, one tensor for all views", k, x.C, C);
+        if (int r = read_feats(feats, k, c)) return r;
+        if (!feats_part(c)) continue;
+        if (C == 0) { C = c.C; features = c.features; }
+        else if (c.C != C || c.features != features)
+            return fail(TGS_ERR_INVALID, "view %d: C=%d / features differ from an earlier view's (C=%d): the features are the model's, one tensor for all views", k, c.C, C);
+    }
+    return TGS_OK;
+}
+static int check_streams(void* const* streams, int n_streams, int n_views)
+{
+    if ((n_views > 0 && !streams) || n_streams <= 0) return fail(TGS_ERR_INVALID, "bad arguments (streams, n_streams=%d)", n_streams);
+    return TGS_OK;
+}
+
+// The per-pixel backward of several views, view k on streams[k % n_streams]: tgs_backward_render_views_opt and, with the views' extras and
+// feature elements (either array may be NULL: no view has any), its two extensions.  The arrays were checked by the caller.
+static int backward_render_views(const tgs_options_t* o, void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views,
+                                 const tgs_view_extras_t* extras, const tgs_view_features_t* feats)
+{
+    const Opts opt0 = resolve_options(o, true);
+    for (int k = 0; k < n_views; k++) {
+        tgs_view_extras_t x;
+        tgs_view_features_t f;
+        if (int r = read_extras(extras, k, x)) return r;
+        if (int r = read_feats(feats, k, f)) return r;
+        BwdArgs fa{};
+        fa.C = f.C; fa.features = f.features; fa.dL_dfeat_map = f.dL_dfeature_map; fa.feat_scratch = f.feature_scratch;
+        const int r = backward_render_impl(view_options(opt0, views[k]), (hipStream_t)streams[k % n_streams], P, views[k], x.dL_dalpha, x.dL_ddepth, x.dz_scratch,
+                                           f.dL_dfeature_map ? &fa : nullptr);
+        if (r < 0) return r;
+    }
+    return TGS_OK;
+}
+
+// tgs_backward_render_views_extras_opt / _features_opt, under their name `fn`: the arrays, then the streams, then the loop
+static int backward_render_views_checked(const char* fn, const tgs_options_t* o, void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views,
+                                         const tgs_view_extras_t* extras, const tgs_view_features_t* feats)
+{
+    int C;
+    if (int r = check_views_call(P, n_views, views, extras, feats, C)) return named(fn, r);
+    if (int r = check_streams(streams, n_streams, n_views)) return named(fn, r);
+    return named(fn, backward_render_views(o, streams, n_streams, P, n_views, views, extras, feats));
+}
+
+// The Gaussians [first, first + count) of a per-Gaussian pass over a batch: whole blocks of PRE_BLOCK, or the model's last ones
+static int check_gaussian_range(int P, int first, int count)
+{
+    if (first < 0 || count < 0 || first % PRE_BLOCK != 0 || (long long)first + count > P || ((first + count) % PRE_BLOCK != 0 && first + count != P))
+        return fail(TGS_ERR_INVALID, "Gaussian range [%d, %d + %d) must start and end on multiples of %d (or end at P = %d)", first, first, count, PRE_BLOCK, P);
+    return TGS_OK;
+}
+
+// ---- a finished frame, opened for reading (the extra outputs: depth, median, features; alpha and depth / features of a batch's views) ----
+// The one place that knows what such a call asks of a frame: P, R >= 0 and an image; with P == 0 or R == 0 nothing was blended (an empty
+// model writes no image state at all) and no buffer is looked at; otherwise the state buffers the call reads, and a tile grid that fits a
+// launch.  The callers say it in their own words and order: open_frame for the one-view calls, outputs_views for view k of a batch.
+struct Frame {
+    ViewArgs v; FrameBuffers fb;
+    bool sizes_ok, blended, buffers_ok, grid_ok;
+};
+static Frame frame_facts(int P, int width, int height, int64_t R, const void* geom, const void* binning, const void* img, bool image_only = false)
+{
+    Frame f{};
+    f.v = ViewArgs{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
+    f.sizes_ok = P >= 0 && R >= 0 && width > 0 && height > 0;
+    f.blended = P > 0 && R > 0;
+    f.buffers_ok = img && (image_only || (geom && binning));
+    f.grid_ok = f.sizes_ok && f.v.gx() <= 65535u && f.v.gy() <= 65535u;
+    if (f.sizes_ok && f.blended && f.buffers_ok && f.grid_ok) f.fb = carve_frame(GeomShape{(size_t)P, false, false}, f.v, R, geom, binning, img);
+    return f;
+}
+// one view's call `fn`; own_ptrs: the call's own pointers are all there.  -> 1: launch; 0: nothing was blended and nothing is launched (the
+// caller's fill stands); < 0: the error
+static int open_frame(Frame& f, const char* fn, int P, int width, int height, int64_t R, const void* geom, const void* binning, const void* img, bool own_ptrs)
+{
+    g_err[0] = 0;
+    f = frame_facts(P, width, height, R, geom, binning, img);
+    if (!f.sizes_ok) return fail(TGS_ERR_INVALID, "%s: bad sizes P=%d W=%d H=%d R=%lld", fn, P, width, height, (long long)R);
+    if (!f.blended) return 0;
+    if (!f.buffers_ok || !own_ptrs) return fail(TGS_ERR_INVALID, "%s: NULL required pointer", fn);
+    if (!f.grid_ok) return fail(TGS_ERR_INVALID, "%s: image too large", fn);
+    return 1;
+}
+// The extra outputs of several views of a finished tgs_forward_views call, view k on streams[k % n_streams]: alpha and depth (tgs_outputs_views)
+// and the feature map (tgs_features_views), under their name `fn` -- either array may be NULL: no view has any.  A view in which nothing was
+// blended has its outputs zero-filled.
+static int outputs_views(const char* fn, void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras,
+                         const tgs_view_features_t* feats)
+{
+    int C;
+    if (int r = check_views_call(P, n_views, views, extras, feats, C)) return named(fn, r);
+    if (int r = check_streams(streams, n_streams, n_views)) return named(fn, r);
+    for (int k = 0; k < n_views; k++) {
+        tgs_view_extras_t x;
+        tgs_view_features_t c;
+        if (int r = read_extras(extras, k, x)) return named(fn, r);
+        if (int r = read_feats(feats, k, c)) return named(fn, r);
+        if (!x.out_alpha && !x.out_depth && !c.out_features) continue;
+        const tgs_view_t& w = views[k];
+        hipStream_t st = (hipStream_t)streams[k % n_streams];
+        const Frame f = frame_facts(P, w.width, w.height, w.R, w.geom_buffer, w.binning_buffer, w.img_buffer, !x.out_depth && !c.out_features);
+        if (!f.sizes_ok) return fail(TGS_ERR_INVALID, "%s: view %d: bad sizes", fn, k);
+        if (!f.grid_ok) return fail(TGS_ERR_INVALID, "%s: view %d: image too large", fn, k);
+        const size_t N = f.v.N();
+        if (!f.blended) {
+            if (x.out_alpha) HIP_TRY(hipMemsetAsync(x.out_alpha, 0, N * sizeof(float), st));
+            if (x.out_depth) HIP_TRY(hipMemsetAsync(x.out_depth, 0, N * sizeof(float), st));
+            if (c.out_features) HIP_TRY(hipMemsetAsync(c.out_features, 0, (size_t)c.C * N * sizeof(float), st));
+            continue;
+        }
+        if (!f.buffers_ok) return fail(TGS_ERR_INVALID, "%s: view %d: NULL required pointer", fn, k);
+        if (x.out_alpha) launch_alpha(st, f.fb.s, N, x.out_alpha);
+        if (x.out_depth) launch_depth_fwd(st, f.fb.s, f.fb.b, w.width, w.height, f.v.gx(), (uint32_t)f.v.T(), x.out_depth);
+        if (c.out_features) launch_feat_fwd(st, f.fb.s, f.fb.b, w.width, w.height, f.v.gx(), (uint32_t)f.v.T(), P, c.C, c.features, c.out_features);   // (zero-fills the map first)
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(TGS_ERR_HIP, "%s: view %d: %s", fn, k, hipGetErrorString(e));
     }
     return TGS_OK;
 }
@@ -808,93 +913,72 @@ int tgs_frame_status(void* stream, const void* img_buffer, int64_t* num_rendered
     return TGS_OK;
 }
 
-int tgs_backward(void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height, const float* means3D,
-                 const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                 const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                 float tan_fovy, const int* radii, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
-                 const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-                 float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug)
+// The six one-view backward entry points differ in the upstream gradients they take, in their name, and in how strict they are about
+// outputs; the frame they differentiate and the gradients they write are one list, declared in include/tgs_raster.h six times (the compiler
+// holds these definitions against it) and spelled here once: as parameters, and as the arguments handed on to the one packing.
+#define TGS_BWD_FRAME_PARAMS                                                                                                               \
+    void *stream, int P, int D, int M, int64_t R, const float *background, int width, int height, const float *means3D, const float *shs,  \
+        const float *colors_precomp, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,        \
+        const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx, float tan_fovy, const int *radii,           \
+        const void *geom_buffer, const void *binning_buffer, const void *img_buffer, const float *dL_dpix
+#define TGS_BWD_FRAME_ARGS                                                                                                                 \
+    stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,         \
+        viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix
+#define TGS_BWD_GRAD_PARAMS                                                                                                                \
+    float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,         \
+        float *dL_dscale, float *dL_drot, int debug
+#define TGS_BWD_GRAD_ARGS dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug
+
+// the upstream gradients beside dL_dpix, with what each needs (BwdArgs says what they are); an entry point leaves out what it does not take
+struct Upstream {
+    const float* dL_dalpha = nullptr;
+    const float* dL_ddepth = nullptr; float* dz_scratch = nullptr;
+    int C = 0; const float* features = nullptr; const float* dL_dfeature_map = nullptr; float* feature_scratch = nullptr; float* dL_dfeatures = nullptr;
+};
+static int backward_packed(bool strict, const Opts& opt, int accumulate, TGS_BWD_FRAME_PARAMS, const Upstream& u, TGS_BWD_GRAD_PARAMS)
 {
-    return backward_impl(true, resolve_options(nullptr), 0, (hipStream_t)stream, debug,
+    BwdArgs a{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, u.dL_dalpha};
+    a.dL_ddepth = u.dL_ddepth; a.dz_scratch = u.dL_ddepth ? u.dz_scratch : nullptr;
+    a.C = u.C; a.features = u.features; a.dL_dfeat_map = u.dL_dfeature_map; a.feat_scratch = u.feature_scratch; a.dL_dfeatures = u.dL_dfeatures;
+    return backward_impl(strict, opt, accumulate ? 1 : 0, (hipStream_t)stream, debug,
                          Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
-                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy},
-                         BwdArgs{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot});
+                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy}, a);
 }
 
-int tgs_backward_opt(const tgs_options_t* o, int accumulate, void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height,
-                     const float* means3D, const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                     const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                     const int* radii, const void* geom_buffer, const void* binning_buffer, const void* img_buffer, const float* dL_dpix, float* dL_dmean2D,
-                     float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                     int debug)
+int tgs_backward(TGS_BWD_FRAME_PARAMS, TGS_BWD_GRAD_PARAMS)
 {
-    return backward_impl(false, resolve_options(o), accumulate ? 1 : 0, (hipStream_t)stream, debug,
-                         Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
-                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy},
-                         BwdArgs{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot});
+    return backward_packed(true, resolve_options(nullptr), 0, TGS_BWD_FRAME_ARGS, Upstream{}, TGS_BWD_GRAD_ARGS);
 }
 
-int tgs_backward_alpha_opt(const tgs_options_t* o, int accumulate, void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height,
-                           const float* means3D, const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                           const int* radii, const void* geom_buffer, const void* binning_buffer, const void* img_buffer, const float* dL_dpix, const float* dL_dalpha,
-                           float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                           float* dL_drot, int debug)
+int tgs_backward_accumulate(TGS_BWD_FRAME_PARAMS, TGS_BWD_GRAD_PARAMS)
 {
-    return named("tgs_backward_alpha_opt", backward_impl(false, resolve_options(o), accumulate ? 1 : 0, (hipStream_t)stream, debug,
-                         Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
-                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy},
-                         BwdArgs{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
-                                 dL_dalpha}));
+    return backward_packed(true, resolve_options(nullptr), 1, TGS_BWD_FRAME_ARGS, Upstream{}, TGS_BWD_GRAD_ARGS);
 }
 
-int tgs_backward_depth_opt(const tgs_options_t* o, int accumulate, void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height,
-                           const float* means3D, const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                           const int* radii, const void* geom_buffer, const void* binning_buffer, const void* img_buffer, const float* dL_dpix, const float* dL_dalpha,
-                           const float* dL_ddepth, float* dz_scratch,
-                           float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                           float* dL_drot, int debug)
+int tgs_backward_opt(const tgs_options_t* o, int accumulate, TGS_BWD_FRAME_PARAMS, TGS_BWD_GRAD_PARAMS)
 {
-    BwdArgs a{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dalpha};
-    a.dL_ddepth = dL_ddepth; a.dz_scratch = dL_ddepth ? dz_scratch : nullptr;
-    return named("tgs_backward_depth_opt", backward_impl(false, resolve_options(o), accumulate ? 1 : 0, (hipStream_t)stream, debug,
-                         Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
-                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy}, a));
+    return backward_packed(false, resolve_options(o), accumulate, TGS_BWD_FRAME_ARGS, Upstream{}, TGS_BWD_GRAD_ARGS);
 }
 
-int tgs_backward_features_opt(const tgs_options_t* o, int accumulate, void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height,
-                              const float* means3D, const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                              const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                              const int* radii, const void* geom_buffer, const void* binning_buffer, const void* img_buffer, const float* dL_dpix, const float* dL_dalpha,
-                              const float* dL_ddepth, float* dz_scratch,
-                              int C, const float* features, const float* dL_dfeature_map, float* feature_scratch, float* dL_dfeatures,
-                              float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                              float* dL_drot, int debug)
+int tgs_backward_alpha_opt(const tgs_options_t* o, int accumulate, TGS_BWD_FRAME_PARAMS, const float* dL_dalpha, TGS_BWD_GRAD_PARAMS)
 {
-    if (!dL_dfeature_map)                                   // exactly the depth call: the other four arguments are not looked at
-        return tgs_backward_depth_opt(o, accumulate, stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
-                                      cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dalpha,
-                                      dL_ddepth, dz_scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug);
-    BwdArgs a{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dalpha};
-    a.dL_ddepth = dL_ddepth; a.dz_scratch = dL_ddepth ? dz_scratch : nullptr;
-    a.C = C; a.features = features; a.dL_dfeat_map = dL_dfeature_map; a.feat_scratch = feature_scratch; a.dL_dfeatures = dL_dfeatures;
-    return named("tgs_backward_features_opt", backward_impl(false, resolve_options(o), accumulate ? 1 : 0, (hipStream_t)stream, debug,
-                         Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
-                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy}, a));
+    return named("tgs_backward_alpha_opt", backward_packed(false, resolve_options(o), accumulate, TGS_BWD_FRAME_ARGS, Upstream{dL_dalpha}, TGS_BWD_GRAD_ARGS));
 }
 
-int tgs_backward_accumulate(void* stream, int P, int D, int M, int64_t R, const float* background, int width, int height, const float* means3D,
-                            const float* shs, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                            const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                            float tan_fovy, const int* radii, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
-                            const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-                            float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug)
+int tgs_backward_depth_opt(const tgs_options_t* o, int accumulate, TGS_BWD_FRAME_PARAMS, const float* dL_dalpha, const float* dL_ddepth, float* dz_scratch,
+                           TGS_BWD_GRAD_PARAMS)
 {
-    return backward_impl(true, resolve_options(nullptr), 1, (hipStream_t)stream, debug,
-                         Model{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp},
-                         ViewArgs{background, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy},
-                         BwdArgs{R, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot});
+    return named("tgs_backward_depth_opt",
+                 backward_packed(false, resolve_options(o), accumulate, TGS_BWD_FRAME_ARGS, Upstream{dL_dalpha, dL_ddepth, dz_scratch}, TGS_BWD_GRAD_ARGS));
+}
+
+int tgs_backward_features_opt(const tgs_options_t* o, int accumulate, TGS_BWD_FRAME_PARAMS, const float* dL_dalpha, const float* dL_ddepth, float* dz_scratch,
+                              int C, const float* features, const float* dL_dfeature_map, float* feature_scratch, float* dL_dfeatures, TGS_BWD_GRAD_PARAMS)
+{
+    // without a map this IS the depth call -- the other four arguments are not looked at -- and it says so in its errors
+    return named(dL_dfeature_map ? "tgs_backward_features_opt" : "tgs_backward_depth_opt",
+                 backward_packed(false, resolve_options(o), accumulate, TGS_BWD_FRAME_ARGS,
+                                 Upstream{dL_dalpha, dL_ddepth, dz_scratch, C, features, dL_dfeature_map, feature_scratch, dL_dfeatures}, TGS_BWD_GRAD_ARGS));
 }
 
 void tgs_state_sizes(int P, int width, int height, int has_sh, int has_scale_rot, int64_t r_capacity, size_t sizes3[3])
@@ -989,71 +1073,30 @@ int tgs_backward_render_views_opt(const tgs_options_t* o, void* const* streams, 
 {
     if (n_views == 0) return TGS_OK;
     if (!streams || n_streams <= 0 || n_views < 0 || !views) return fail(TGS_ERR_INVALID, "bad arguments");
-    const Opts opt0 = resolve_options(o, true);
-    for (int k = 0; k < n_views; k++) {
-        const int r = backward_render_impl(view_options(opt0, views[k]), (hipStream_t)streams[k % n_streams], P, views[k]);
-        if (r < 0) return r;
-    }
-    return TGS_OK;
+    return backward_render_views(o, streams, n_streams, P, n_views, views, nullptr, nullptr);
 }
 
 size_t tgs_sizeof_view_extras(void) { return sizeof(tgs_view_extras_t); }
 
 int tgs_outputs_views(void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras)
 {
-    static const char* fn = "tgs_outputs_views";
-    if (int r = check_extras_call(P, n_views, views, extras)) return named(fn, r);
-    if ((n_views > 0 && !streams) || n_streams <= 0) return named(fn, fail(TGS_ERR_INVALID, "bad arguments (streams, n_streams=%d)", n_streams));
-    if (!extras) return TGS_OK;
-    for (int k = 0; k < n_views; k++) {
-        tgs_view_extras_t x;
-        if (int r = read_extras(extras, k, x)) return named(fn, r);
-        if (!x.out_alpha && !x.out_depth) continue;
-        const tgs_view_t& w = views[k];
-        hipStream_t st = (hipStream_t)streams[k % n_streams];
-        if (w.width <= 0 || w.height <= 0 || w.R < 0) return named(fn, fail(TGS_ERR_INVALID, "view %d: bad sizes", k));
-        const ViewArgs v = view_args(w);
-        if (v.gx() > 65535u || v.gy() > 65535u) return named(fn, fail(TGS_ERR_INVALID, "view %d: image too large", k));
-        const size_t bytes = v.N() * sizeof(float);
-        if (P == 0 || w.R == 0) {                           // nothing was blended (an empty model writes no image state at all)
-            if (x.out_alpha) HIP_TRY(hipMemsetAsync(x.out_alpha, 0, bytes, st));
-            if (x.out_depth) HIP_TRY(hipMemsetAsync(x.out_depth, 0, bytes, st));
-            continue;
-        }
-        if (!w.img_buffer || (x.out_depth && (!w.geom_buffer || !w.binning_buffer))) return named(fn, fail(TGS_ERR_INVALID, "view %d: NULL required pointer", k));
-        const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, w.R, w.geom_buffer, w.binning_buffer, w.img_buffer);
-        if (x.out_alpha) launch_alpha(st, fb.s, v.N(), x.out_alpha);
-        if (x.out_depth) launch_depth_fwd(st, fb.s, fb.b, w.width, w.height, v.gx(), (uint32_t)v.T(), x.out_depth);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(TGS_ERR_HIP, "%s: view %d: %s", fn, k, hipGetErrorString(e));
-    }
-    return TGS_OK;
+    return outputs_views("tgs_outputs_views", streams, n_streams, P, n_views, views, extras, nullptr);
 }
 
 int tgs_backward_render_views_extras_opt(const tgs_options_t* o, void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views,
                                          const tgs_view_extras_t* extras)
 {
-    static const char* fn = "tgs_backward_render_views_extras_opt";
-    if (int r = check_extras_call(P, n_views, views, extras)) return named(fn, r);
-    if ((n_views > 0 && !streams) || n_streams <= 0) return named(fn, fail(TGS_ERR_INVALID, "bad arguments (streams, n_streams=%d)", n_streams));
-    const Opts opt0 = resolve_options(o, true);
-    for (int k = 0; k < n_views; k++) {
-        tgs_view_extras_t x;
-        if (int r = read_extras(extras, k, x)) return named(fn, r);
-        const int r = backward_render_impl(view_options(opt0, views[k]), (hipStream_t)streams[k % n_streams], P, views[k], x.dL_dalpha, x.dL_ddepth, x.dz_scratch);
-        if (r < 0) return named(fn, r);
-    }
-    return TGS_OK;
+    return backward_render_views_checked("tgs_backward_render_views_extras_opt", o, streams, n_streams, P, n_views, views, extras, nullptr);
 }
 
 int tgs_backward_batch_depth_range(void* stream, int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras, float* dL_dmean3D, int first, int count)
 {
     static const char* fn = "tgs_backward_batch_depth_range";
     hipStream_t st = (hipStream_t)stream;
-    if (int r = check_extras_call(P, n_views, views, extras)) return named(fn, r);
+    int C;
+    if (int r = check_views_call(P, n_views, views, extras, nullptr, C)) return named(fn, r);
     if (P == 0 || n_views == 0 || count == 0 || !extras) return TGS_OK;
-    if (first < 0 || count < 0 || first % PRE_BLOCK != 0 || (long long)first + count > P || ((first + count) % PRE_BLOCK != 0 && first + count != P))
-        return fail(TGS_ERR_INVALID, "%s: Gaussian range [%d, %d + %d) must start and end on multiples of %d (or end at P = %d)", fn, first, first, count, PRE_BLOCK, P);
+    if (int r = check_gaussian_range(P, first, count)) return named(fn, r);
     DepthViews dv;
     memset(&dv, 0, sizeof(dv));
     auto flush = [&]() -> int {
@@ -1082,54 +1125,13 @@ size_t tgs_sizeof_view_features(void) { return sizeof(tgs_view_features_t); }
 
 int tgs_features_views(void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_features_t* feats)
 {
-    static const char* fn = "tgs_features_views";
-    int C; const float* features;
-    if (int r = check_feats_call(P, n_views, views, feats, C, features)) return named(fn, r);
-    if ((n_views > 0 && !streams) || n_streams <= 0) return named(fn, fail(TGS_ERR_INVALID, "bad arguments (streams, n_streams=%d)", n_streams));
-    if (!feats) return TGS_OK;
-    for (int k = 0; k < n_views; k++) {
-        tgs_view_features_t x;
-        if (int r = read_feats(feats, k, x)) return named(fn, r);
-        if (!x.out_features) continue;
-        const tgs_view_t& w = views[k];
-        hipStream_t st = (hipStream_t)streams[k % n_streams];
-        if (w.width <= 0 || w.height <= 0 || w.R < 0) return named(fn, fail(TGS_ERR_INVALID, "view %d: bad sizes", k));
-        const ViewArgs v = view_args(w);
-        if (v.gx() > 65535u || v.gy() > 65535u) return named(fn, fail(TGS_ERR_INVALID, "view %d: image too large", k));
-        if (P == 0 || w.R == 0) {                           // nothing was blended (an empty model writes no image state at all)
-            HIP_TRY(hipMemsetAsync(x.out_features, 0, (size_t)x.C * v.N() * sizeof(float), st));
-            continue;
-        }
-        if (!w.img_buffer || !w.geom_buffer || !w.binning_buffer) return named(fn, fail(TGS_ERR_INVALID, "view %d: NULL required pointer", k));
-        const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, w.R, w.geom_buffer, w.binning_buffer, w.img_buffer);
-        launch_feat_fwd(st, fb.s, fb.b, w.width, w.height, v.gx(), (uint32_t)v.T(), P, x.C, x.features, x.out_features);   // (zero-fills the map first)
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(TGS_ERR_HIP, "%s: view %d: %s", fn, k, hipGetErrorString(e));
-    }
-    return TGS_OK;
+    return outputs_views("tgs_features_views", streams, n_streams, P, n_views, views, nullptr, feats);
 }
 
 int tgs_backward_render_views_features_opt(const tgs_options_t* o, void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views,
                                            const tgs_view_extras_t* extras, const tgs_view_features_t* feats)
 {
-    static const char* fn = "tgs_backward_render_views_features_opt";
-    int C; const float* features;
-    if (int r = check_extras_call(P, n_views, views, extras)) return named(fn, r);
-    if (int r = check_feats_call(P, n_views, views, feats, C, features)) return named(fn, r);
-    if ((n_views > 0 && !streams) || n_streams <= 0) return named(fn, fail(TGS_ERR_INVALID, "bad arguments (streams, n_streams=%d)", n_streams));
-    const Opts opt0 = resolve_options(o, true);
-    for (int k = 0; k < n_views; k++) {
-        tgs_view_extras_t x;
-        tgs_view_features_t f;
-        if (int r = read_extras(extras, k, x)) return named(fn, r);
-        if (int r = read_feats(feats, k, f)) return named(fn, r);
-        BwdArgs fa{};
-        fa.C = f.C; fa.features = f.features; fa.dL_dfeat_map = f.dL_dfeature_map; fa.feat_scratch = f.feature_scratch;
-        const int r = backward_render_impl(view_options(opt0, views[k]), (hipStream_t)streams[k % n_streams], P, views[k], x.dL_dalpha, x.dL_ddepth, x.dz_scratch,
-                                           f.dL_dfeature_map ? &fa : nullptr);
-        if (r < 0) return named(fn, r);
-    }
-    return TGS_OK;
+    return backward_render_views_checked("tgs_backward_render_views_features_opt", o, streams, n_streams, P, n_views, views, extras, feats);
 }
 
 int tgs_backward_batch_features_range(void* stream, int P, int n_views, const tgs_view_t* views, const tgs_view_features_t* feats, float* dL_dfeatures,
@@ -1137,11 +1139,10 @@ int tgs_backward_batch_features_range(void* stream, int P, int n_views, const tg
 {
     static const char* fn = "tgs_backward_batch_features_range";
     hipStream_t st = (hipStream_t)stream;
-    int C; const float* features;
-    if (int r = check_feats_call(P, n_views, views, feats, C, features)) return named(fn, r);
+    int C;
+    if (int r = check_views_call(P, n_views, views, nullptr, feats, C)) return named(fn, r);
     if (P == 0 || n_views == 0 || count == 0 || !feats || C == 0) return TGS_OK;
-    if (first < 0 || count < 0 || first % PRE_BLOCK != 0 || (long long)first + count > P || ((first + count) % PRE_BLOCK != 0 && first + count != P))
-        return fail(TGS_ERR_INVALID, "%s: Gaussian range [%d, %d + %d) must start and end on multiples of %d (or end at P = %d)", fn, first, first, count, PRE_BLOCK, P);
+    if (int r = check_gaussian_range(P, first, count)) return named(fn, r);
     if ((unsigned long long)count * (unsigned)((C + 3) / 4) > 0xffffff00ull) return fail(TGS_ERR_INVALID, "%s: range of %d Gaussians x %d channels is too large for one call", fn, count, C);
     // the views that take part: a gradient of the map, and instances (R == 0: the per-pixel backward launched nothing and the scratch was not filled)
     int n_part = 0;
@@ -1191,24 +1192,30 @@ int tgs_backward_render(void* stream, int P, int64_t R, const float* background,
     return tgs_backward_render_opt(nullptr, stream, P, R, background, width, height, binning_buffer, img_buffer, dL_dpix);
 }
 
-int tgs_backward_render_opt(const tgs_options_t* o, void* stream, int P, int64_t R, const float* background, int width, int height, const void* binning_buffer,
-                            const void* img_buffer, const float* dL_dpix)
+// tgs_backward_render[_alpha]_opt: their arguments as the one view of backward_render_impl
+static tgs_view_t render_view(int64_t R, const float* background, int width, int height, const void* binning_buffer, const void* img_buffer, const float* dL_dpix)
 {
     tgs_view_t v;
     memset(&v, 0, sizeof(v));
     v.width = width; v.height = height; v.R = R; v.background = background; v.binning_buffer = binning_buffer; v.img_buffer = img_buffer; v.dL_dpix = dL_dpix;
-    return backward_render_impl(resolve_options(o), (hipStream_t)stream, P, v);
+    return v;
+}
+
+int tgs_backward_render_opt(const tgs_options_t* o, void* stream, int P, int64_t R, const float* background, int width, int height, const void* binning_buffer,
+                            const void* img_buffer, const float* dL_dpix)
+{
+    return backward_render_impl(resolve_options(o), (hipStream_t)stream, P, render_view(R, background, width, height, binning_buffer, img_buffer, dL_dpix));
 }
 
 int tgs_backward_render_alpha_opt(const tgs_options_t* o, void* stream, int P, int64_t R, const float* background, int width, int height,
                                   const void* binning_buffer, const void* img_buffer, const float* dL_dpix, const float* dL_dalpha)
 {
-    tgs_view_t v;
-    memset(&v, 0, sizeof(v));
-    v.width = width; v.height = height; v.R = R; v.background = background; v.binning_buffer = binning_buffer; v.img_buffer = img_buffer; v.dL_dpix = dL_dpix;
-    return named("tgs_backward_render_alpha_opt", backward_render_impl(resolve_options(o), (hipStream_t)stream, P, v, dL_dalpha));
+    return named("tgs_backward_render_alpha_opt", backward_render_impl(resolve_options(o), (hipStream_t)stream, P,
+                                                                       render_view(R, background, width, height, binning_buffer, img_buffer, dL_dpix), dL_dalpha));
 }
 
+// tgs_alpha stays apart from open_frame: it reads the image buffer alone, of a frame it knows neither P nor R of (so there is no "nothing
+// was blended"), and its launch is linear in the pixels: no tile grid, no grid limit
 int tgs_alpha(void* stream, int width, int height, const void* img_buffer, float* out_alpha)
 {
     g_err[0] = 0;
@@ -1218,77 +1225,57 @@ int tgs_alpha(void* stream, int width, int height, const void* img_buffer, float
     ImgState s;
     img_carve(s, (char*)img_buffer, v.N(), v.T());
     launch_alpha((hipStream_t)stream, s, v.N(), out_alpha);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(TGS_ERR_HIP, "tgs_alpha: %s", hipGetErrorString(e));
-    return TGS_OK;
+    return hip_status("tgs_alpha");
 }
 
 int tgs_depth(void* stream, int P, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* img_buffer, float* out_depth)
 {
-    g_err[0] = 0;
-    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "tgs_depth: bad sizes P=%d W=%d H=%d R=%lld", P, width, height, (long long)R);
-    if (P == 0 || R == 0) return TGS_OK;                    // nothing was blended: the depth is zero and nothing is launched (the caller's zeros stand)
-    if (!geom_buffer || !binning_buffer || !img_buffer || !out_depth) return fail(TGS_ERR_INVALID, "tgs_depth: NULL required pointer");
-    const ViewArgs v{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
-    if (v.gx() > 65535u || v.gy() > 65535u) return fail(TGS_ERR_INVALID, "tgs_depth: image too large");
-    const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, R, geom_buffer, binning_buffer, img_buffer);
-    launch_depth_fwd((hipStream_t)stream, fb.s, fb.b, width, height, v.gx(), (uint32_t)v.T(), out_depth);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(TGS_ERR_HIP, "tgs_depth: %s", hipGetErrorString(e));
-    return TGS_OK;
+    Frame f;                                                // nothing blended: the depth is zero (the caller's zeros stand)
+    const int go = open_frame(f, "tgs_depth", P, width, height, R, geom_buffer, binning_buffer, img_buffer, out_depth != nullptr);
+    if (go <= 0) return go;
+    launch_depth_fwd((hipStream_t)stream, f.fb.s, f.fb.b, width, height, f.v.gx(), (uint32_t)f.v.T(), out_depth);
+    return hip_status("tgs_depth");
 }
 
 int tgs_median(void* stream, int P, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
                float* out_depth, int32_t* out_index, int32_t* out_pos)
 {
-    g_err[0] = 0;
-    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "tgs_median: bad sizes P=%d W=%d H=%d R=%lld", P, width, height, (long long)R);
-    if (P == 0 || R == 0) return TGS_OK;                    // nothing was blended: no pixel has a median entry and nothing is launched (the caller's 0 / -1 / 0 stand)
-    if (!geom_buffer || !binning_buffer || !img_buffer || !out_depth || !out_index || !out_pos) return fail(TGS_ERR_INVALID, "tgs_median: NULL required pointer");
-    const ViewArgs v{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
-    if (v.gx() > 65535u || v.gy() > 65535u) return fail(TGS_ERR_INVALID, "tgs_median: image too large");
-    const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, R, geom_buffer, binning_buffer, img_buffer);
-    launch_median_fwd((hipStream_t)stream, fb.s, fb.b, width, height, v.gx(), (uint32_t)v.T(), out_depth, out_index, out_pos);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(TGS_ERR_HIP, "tgs_median: %s", hipGetErrorString(e));
-    return TGS_OK;
+    Frame f;                                                // nothing blended: no pixel has a median entry (the caller's 0 / -1 / 0 stand)
+    const int go = open_frame(f, "tgs_median", P, width, height, R, geom_buffer, binning_buffer, img_buffer, out_depth && out_index && out_pos);
+    if (go <= 0) return go;
+    launch_median_fwd((hipStream_t)stream, f.fb.s, f.fb.b, width, height, f.v.gx(), (uint32_t)f.v.T(), out_depth, out_index, out_pos);
+    return hip_status("tgs_median");
 }
 
 int tgs_backward_median(void* stream, int P, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
                         const float* viewmatrix, const int* radii, const int32_t* median_pos, const float* dL_dmedian_depth, float* dz_scratch, float* dL_dmean3D)
 {
+    static const char* fn = "tgs_backward_median";
     hipStream_t st = (hipStream_t)stream;
-    g_err[0] = 0;
-    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "tgs_backward_median: bad sizes P=%d W=%d H=%d R=%lld", P, width, height, (long long)R);
-    if (P == 0 || R == 0) return TGS_OK;                    // no pixel has a median entry: nothing to add
-    if (!geom_buffer || !binning_buffer || !img_buffer || !viewmatrix || !radii || !median_pos || !dL_dmedian_depth || !dz_scratch || !dL_dmean3D)
-        return fail(TGS_ERR_INVALID, "tgs_backward_median: NULL required pointer");
-    const ViewArgs v{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
-    if (v.gx() > 65535u || v.gy() > 65535u) return fail(TGS_ERR_INVALID, "tgs_backward_median: image too large");
-    const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, R, geom_buffer, binning_buffer, img_buffer);
+    Frame f;                                                // nothing blended: no pixel has a median entry, nothing to add
+    const int go = open_frame(f, fn, P, width, height, R, geom_buffer, binning_buffer, img_buffer,
+                              viewmatrix && radii && median_pos && dL_dmedian_depth && dz_scratch && dL_dmean3D);
+    if (go <= 0) return go;
     if (int r = stage(st, TGS_STAGE_RENDER_BWD, "median_bwd", 0, [&] {
-            launch_median_bwd(st, fb.s, fb.b, width, height, v.gx(), (uint32_t)v.T(), (size_t)R, median_pos, dL_dmedian_depth, dz_scratch); }))
-        return named("tgs_backward_median", r);
+            launch_median_bwd(st, f.fb.s, f.fb.b, width, height, f.v.gx(), (uint32_t)f.v.T(), (size_t)R, median_pos, dL_dmedian_depth, dz_scratch); }))
+        return named(fn, r);
     // dz . (third row of the view transform), added behind whatever the main backward stored or accumulated on this stream
-    return named("tgs_backward_median", stage(st, TGS_STAGE_PREPROCESS_BWD, "median_bwd_gauss", 0, [&] {
-        launch_depth_bwd_gauss(st, P, fb.s.meta, radii, fb.g, viewmatrix, dz_scratch, dL_dmean3D); }));
+    return named(fn, stage(st, TGS_STAGE_PREPROCESS_BWD, "median_bwd_gauss", 0, [&] {
+        launch_depth_bwd_gauss(st, P, f.fb.s.meta, radii, f.fb.g, viewmatrix, dz_scratch, dL_dmean3D); }));
 }
 
 int tgs_features(void* stream, int P, int C, int width, int height, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
                  const float* features, float* out)
 {
-    g_err[0] = 0;
-    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(TGS_ERR_INVALID, "tgs_features: bad sizes P=%d W=%d H=%d R=%lld", P, width, height, (long long)R);
-    if (C < 1 || C > TGS_FEATURE_MAX_CHANNELS) return fail(TGS_ERR_INVALID, "tgs_features: bad channel count C=%d (1 .. %d)", C, TGS_FEATURE_MAX_CHANNELS);
-    if (P == 0 || R == 0) return TGS_OK;                    // nothing was blended: the map is zero and nothing is launched (the caller's zeros stand)
-    if (!geom_buffer || !binning_buffer || !img_buffer || !features || !out) return fail(TGS_ERR_INVALID, "tgs_features: NULL required pointer");
-    const ViewArgs v{nullptr, width, height, nullptr, nullptr, nullptr, 0.f, 0.f};
-    if (v.gx() > 65535u || v.gy() > 65535u) return fail(TGS_ERR_INVALID, "tgs_features: image too large");
-    const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, v, R, geom_buffer, binning_buffer, img_buffer);
-    launch_feat_fwd((hipStream_t)stream, fb.s, fb.b, width, height, v.gx(), (uint32_t)v.T(), P, C, features, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(TGS_ERR_HIP, "tgs_features: %s", hipGetErrorString(e));
-    return TGS_OK;
+    static const char* fn = "tgs_features";
+    Frame f;                                                // nothing blended: the map is zero (the caller's zeros stand)
+    // (the channel count is looked at behind the sizes and in front of everything else: an empty model with C = 0 is an error)
+    const bool bad_C = C < 1 || C > TGS_FEATURE_MAX_CHANNELS;
+    const int go = open_frame(f, fn, P, width, height, R, geom_buffer, binning_buffer, img_buffer, features && out);
+    if (f.sizes_ok && bad_C) return fail(TGS_ERR_INVALID, "%s: bad channel count C=%d (1 .. %d)", fn, C, TGS_FEATURE_MAX_CHANNELS);
+    if (go <= 0) return go;
+    launch_feat_fwd((hipStream_t)stream, f.fb.s, f.fb.b, width, height, f.v.gx(), (uint32_t)f.v.T(), P, C, features, out);
+    return hip_status(fn);
 }
 
 int tgs_backward_batch(void* stream, int P, int D, int M, int n_views, const tgs_view_t* views, const float* means3D, const float* shs,
@@ -1316,8 +1303,7 @@ int tgs_backward_batch_range_planes(void* stream, int P, int D, int M, int n_vie
     g_err[0] = 0;
     if (P == 0 || n_views == 0 || count == 0) return TGS_OK;
     if (P < 0 || n_views < 0 || !views) return fail(TGS_ERR_INVALID, "bad sizes");
-    if (first < 0 || count < 0 || first % PRE_BLOCK != 0 || (long long)first + count > P || ((first + count) % PRE_BLOCK != 0 && first + count != P))
-        return fail(TGS_ERR_INVALID, "Gaussian range [%d, %d + %d) must start and end on multiples of %d (or end at P = %d)", first, first, count, PRE_BLOCK, P);
+    if (int r = check_gaussian_range(P, first, count)) return r;
     const Model m{P, D, M, means3D, shs, nullptr, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
     const bool has_sh = m.has_sh(), has_sr = m.has_sr();
     if (int r = check_model(m, MODEL_BATCH_BACKWARD)) return r;

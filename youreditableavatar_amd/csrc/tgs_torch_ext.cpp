@@ -129,14 +129,13 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
 {
     // grad_out_median (extension keyword): upstream gradient of the median depth (median_from_state), [1,H,W] or [H,W], with median_pos, the int32 map
     // [1,H,W] that median_from_state returned for this frame; None launches no median kernel, a tensor runs tgs_backward_median behind the main call
-    // (whichever of the four it is) and adds its share into the returned dL_dmeans3D.  No other gradient gets anything from it.
+    // and adds its share into the returned dL_dmeans3D.  No other gradient gets anything from it.
     // grad_out_features (extension keyword): upstream gradient of the feature map (features_from_state), [C,H,W], with features [P,C]; None launches no
-    // feature kernel and returns today's tuple, a tensor goes to tgs_backward_features_opt (with grad_out_alpha / grad_out_depth or without) together with
-    // a scratch of R * C floats allocated here, and dL_dfeatures[P,C] is appended to the tuple.
+    // feature kernel and returns today's tuple, a tensor travels with a scratch of R * C floats allocated here, and dL_dfeatures[P,C] is appended to
+    // the tuple.
     // grad_out_depth (extension keyword): upstream gradient of the expected depth (depth_from_state), [1,H,W] or [H,W]; None launches no depth kernel,
-    // a tensor goes to tgs_backward_depth_opt (with grad_out_alpha or without) together with a scratch of R floats allocated here.
-    // grad_out_alpha (extension keyword): upstream gradient of the accumulated alpha (alpha_from_state), [1,H,W] or [H,W]; None takes today's call
-    // (tgs_backward_opt) unchanged, a tensor goes to tgs_backward_alpha_opt.
+    // a tensor travels with a scratch of R floats allocated here.
+    // grad_out_alpha (extension keyword): upstream gradient of the accumulated alpha (alpha_from_state), [1,H,W] or [H,W]; None: the colour's alone.
     // need_colors / need_cov3D = false (extension keywords; the reference's signature has neither): the caller will discard dL_dcolors / dL_dcov3D --
     // GaussianRasterizer's backward does when the forward was given shs / scales + rotations (__init__.py:137-152 hands them to inputs that are None) --
     // so they are neither allocated nor written (empty tensors come back); dL_dconic, an intermediate of the reference's two kernels, only on request.
@@ -191,37 +190,16 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
         int r;
         {
             py::gil_scoped_release nogil;
-            if (with_feat)
-                r = tgs_backward_features_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p,
-                                              tan_fovx, tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p,
-                                              with_alpha ? dA.p : nullptr, with_depth ? dD.p : nullptr, with_depth ? dz_scratch.data_ptr<float>() : nullptr,
-                                              C, feat.p, dF.p, feat_scratch.data_ptr<float>(), dL_dfeatures.data_ptr<float>(),
-                                              dL_dmeans2D.data_ptr<float>(), with_conic ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
-                                              want_col ? dL_dcolors.data_ptr<float>() : nullptr, dL_dmeans3D.data_ptr<float>(), want_cov ? dL_dcov3D.data_ptr<float>() : nullptr,
-                                              M ? dL_dsh.data_ptr<float>() : nullptr,
-                                              has_sr ? dL_dscales.data_ptr<float>() : nullptr, has_sr ? dL_drotations.data_ptr<float>() : nullptr, debug);
-            else if (with_depth)
-                r = tgs_backward_depth_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p,
-                                           tan_fovx, tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p,
-                                           with_alpha ? dA.p : nullptr, dD.p, dz_scratch.data_ptr<float>(),
-                                           dL_dmeans2D.data_ptr<float>(), with_conic ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
-                                           want_col ? dL_dcolors.data_ptr<float>() : nullptr, dL_dmeans3D.data_ptr<float>(), want_cov ? dL_dcov3D.data_ptr<float>() : nullptr,
-                                           M ? dL_dsh.data_ptr<float>() : nullptr,
-                                           has_sr ? dL_dscales.data_ptr<float>() : nullptr, has_sr ? dL_drotations.data_ptr<float>() : nullptr, debug);
-            else if (with_alpha)
-                r = tgs_backward_alpha_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p,
-                                           tan_fovx, tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p, dA.p,
-                                           dL_dmeans2D.data_ptr<float>(), with_conic ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
-                                           want_col ? dL_dcolors.data_ptr<float>() : nullptr, dL_dmeans3D.data_ptr<float>(), want_cov ? dL_dcov3D.data_ptr<float>() : nullptr,
-                                           M ? dL_dsh.data_ptr<float>() : nullptr,
-                                           has_sr ? dL_dscales.data_ptr<float>() : nullptr, has_sr ? dL_drotations.data_ptr<float>() : nullptr, debug);
-            else
-            r = tgs_backward_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p, tan_fovx,
-                                 tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p,
-                                 dL_dmeans2D.data_ptr<float>(), with_conic ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
-                                 want_col ? dL_dcolors.data_ptr<float>() : nullptr, dL_dmeans3D.data_ptr<float>(), want_cov ? dL_dcov3D.data_ptr<float>() : nullptr,
-                                 M ? dL_dsh.data_ptr<float>() : nullptr,
-                                 has_sr ? dL_dscales.data_ptr<float>() : nullptr, has_sr ? dL_drotations.data_ptr<float>() : nullptr, debug);
+            // one call whatever upstreams there are: NULL / 0 where one is absent, and without a feature gradient the library takes this for its
+            // depth call (tgs_backward_depth_opt, the name its errors then carry), without that for the alpha call's, without that for today's
+            r = tgs_backward_features_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p,
+                                          tan_fovx, tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p,
+                                          dA.p, dD.p, with_depth ? dz_scratch.data_ptr<float>() : nullptr,
+                                          C, feat.p, dF.p, with_feat ? feat_scratch.data_ptr<float>() : nullptr, with_feat ? dL_dfeatures.data_ptr<float>() : nullptr,
+                                          dL_dmeans2D.data_ptr<float>(), with_conic ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
+                                          want_col ? dL_dcolors.data_ptr<float>() : nullptr, dL_dmeans3D.data_ptr<float>(), want_cov ? dL_dcov3D.data_ptr<float>() : nullptr,
+                                          M ? dL_dsh.data_ptr<float>() : nullptr,
+                                          has_sr ? dL_dscales.data_ptr<float>() : nullptr, has_sr ? dL_drotations.data_ptr<float>() : nullptr, debug);
             // the median's share: a call of its own behind the main one, added into dL_dmeans3D (the depth's dz scratch is free again by then:
             // the same stream)
             if (r >= 0 && with_median && R > 0) {
@@ -232,14 +210,39 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
         }
         if (r < 0) raise_last(r);
     }
-    if (with_feat && with_conic) return py::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dconic, dL_dfeatures);
-    if (with_feat) return py::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dfeatures);
-    if (with_conic) return py::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dconic);
-    return py::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations);
+    py::list out;
+    for (const torch::Tensor& g : {dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations}) out.append(g);
+    if (with_conic) out.append(dL_dconic);
+    if (with_feat) out.append(dL_dfeatures);
+    return py::tuple(out);
 }
 
+// What depth_from_state, median_from_state and features_from_state share: the frame of a finished forward on `dev`, its sizes checked, the
+// device made current for the caller's lifetime of this object, and -- unless nothing was blended (P == 0 / R == 0: the caller returns its fill
+// and nothing is launched) -- the three state buffers checked against the sizes of such a frame.
+struct StateFrame {
+    c10::hip::HIPGuardMasqueradingAsCUDA guard;
+    torch::TensorOptions f32;
+    bool blended;
+    void* stream;
+    StateFrame(const char* fn, const c10::Device& dev, const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, int P, int H,
+               int W, int64_t R)
+        : guard(dev), f32(torch::TensorOptions().dtype(torch::kFloat32).device(dev)), blended(P != 0 && R != 0),
+          stream((void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream())
+    {
+        if (!blended) return;
+        size_t sizes[3];
+        tgs_state_sizes(P, W, H, 0, 0, R, sizes);
+        const auto bytes = [](const torch::Tensor& t) { return (size_t)t.numel() * t.element_size(); };
+        if (!geomBuffer.is_cuda() || !binningBuffer.is_cuda() || !imageBuffer.is_cuda() || bytes(geomBuffer) < sizes[TGS_BUF_GEOM] ||
+            bytes(binningBuffer) < sizes[TGS_BUF_BINNING] || bytes(imageBuffer) < sizes[TGS_BUF_IMAGE])
+            throw std::runtime_error(std::string(fn) + ": state buffers smaller than a frame of these sizes");
+    }
+};
+
 // The accumulated alpha of a finished forward (tgs_alpha): [1,H,W] = 1 - final_T.  The forward of an empty model (P == 0) carves no image
-// state -- its buffer is smaller than a frame's -- and has alpha 0 everywhere.
+// state -- its buffer is smaller than a frame's -- and has alpha 0 everywhere.  (Apart from StateFrame: it has the image buffer alone and
+// neither P nor R, and a buffer that is too small is its empty frame, not an error.)
 torch::Tensor alpha_from_state(const torch::Tensor& imageBuffer, int H, int W)
 {
     if (!imageBuffer.is_cuda()) throw std::runtime_error("alpha_from_state: imageBuffer must be the image state buffer of a forward, on a HIP device");
@@ -263,19 +266,10 @@ torch::Tensor depth_from_state(const torch::Tensor& geomBuffer, const torch::Ten
 {
     if (!imageBuffer.is_cuda()) throw std::runtime_error("depth_from_state: the state buffers must be those of a forward, on a HIP device");
     if (P < 0 || H <= 0 || W <= 0 || R < 0) throw std::runtime_error("depth_from_state: bad sizes");
-    const c10::Device dev = imageBuffer.device();
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
-    if (P == 0 || R == 0) return torch::zeros({1, H, W}, f32);
-    size_t sizes[3];
-    tgs_state_sizes(P, W, H, 0, 0, R, sizes);
-    const auto bytes = [](const torch::Tensor& t) { return (size_t)t.numel() * t.element_size(); };
-    if (!geomBuffer.is_cuda() || !binningBuffer.is_cuda() || bytes(geomBuffer) < sizes[TGS_BUF_GEOM] || bytes(binningBuffer) < sizes[TGS_BUF_BINNING] ||
-        bytes(imageBuffer) < sizes[TGS_BUF_IMAGE])
-        throw std::runtime_error("depth_from_state: state buffers smaller than a frame of these sizes");
-    torch::Tensor depth = torch::empty({1, H, W}, f32);
-    void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
-    const int r = tgs_depth(stream, P, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), depth.data_ptr<float>());
+    const StateFrame s("depth_from_state", imageBuffer.device(), geomBuffer, binningBuffer, imageBuffer, P, H, W, R);
+    if (!s.blended) return torch::zeros({1, H, W}, s.f32);
+    torch::Tensor depth = torch::empty({1, H, W}, s.f32);
+    const int r = tgs_depth(s.stream, P, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), depth.data_ptr<float>());
     if (r < 0) raise_last(r);
     return depth;
 }
@@ -287,20 +281,11 @@ py::tuple median_from_state(const torch::Tensor& geomBuffer, const torch::Tensor
 {
     if (!imageBuffer.is_cuda()) throw std::runtime_error("median_from_state: the state buffers must be those of a forward, on a HIP device");
     if (P < 0 || H <= 0 || W <= 0 || R < 0) throw std::runtime_error("median_from_state: bad sizes");
-    const c10::Device dev = imageBuffer.device();
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
-    const auto i32 = f32.dtype(torch::kInt32);
-    if (P == 0 || R == 0) return py::make_tuple(torch::zeros({1, H, W}, f32), torch::full({1, H, W}, -1, i32), torch::zeros({1, H, W}, i32));
-    size_t sizes[3];
-    tgs_state_sizes(P, W, H, 0, 0, R, sizes);
-    const auto bytes = [](const torch::Tensor& t) { return (size_t)t.numel() * t.element_size(); };
-    if (!geomBuffer.is_cuda() || !binningBuffer.is_cuda() || bytes(geomBuffer) < sizes[TGS_BUF_GEOM] || bytes(binningBuffer) < sizes[TGS_BUF_BINNING] ||
-        bytes(imageBuffer) < sizes[TGS_BUF_IMAGE])
-        throw std::runtime_error("median_from_state: state buffers smaller than a frame of these sizes");
-    torch::Tensor depth = torch::empty({1, H, W}, f32), index = torch::empty({1, H, W}, i32), pos = torch::empty({1, H, W}, i32);
-    void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
-    const int r = tgs_median(stream, P, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), depth.data_ptr<float>(), index.data_ptr<int>(),
+    const StateFrame s("median_from_state", imageBuffer.device(), geomBuffer, binningBuffer, imageBuffer, P, H, W, R);
+    const auto i32 = s.f32.dtype(torch::kInt32);
+    if (!s.blended) return py::make_tuple(torch::zeros({1, H, W}, s.f32), torch::full({1, H, W}, -1, i32), torch::zeros({1, H, W}, i32));
+    torch::Tensor depth = torch::empty({1, H, W}, s.f32), index = torch::empty({1, H, W}, i32), pos = torch::empty({1, H, W}, i32);
+    const int r = tgs_median(s.stream, P, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), depth.data_ptr<float>(), index.data_ptr<int>(),
                              pos.data_ptr<int>());
     if (r < 0) raise_last(r);
     return py::make_tuple(depth, index, pos);
@@ -317,19 +302,11 @@ torch::Tensor features_from_state(const torch::Tensor& geomBuffer, const torch::
     const int C = (int)features.size(1);
     if (C < 1 || C > TGS_FEATURE_MAX_CHANNELS) throw std::runtime_error("features_from_state: features must have 1 .. 16 channels");
     const c10::Device dev = features.device();
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
-    if (P == 0 || R == 0) return torch::zeros({C, H, W}, f32);
-    size_t sizes[3];
-    tgs_state_sizes(P, W, H, 0, 0, R, sizes);
-    const auto bytes = [](const torch::Tensor& t) { return (size_t)t.numel() * t.element_size(); };
-    if (!geomBuffer.is_cuda() || !binningBuffer.is_cuda() || !imageBuffer.is_cuda() || bytes(geomBuffer) < sizes[TGS_BUF_GEOM] ||
-        bytes(binningBuffer) < sizes[TGS_BUF_BINNING] || bytes(imageBuffer) < sizes[TGS_BUF_IMAGE])
-        throw std::runtime_error("features_from_state: state buffers smaller than a frame of these sizes");
+    const StateFrame s("features_from_state", dev, geomBuffer, binningBuffer, imageBuffer, P, H, W, R);
+    if (!s.blended) return torch::zeros({C, H, W}, s.f32);
     const Arg feat(features, dev, "features");
-    torch::Tensor out = torch::empty({C, H, W}, f32);
-    void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
-    const int r = tgs_features(stream, P, C, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), feat.p, out.data_ptr<float>());
+    torch::Tensor out = torch::empty({C, H, W}, s.f32);
+    const int r = tgs_features(s.stream, P, C, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), feat.p, out.data_ptr<float>());
     if (r < 0) raise_last(r);
     return out;
 }

@@ -305,8 +305,8 @@ def rasterize_gaussians_backward_accumulate(background, means3D, radii, colors, 
     """Multi-view extension (tgs_backward_accumulate): parameter gradients are ADDED into the fp32 tensors of ``into``
     (keys: means3D, opacities, and sh|colors_precomp, scales+rotations|cov3D_precomp; contiguous, on the device).
     Returns dL_dmeans2D[P,3], the only per-view gradient.  ``grad_out_alpha`` / ``grad_out_depth`` ([1,H,W]): upstream gradients of the
-    frame's accumulated alpha / expected depth as well (tgs_backward_depth_opt with accumulate = 1; the dz scratch of R floats is
-    allocated here); both None: today's call (tgs_backward_opt), bit for bit.  ``grad_out_features`` ([C,H,W]) with ``features`` ([P,C],
+    frame's accumulated alpha / expected depth as well (what tgs_backward_depth_opt with accumulate = 1 does; the dz scratch of R floats is
+    allocated here); both None: what tgs_backward_opt does, bit for bit.  ``grad_out_features`` ([C,H,W]) with ``features`` ([P,C],
     float32, 1 <= C <= 16): the upstream gradient of the frame's feature map as well (tgs_backward_features_opt with accumulate = 1; the
     scratch of R * C floats is allocated here); dL/d features is ADDED into ``into["features"]`` ([P,C]), which is required then.
     ``grad_out_median`` ([1,H,W]) with ``median_pos`` (the int32 map [1,H,W] of ``median_from_state`` for this frame): the upstream gradient
@@ -337,15 +337,12 @@ def rasterize_gaussians_backward_accumulate(background, means3D, radii, colors, 
 
         has_sh, has_sr = t["sh"] is not None, t["scales"] is not None
         opt = options(tile_bound=tile_bound, deterministic=deterministic, mid_bound=mid_bound)
-        extras = []
-        if grad_out_alpha is not None or grad_out_depth is not None:
-            for name, g in (("grad_out_alpha", grad_out_alpha), ("grad_out_depth", grad_out_depth)):
-                if g is not None and g.numel() != H * W:
-                    raise RuntimeError(f"{name} must have H*W elements ([1,H,W])")
-            dA, dD = _dev_f32(grad_out_alpha, dev, "grad_out_alpha"), _dev_f32(grad_out_depth, dev, "grad_out_depth")
-            dz = torch.empty((max(int(R), 1),), dtype=torch.float32, device=dev) if dD is not None else None
-            extras = [_p(dA), _p(dD), _p(dz)]
-        fn = _lib.tgs_backward_depth_opt if extras else _lib.tgs_backward_opt
+        for name, g in (("grad_out_alpha", grad_out_alpha), ("grad_out_depth", grad_out_depth)):
+            if g is not None and g.numel() != H * W:
+                raise RuntimeError(f"{name} must have H*W elements ([1,H,W])")
+        dA, dD = _dev_f32(grad_out_alpha, dev, "grad_out_alpha"), _dev_f32(grad_out_depth, dev, "grad_out_depth")
+        dz = torch.empty((max(int(R), 1),), dtype=torch.float32, device=dev) if dD is not None else None
+        Cf, F, dF, fscratch, dL_dfeatures = 0, None, None, None, None
         if grad_out_features is not None:
             F = _dev_f32(features, dev, "features")
             if F is None or F.dim() != 2 or int(F.size(0)) != P or not 1 <= int(F.size(1)) <= FEATURE_MAX_CHANNELS:
@@ -357,13 +354,14 @@ def rasterize_gaussians_backward_accumulate(background, means3D, radii, colors, 
                 raise RuntimeError("grad_out_features: into[\"features\"] ([P,C]) is required")
             dF = _dev_f32(grad_out_features, dev, "grad_out_features")
             fscratch = torch.empty((max(int(R), 1) * Cf,), dtype=torch.float32, device=dev)
-            extras = (extras or [None, None, None]) + [Cf, _p(F), _p(dF), _p(fscratch), dst("features", (P, Cf))]
-            fn = _lib.tgs_backward_features_opt
-        r = fn(
+            dL_dfeatures = dst("features", (P, Cf))
+        # one call whatever upstreams there are: None where one is absent (the library then launches what the call without it launches)
+        r = _lib.tgs_backward_features_opt(
             C.byref(opt), 1, torch.cuda.current_stream(dev).cuda_stream, P, int(degree), M, int(R), _p(t["bg"]), W, H, _p(t["means"]), _p(t["sh"]), _p(t["colors"]),
             _p(t["scales"]), float(scale_modifier), _p(t["rots"]), _p(t["cov"]), _p(t["view"]), _p(t["proj"]), _p(t["campos"]),
             float(tan_fovx), float(tan_fovy), radii.contiguous().data_ptr(), geomBuffer.data_ptr(), binningBuffer.data_ptr(),
-            imageBuffer.data_ptr(), _p(t["dL"]), *extras, dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dst("opacities", (P, 1)),
+            imageBuffer.data_ptr(), _p(t["dL"]), _p(dA), _p(dD), _p(dz), Cf, _p(F), _p(dF), _p(fscratch), dL_dfeatures,
+            dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dst("opacities", (P, 1)),
             None if has_sh else dst("colors_precomp", (P, 3)), dst("means3D", (P, 3)), None if has_sr else dst("cov3D_precomp", (P, 6)),
             dst("sh", (P, M, 3)) if has_sh else None, dst("scales", (P, 3)) if has_sr else None, dst("rotations", (P, 4)) if has_sr else None,
             int(bool(debug)))
@@ -447,14 +445,32 @@ def state_sizes(P: int, width: int, height: int, has_sh: bool, has_scale_rot: bo
     return int(out[0]), int(out[1]), int(out[2])
 
 
+_NO_OPTIONS = object()                  # (a *_views function of the library without an options parameter)
+
+
+def _ptr(a):
+    """a ctypes array (views, extras, feats) as the pointer the library takes; None and pointers stay"""
+    return a if a is None or isinstance(a, C.c_void_p) else C.cast(a, C.c_void_p)
+
+
+def _views_call(fn, opt, stream_handles, *args):
+    """One *_views call of the library: ``opt`` by reference (None: NULL; _NO_OPTIONS: ``fn`` takes none), the stream handles as an array and
+    their number, then ``args``; an error code raises.  (This sits in every step of the whole-batch path, several times: a few microseconds
+    of Python per call show in bench.py, so the arguments come converted and nothing here loops over them.)"""
+    arr = (C.c_void_p * len(stream_handles))(*stream_handles)
+    if opt is _NO_OPTIONS:
+        r = fn(arr, len(stream_handles), *args)
+    else:
+        r = fn(C.byref(opt) if opt is not None else None, arr, len(stream_handles), *args)
+    if r < 0:
+        raise _err(int(r))
+
+
 def forward_views(stream_handles, r_capacity, P, D, M, means3D, shs, opacities, scales, scale_modifier, rotations, views, n_views, prefiltered=False,
                   opt: Optional[_OptionsT] = None) -> None:
     """tgs_forward_views_opt on prepared device pointers (ints) and a filled ``ViewArray``; ``opt``: ``options(...)`` or None (defaults)."""
-    arr = (C.c_void_p * len(stream_handles))(*stream_handles)
-    r = _lib.tgs_forward_views_opt(C.byref(opt) if opt is not None else None, arr, len(stream_handles), int(r_capacity), int(P), int(D), int(M), means3D, shs, None,
-                                   opacities, scales, float(scale_modifier), rotations, None, int(bool(prefiltered)), int(n_views), C.cast(views, C.c_void_p))
-    if r < 0:
-        raise _err(int(r))
+    _views_call(_lib.tgs_forward_views_opt, opt, stream_handles, int(r_capacity), int(P), int(D), int(M), means3D, shs, None, opacities, scales, float(scale_modifier),
+                rotations, None, int(bool(prefiltered)), int(n_views), _ptr(views))
 
 
 def set_render_streams(stream_handles) -> None:
@@ -464,29 +480,18 @@ def set_render_streams(stream_handles) -> None:
 
 
 def backward_render_views(stream_handles, P, views, n_views, opt: Optional[_OptionsT] = None) -> None:
-    arr = (C.c_void_p * len(stream_handles))(*stream_handles)
-    r = _lib.tgs_backward_render_views_opt(C.byref(opt) if opt is not None else None, arr, len(stream_handles), int(P), int(n_views),
-                                           views if isinstance(views, C.c_void_p) else C.cast(views, C.c_void_p))
-    if r < 0:
-        raise _err(int(r))
+    _views_call(_lib.tgs_backward_render_views_opt, opt, stream_handles, int(P), int(n_views), _ptr(views))
 
 
 def outputs_views(stream_handles, P, views, extras, n_views) -> None:
     """tgs_outputs_views: alpha / depth of every view into extras[k].out_alpha / out_depth; ``stream_handles``: the streams the views'
     k_render_fwd ran on (forward_views' streams, or the render streams when set_render_streams was in force)."""
-    arr = (C.c_void_p * len(stream_handles))(*stream_handles)
-    r = _lib.tgs_outputs_views(arr, len(stream_handles), int(P), int(n_views), C.cast(views, C.c_void_p), C.cast(extras, C.c_void_p))
-    if r < 0:
-        raise _err(int(r))
+    _views_call(_lib.tgs_outputs_views, _NO_OPTIONS, stream_handles, int(P), int(n_views), _ptr(views), _ptr(extras))
 
 
 def backward_render_views_extras(stream_handles, P, views, extras, n_views, opt: Optional[_OptionsT] = None) -> None:
     """tgs_backward_render_views_extras_opt: backward_render_views with extras[k].dL_dalpha / dL_ddepth entering view k's per-pixel backward."""
-    arr = (C.c_void_p * len(stream_handles))(*stream_handles)
-    r = _lib.tgs_backward_render_views_extras_opt(C.byref(opt) if opt is not None else None, arr, len(stream_handles), int(P), int(n_views),
-                                                  C.cast(views, C.c_void_p), C.cast(extras, C.c_void_p) if extras is not None else None)
-    if r < 0:
-        raise _err(int(r))
+    _views_call(_lib.tgs_backward_render_views_extras_opt, opt, stream_handles, int(P), int(n_views), _ptr(views), _ptr(extras))
 
 
 def backward_batch_depth_raw(stream, P, views, extras, n_views, dL_dmean3D, first: int = 0, count: Optional[int] = None) -> None:
@@ -501,21 +506,13 @@ def backward_batch_depth_raw(stream, P, views, extras, n_views, dL_dmean3D, firs
 def features_views(stream_handles, P, views, feats, n_views) -> None:
     """tgs_features_views: the feature map of every view into feats[k].out_features; ``stream_handles``: as for ``outputs_views``, the streams
     the views' k_render_fwd ran on."""
-    arr = (C.c_void_p * len(stream_handles))(*stream_handles)
-    r = _lib.tgs_features_views(arr, len(stream_handles), int(P), int(n_views), C.cast(views, C.c_void_p), C.cast(feats, C.c_void_p))
-    if r < 0:
-        raise _err(int(r))
+    _views_call(_lib.tgs_features_views, _NO_OPTIONS, stream_handles, int(P), int(n_views), _ptr(views), _ptr(feats))
 
 
 def backward_render_views_features(stream_handles, P, views, extras, feats, n_views, opt: Optional[_OptionsT] = None) -> None:
     """tgs_backward_render_views_features_opt: backward_render_views_extras (``extras`` may be None) with feats[k].dL_dfeature_map entering
     view k's per-pixel backward behind the depth's share; the channel sums stay in feats[k].feature_scratch."""
-    arr = (C.c_void_p * len(stream_handles))(*stream_handles)
-    r = _lib.tgs_backward_render_views_features_opt(C.byref(opt) if opt is not None else None, arr, len(stream_handles), int(P), int(n_views),
-                                                    C.cast(views, C.c_void_p), C.cast(extras, C.c_void_p) if extras is not None else None,
-                                                    C.cast(feats, C.c_void_p) if feats is not None else None)
-    if r < 0:
-        raise _err(int(r))
+    _views_call(_lib.tgs_backward_render_views_features_opt, opt, stream_handles, int(P), int(n_views), _ptr(views), _ptr(extras), _ptr(feats))
 
 
 def backward_batch_features_raw(stream, P, views, feats, n_views, dL_dfeatures, accumulate, first: int = 0, count: Optional[int] = None) -> None:
