@@ -254,8 +254,8 @@ int tgs_backward_render_alpha_opt(const tgs_options_t* opt, void* stream, int P,
  *                     to dL_dopacity, dL_dconic, dL_dmean2D and on through the unchanged per-Gaussian pass;
  *   dL_dcolor / dL_dsh get nothing from it.
  * Part of the whole-batch path since tgs_view_extras_t (below, behind tgs_backward_batch_range_planes): alpha and depth of every view of a
- * batch and their gradients, beside the frozen tgs_view_t.  The median depth of one view is tgs_median below; the whole-batch path has no
- * median depth, and there is no mode depth anywhere; normals and feature channels are tgs_features below.
+ * batch and their gradients, beside the frozen tgs_view_t.  The median depth of one view is tgs_median below, that of a batch's views
+ * tgs_median_views (tgs_view_median_t); there is no mode depth anywhere; normals and feature channels are tgs_features below.
  *
  * tgs_depth: out_depth[H*W] of a finished forward (any of the forward entry points; P, width, height as given to it, R as it returned or was
  * given), enqueued on `stream`: a pass of its own over the frame's state, the render kernels are not involved.  P == 0 or R == 0: nothing
@@ -297,10 +297,10 @@ int tgs_backward_depth_opt(const tgs_options_t* opt, int accumulate, void* strea
  * Channels travel in groups of 8 per launch (C = 9 .. 16: two launches each way).  No float atomics: two runs give the same bits.
  * Part of the whole-batch path since tgs_view_features_t (below, behind tgs_backward_batch_depth_range): the feature map of every view of a
  * batch and its gradients, in a third array beside tgs_view_t and tgs_view_extras_t (the latter keeps its six fields: nothing is appended to
- * it).  What is still NOT part of the whole-batch path: median / mode depth, more than 16 channels, half-precision features, and
- * tgs_backward_batch without ranges (the features' per-Gaussian pass exists as tgs_backward_batch_features_range only; first = 0, count = P
- * is the whole model).
- * (The median depth of ONE view exists: tgs_median below.)
+ * it).  What is still NOT part of the whole-batch path: median / mode depth as an output of the step's own calls (the median has calls of
+ * its own behind them and a fourth array, tgs_view_median_t; a mode depth exists nowhere), more than 16 channels, half-precision features,
+ * and tgs_backward_batch without ranges (the features' per-Gaussian pass exists as tgs_backward_batch_features_range only; first = 0,
+ * count = P is the whole model).
  *
  * tgs_features: out[C*H*W] of a finished forward (P, width, height as given to it, R as it returned or was given), enqueued on `stream`: a
  * pass of its own over the frame's state, the render kernels are not involved.  P == 0 or R == 0: nothing was blended, nothing is launched
@@ -342,7 +342,8 @@ int tgs_backward_features_opt(const tgs_options_t* opt, int accumulate, void* st
  * g[H*W]: dL/dz_i = sum over the pixels p with m(p) = i of g(p), which reaches dL_dmean3D through the third row of the view transform
  * (m[2], m[6], m[10]) as the z-path of tgs_depth does.  Opacities, mean2D, scales, rotations, colours and SH get NOTHING from it: a loss on
  * the median depth moves positions; the expected depth is the one that moves opacities.  median_index is an integer output without a gradient.
- * One view only: the *_views entry points have no median.  No quantile other than one half.
+ * The views of a batch: tgs_median_views and its two backward calls, behind tgs_backward_batch_features_range.  No quantile other than
+ * one half.
  *
  * tgs_median: the three maps of a finished forward (any of the forward entry points; P, width, height as given to it, R as it returned or
  * was given), enqueued on `stream`: the maps are filled with 0 / -1 / 0, then one pass over the frame's state writes the pixels that have a
@@ -659,6 +660,50 @@ int tgs_backward_render_views_features_opt(const tgs_options_t* opt, void* const
  * tgs_backward_render_views_features_opt.  NULL dL_dfeatures with a view that has dL_dfeature_map is an error. */
 int tgs_backward_batch_features_range(void* stream, int P, int n_views, const tgs_view_t* views, const tgs_view_features_t* feats,
                                       float* dL_dfeatures, int accumulate, int first, int count);
+
+/* ---- median depth and surface index of a batch's views, and surface votes ----
+ * The median reads what the forward kernels left behind (the sorted keys, the instance records, n_contrib, the tile descriptors) and its
+ * gradient reaches positions alone and replays nothing, so both passes are independent of the step's own kernels: calls of their own,
+ * anywhere behind tgs_forward_views, with a FOURTH array beside the three above -- same length, same index, the struct_size rule of
+ * tgs_view_features_t.  The three outputs are all set or all NULL (NULL: the view takes no part).  med == NULL: no view takes part.
+ * Definitions: tgs_median above. */
+typedef struct {
+    uint32_t struct_size;            /* sizeof(tgs_view_median_t) of the caller's build: fields beyond it read as NULL */
+    float*   out_depth;              /* [H*W] or NULL */
+    int32_t* out_index;              /* [H*W] or NULL */
+    int32_t* out_pos;                /* [H*W] or NULL: the internal 1-based list position, kept for the backward */
+    const float* dL_dmedian_depth;   /* [H*W] or NULL */
+    float*   dz_scratch;             /* views[k].R floats of the caller's (contents on entry do not matter), required with dL_dmedian_depth */
+} tgs_view_median_t;                 /* 48 bytes */
+size_t tgs_sizeof_view_median(void);
+
+/* tgs_median into med[k].out_depth / out_index / out_pos for every view of a finished tgs_forward_views call that has the three pointers, from
+ * the view's state (views[k]: width, height, R, the three buffers).  View k is enqueued on streams[k % n_streams].  WHICH streams: the rule
+ * written above tgs_outputs_views (the pass reads n_contrib, which k_render_fwd writes) -- or any streams that are ordered behind the
+ * forward by other means, e.g. behind the whole step.  The backward of the step writes none of the arrays the pass reads: the maps are the
+ * same bits in front of it and behind it.  A frame the sync-free forward rejected, a frame without instances (R == 0) and an empty model
+ * (P == 0) give 0 / -1 / 0. */
+int tgs_median_views(void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_median_t* med);
+
+/* The per-pixel half of the median's gradient: per view with med[k].dL_dmedian_depth and R > 0, on streams[k % n_streams], dz_scratch is
+ * zero-filled and the upstream gradients of the pixels that share a median entry are summed into that instance's row (k_median_bwd; out_pos
+ * is the map tgs_median_views wrote for the same frame, required then).  No per-Gaussian pass runs: that is
+ * tgs_backward_batch_median_range.  Fixed order, no float atomics. */
+int tgs_backward_median_views(void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_median_t* med);
+
+/* tgs_backward_batch_depth_range reading the rows from med[k].dz_scratch: for Gaussians [first, first + count)
+ *     dL_dmean3D[p] += sum over the views k with dL_dmedian_depth and R > 0, ascending, of (sum of p's dz rows of view k) * (m_k[2], m_k[6], m_k[10]).
+ * It always adds: call it on one stream behind whatever stored or accumulated dL_dmean3D and behind the join of the streams of
+ * tgs_backward_median_views.  One launch per 8 such views; two runs give the same bits. */
+int tgs_backward_batch_median_range(void* stream, int P, int n_views, const tgs_view_t* views, const tgs_view_median_t* med, float* dL_dmean3D,
+                                    int first, int count);
+
+/* Surface votes over n pixels -- the median_index maps of any number of views, concatenated: seen[p] += the number of pixels with
+ * index == p, hits[p] += the number of those whose mask byte is not zero.  seen / hits: int32 [P], ADDED to (the caller zero-fills them:
+ * many cameras can be voted in chunks).  mask == NULL: hits is not touched and may be NULL; with a mask hits is required.  An index < 0
+ * (no surface) or >= P is skipped.  Integer counts: the result does not depend on the order, two runs give the same bits.  P == 0 or
+ * n == 0: nothing is launched.  Nothing is read back. */
+int tgs_surface_votes(void* stream, int P, int64_t n, const int32_t* index, const uint8_t* mask, int32_t* seen, int32_t* hits);
 
 /* ---- "next" row 2: the trainers' photometric loss ----
  * loss = (1 - dssim_factor) * l1_loss(img, gt) + dssim_factor * (1 - ssim(img, gt)), window 11, sigma 1.5, zero padding

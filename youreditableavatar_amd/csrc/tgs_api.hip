@@ -41,6 +41,7 @@ void launch_feat_bwd_gauss_views(hipStream_t, int first, int count, int C, const
 void launch_median_fwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t T, float* out_depth, int* out_index, int* out_pos);
 void launch_median_bwd(hipStream_t, const ImgState&, const BinState&, int W, int H, uint32_t gx, uint32_t T, size_t R, const int* median_pos, const float* dL_dmedian,
                        float* dz_rows);
+void launch_surface_votes(hipStream_t, int P, long long n, const int* index, const uint8_t* mask, int* seen, int* hits);
 }  // namespace tgs
 
 using namespace tgs;
@@ -618,11 +619,23 @@ static int read_feats(const tgs_view_features_t* base, int k, tgs_view_features_
     if (out.dL_dfeature_map && !out.feature_scratch) return fail(TGS_ERR_INVALID, "view %d: dL_dfeature_map without feature_scratch", k);
     return TGS_OK;
 }
+// an element's three maps come together or not at all; the gradient needs the position map the forward left and a scratch
+static int read_median(const tgs_view_median_t* base, int k, tgs_view_median_t& out)
+{
+    if (int r = read_element(base, k, out, "tgs_view_median_t", offsetof(tgs_view_median_t, out_depth) + sizeof(out.out_depth), "the first pointer field")) return r;
+    const int outs = (out.out_depth != nullptr) + (out.out_index != nullptr) + (out.out_pos != nullptr);
+    if (outs != 0 && outs != 3) return fail(TGS_ERR_INVALID, "view %d: out_depth, out_index and out_pos come together or not at all", k);
+    if (out.dL_dmedian_depth && !out.dz_scratch) return fail(TGS_ERR_INVALID, "view %d: dL_dmedian_depth without dz_scratch", k);
+    if (out.dL_dmedian_depth && !out.out_pos) return fail(TGS_ERR_INVALID, "view %d: dL_dmedian_depth without out_pos (the map tgs_median_views wrote)", k);
+    return TGS_OK;
+}
 
-// The arguments the entry points with a tgs_view_extras_t and / or a tgs_view_features_t array share, checked before anything is enqueued: the
-// sizes and the views, then every element of the extras, then every element of the feats (an array the call does not take: NULL).
+// The arguments the entry points with a tgs_view_extras_t, a tgs_view_features_t and / or a tgs_view_median_t array share, checked before
+// anything is enqueued: the sizes and the views, then every element of the extras, of the feats, of the med (an array the call does not
+// take: NULL).
 // -> C of the elements that take part (the features are the model's: C and the pointer are the same in all of them; 0: none takes part)
-static int check_views_call(int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras, const tgs_view_features_t* feats, int& C)
+static int check_views_call(int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras, const tgs_view_features_t* feats, int& C,
+                            const tgs_view_median_t* med = nullptr)
 {
     g_err[0] = 0;
     C = 0;
@@ -640,6 +653,9 @@ static int check_views_call(int P, int n_views, const tgs_view_t* views, const t
         else if (c.C != C || c.features != features)
             return fail(TGS_ERR_INVALID, "view %d: C=%d / features differ from an earlier view's (C=%d): the features are the model's, one tensor for all views", k, c.C, C);
     }
+    tgs_view_median_t m;
+    for (int k = 0; k < n_views && med; k++)
+        if (int r = read_median(med, k, m)) return r;
     return TGS_OK;
 }
 static int check_streams(void* const* streams, int n_streams, int n_views)
@@ -718,23 +734,25 @@ static int open_frame(Frame& f, const char* fn, int P, int width, int height, in
     return 1;
 }
 // The extra outputs of several views of a finished tgs_forward_views call, view k on streams[k % n_streams]: alpha and depth (tgs_outputs_views)
-// and the feature map (tgs_features_views), under their name `fn` -- either array may be NULL: no view has any.  A view in which nothing was
-// blended has its outputs zero-filled.
+// the feature map (tgs_features_views) and the median maps (tgs_median_views), under their name `fn` -- any array may be NULL: no view has
+// any.  A view in which nothing was blended has its outputs zero-filled (the median's index map: -1).
 static int outputs_views(const char* fn, void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras,
-                         const tgs_view_features_t* feats)
+                         const tgs_view_features_t* feats, const tgs_view_median_t* med = nullptr)
 {
     int C;
-    if (int r = check_views_call(P, n_views, views, extras, feats, C)) return named(fn, r);
+    if (int r = check_views_call(P, n_views, views, extras, feats, C, med)) return named(fn, r);
     if (int r = check_streams(streams, n_streams, n_views)) return named(fn, r);
     for (int k = 0; k < n_views; k++) {
         tgs_view_extras_t x;
         tgs_view_features_t c;
         if (int r = read_extras(extras, k, x)) return named(fn, r);
+        tgs_view_median_t m;
         if (int r = read_feats(feats, k, c)) return named(fn, r);
-        if (!x.out_alpha && !x.out_depth && !c.out_features) continue;
+        if (int r = read_median(med, k, m)) return named(fn, r);
+        if (!x.out_alpha && !x.out_depth && !c.out_features && !m.out_depth) continue;
         const tgs_view_t& w = views[k];
         hipStream_t st = (hipStream_t)streams[k % n_streams];
-        const Frame f = frame_facts(P, w.width, w.height, w.R, w.geom_buffer, w.binning_buffer, w.img_buffer, !x.out_depth && !c.out_features);
+        const Frame f = frame_facts(P, w.width, w.height, w.R, w.geom_buffer, w.binning_buffer, w.img_buffer, !x.out_depth && !c.out_features && !m.out_depth);
         if (!f.sizes_ok) return fail(TGS_ERR_INVALID, "%s: view %d: bad sizes", fn, k);
         if (!f.grid_ok) return fail(TGS_ERR_INVALID, "%s: view %d: image too large", fn, k);
         const size_t N = f.v.N();
@@ -742,16 +760,54 @@ static int outputs_views(const char* fn, void* const* streams, int n_streams, in
             if (x.out_alpha) HIP_TRY(hipMemsetAsync(x.out_alpha, 0, N * sizeof(float), st));
             if (x.out_depth) HIP_TRY(hipMemsetAsync(x.out_depth, 0, N * sizeof(float), st));
             if (c.out_features) HIP_TRY(hipMemsetAsync(c.out_features, 0, (size_t)c.C * N * sizeof(float), st));
+            if (m.out_depth) {
+                HIP_TRY(hipMemsetAsync(m.out_depth, 0, N * sizeof(float), st));
+                HIP_TRY(hipMemsetAsync(m.out_index, 0xff, N * sizeof(int32_t), st));
+                HIP_TRY(hipMemsetAsync(m.out_pos, 0, N * sizeof(int32_t), st));
+            }
             continue;
         }
         if (!f.buffers_ok) return fail(TGS_ERR_INVALID, "%s: view %d: NULL required pointer", fn, k);
         if (x.out_alpha) launch_alpha(st, f.fb.s, N, x.out_alpha);
         if (x.out_depth) launch_depth_fwd(st, f.fb.s, f.fb.b, w.width, w.height, f.v.gx(), (uint32_t)f.v.T(), x.out_depth);
         if (c.out_features) launch_feat_fwd(st, f.fb.s, f.fb.b, w.width, w.height, f.v.gx(), (uint32_t)f.v.T(), P, c.C, c.features, c.out_features);   // (zero-fills the map first)
+        if (m.out_depth) launch_median_fwd(st, f.fb.s, f.fb.b, w.width, w.height, f.v.gx(), (uint32_t)f.v.T(), m.out_depth, m.out_index, m.out_pos);   // (fills 0 / -1 / 0 first)
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(TGS_ERR_HIP, "%s: view %d: %s", fn, k, hipGetErrorString(e));
     }
     return TGS_OK;
+}
+
+// The z-path of a gradient on view-space depths for all views in one pass over Gaussians [first, first + count): the body of
+// tgs_backward_batch_depth_range and tgs_backward_batch_median_range, under their name `fn`.  rows_of(k, rows): the dz rows of view k (one float
+// per instance slot), NULL: the view takes no part.  The arrays were checked by the caller.  One launch per BATCH_VIEWS views that take part.
+template <class RowsOf>
+static int z_path_range(const char* fn, hipStream_t st, int P, int n_views, const tgs_view_t* views, float* dL_dmean3D, int first, int count, RowsOf&& rows_of)
+{
+    if (P == 0 || n_views == 0 || count == 0) return TGS_OK;
+    if (int r = check_gaussian_range(P, first, count)) return named(fn, r);
+    DepthViews dv;
+    memset(&dv, 0, sizeof(dv));
+    auto flush = [&]() -> int {
+        if (dv.n == 0) return TGS_OK;
+        const int r = stage(st, TGS_STAGE_PREPROCESS_BWD, "depth_bwd_gauss_views", 0, [&] { launch_depth_bwd_gauss_views(st, first, count, dv, dL_dmean3D); });
+        dv.n = 0;
+        return r;
+    };
+    for (int k = 0; k < n_views; k++) {
+        const float* rows = nullptr;
+        if (int r = rows_of(k, rows)) return named(fn, r);
+        const tgs_view_t& w = views[k];
+        if (!rows || w.R <= 0) continue;                    // (R == 0: the per-pixel backward launched nothing and the scratch was not filled)
+        if (!dL_dmean3D || !w.geom_buffer || !w.img_buffer || !w.radii || !w.viewmatrix || w.width <= 0 || w.height <= 0)
+            return fail(TGS_ERR_INVALID, "%s: view %d: bad sizes or NULL required pointer", fn, k);
+        const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, view_args(w), w.R, w.geom_buffer, nullptr, w.img_buffer);
+        DepthView& d = dv.v[dv.n++];
+        d.meta = fb.s.meta; d.radii = w.radii; d.tiles_touched = fb.g.tiles_touched; d.offsets = fb.g.offsets; d.dz_rows = rows; d.view = w.viewmatrix;
+        if (dv.n == BATCH_VIEWS)
+            if (int r = flush()) return named(fn, r);
+    }
+    return named(fn, flush());
 }
 
 // the shared per-Gaussian stage of a group of views of tgs_forward_views: one launch on the group's first stream
@@ -1092,33 +1148,15 @@ int tgs_backward_render_views_extras_opt(const tgs_options_t* o, void* const* st
 int tgs_backward_batch_depth_range(void* stream, int P, int n_views, const tgs_view_t* views, const tgs_view_extras_t* extras, float* dL_dmean3D, int first, int count)
 {
     static const char* fn = "tgs_backward_batch_depth_range";
-    hipStream_t st = (hipStream_t)stream;
     int C;
     if (int r = check_views_call(P, n_views, views, extras, nullptr, C)) return named(fn, r);
-    if (P == 0 || n_views == 0 || count == 0 || !extras) return TGS_OK;
-    if (int r = check_gaussian_range(P, first, count)) return named(fn, r);
-    DepthViews dv;
-    memset(&dv, 0, sizeof(dv));
-    auto flush = [&]() -> int {
-        if (dv.n == 0) return TGS_OK;
-        const int r = stage(st, TGS_STAGE_PREPROCESS_BWD, "depth_bwd_gauss_views", 0, [&] { launch_depth_bwd_gauss_views(st, first, count, dv, dL_dmean3D); });
-        dv.n = 0;
-        return r;
-    };
-    for (int k = 0; k < n_views; k++) {
+    if (!extras) return TGS_OK;
+    return z_path_range(fn, (hipStream_t)stream, P, n_views, views, dL_dmean3D, first, count, [&](int k, const float*& rows) -> int {
         tgs_view_extras_t x;
-        if (int r = read_extras(extras, k, x)) return named(fn, r);
-        const tgs_view_t& w = views[k];
-        if (!x.dL_ddepth || w.R <= 0) continue;             // (R == 0: the per-pixel backward launched nothing and dz_scratch was not filled)
-        if (!dL_dmean3D || !w.geom_buffer || !w.img_buffer || !w.radii || !w.viewmatrix || w.width <= 0 || w.height <= 0)
-            return fail(TGS_ERR_INVALID, "%s: view %d: bad sizes or NULL required pointer", fn, k);
-        const FrameBuffers fb = carve_frame(GeomShape{(size_t)P, false, false}, view_args(w), w.R, w.geom_buffer, nullptr, w.img_buffer);
-        DepthView& d = dv.v[dv.n++];
-        d.meta = fb.s.meta; d.radii = w.radii; d.tiles_touched = fb.g.tiles_touched; d.offsets = fb.g.offsets; d.dz_rows = x.dz_scratch; d.view = w.viewmatrix;
-        if (dv.n == BATCH_VIEWS)
-            if (int r = flush()) return named(fn, r);
-    }
-    return named(fn, flush());
+        if (int r = read_extras(extras, k, x)) return r;
+        rows = x.dL_ddepth ? x.dz_scratch : nullptr;
+        return TGS_OK;
+    });
 }
 
 size_t tgs_sizeof_view_features(void) { return sizeof(tgs_view_features_t); }
@@ -1184,6 +1222,64 @@ int tgs_backward_batch_features_range(void* stream, int P, int n_views, const tg
             if (int r = flush()) return named(fn, r);
     }
     return named(fn, flush());
+}
+
+size_t tgs_sizeof_view_median(void) { return sizeof(tgs_view_median_t); }
+
+int tgs_median_views(void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_median_t* med)
+{
+    return outputs_views("tgs_median_views", streams, n_streams, P, n_views, views, nullptr, nullptr, med);
+}
+
+int tgs_backward_median_views(void* const* streams, int n_streams, int P, int n_views, const tgs_view_t* views, const tgs_view_median_t* med)
+{
+    static const char* fn = "tgs_backward_median_views";
+    int C;
+    if (int r = check_views_call(P, n_views, views, nullptr, nullptr, C, med)) return named(fn, r);
+    if (int r = check_streams(streams, n_streams, n_views)) return named(fn, r);
+    if (P == 0 || !med) return TGS_OK;
+    for (int k = 0; k < n_views; k++) {
+        tgs_view_median_t m;
+        if (int r = read_median(med, k, m)) return named(fn, r);
+        const tgs_view_t& w = views[k];
+        if (!m.dL_dmedian_depth || w.R == 0) continue;      // (R == 0: no pixel has a median entry; the range pass skips the view as well)
+        hipStream_t st = (hipStream_t)streams[k % n_streams];
+        const Frame f = frame_facts(P, w.width, w.height, w.R, w.geom_buffer, w.binning_buffer, w.img_buffer);
+        if (!f.sizes_ok) return fail(TGS_ERR_INVALID, "%s: view %d: bad sizes", fn, k);
+        if (!f.grid_ok) return fail(TGS_ERR_INVALID, "%s: view %d: image too large", fn, k);
+        if (!f.buffers_ok) return fail(TGS_ERR_INVALID, "%s: view %d: NULL required pointer", fn, k);
+        if (int r = stage(st, TGS_STAGE_RENDER_BWD, "median_bwd", 0, [&] {
+                launch_median_bwd(st, f.fb.s, f.fb.b, w.width, w.height, f.v.gx(), (uint32_t)f.v.T(), (size_t)w.R, m.out_pos, m.dL_dmedian_depth, m.dz_scratch); }))
+            return named(fn, r);
+    }
+    return TGS_OK;
+}
+
+int tgs_backward_batch_median_range(void* stream, int P, int n_views, const tgs_view_t* views, const tgs_view_median_t* med, float* dL_dmean3D, int first, int count)
+{
+    static const char* fn = "tgs_backward_batch_median_range";
+    int C;
+    if (int r = check_views_call(P, n_views, views, nullptr, nullptr, C, med)) return named(fn, r);
+    if (!med) return TGS_OK;
+    return z_path_range(fn, (hipStream_t)stream, P, n_views, views, dL_dmean3D, first, count, [&](int k, const float*& rows) -> int {
+        tgs_view_median_t m;
+        if (int r = read_median(med, k, m)) return r;
+        rows = m.dL_dmedian_depth ? m.dz_scratch : nullptr;
+        return TGS_OK;
+    });
+}
+
+int tgs_surface_votes(void* stream, int P, int64_t n, const int32_t* index, const uint8_t* mask, int32_t* seen, int32_t* hits)
+{
+    static const char* fn = "tgs_surface_votes";
+    g_err[0] = 0;
+    if (P < 0 || n < 0) return fail(TGS_ERR_INVALID, "%s: bad sizes P=%d n=%lld", fn, P, (long long)n);
+    if (P == 0 || n == 0) return TGS_OK;
+    if (!index || !seen) return fail(TGS_ERR_INVALID, "%s: NULL required pointer (index, seen)", fn);
+    if (mask && !hits) return fail(TGS_ERR_INVALID, "%s: a mask without hits", fn);
+    if ((n + 255) / 256 > 0x7fffffffll) return fail(TGS_ERR_INVALID, "%s: n=%lld is too large for one call", fn, (long long)n);
+    launch_surface_votes((hipStream_t)stream, P, (long long)n, index, mask, seen, hits);
+    return hip_status(fn);
 }
 
 int tgs_backward_render(void* stream, int P, int64_t R, const float* background, int width, int height, const void* binning_buffer,

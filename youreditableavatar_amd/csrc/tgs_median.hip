@@ -5,7 +5,9 @@
 //   k_median_bwd   dL/dz of the median entries: the upstream gradients of a tile's pixels that share a median entry, summed in a fixed order
 //                  into that instance's row of a per-instance scratch.  No pair is replayed: median_pos names the row.
 //   (the per-Gaussian half is k_depth_bwd_gauss of tgs_depth.hip, unchanged: the sum of a Gaussian's rows times the third row of the view
-//   transform, added to dL_dmeans3D)
+//   transform, added to dL_dmeans3D; for the views of a batch k_depth_bwd_gauss_views)
+//   k_surface_votes  over the median_index maps of any number of views: per Gaussian the pixels whose surface it is, and those of them
+//                  inside a mask -- integer counts, one atomic per run of equal indices in a wave
 //
 // The forward is k_depth_fwd's walk (tgs_depth.hip) with less to do per pair: the same geometry (256 threads per tile, one lane per pixel,
 // wave w owns the 8x8-pixel quadrant w), the same staging rounds, the same replay of which pairs were blended (replay_pair_alpha, positions
@@ -135,6 +137,41 @@ __global__ __launch_bounds__(256) void k_median_bwd(const ImgState s, const BinS
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_surface_votes: which Gaussians are the visible surface, counted over n pixels (the median_index maps of any number of views, one behind
+// the other): seen[p] += pixels with index p, hits[p] += those of them whose mask byte is not zero (mask == NULL: hits is not touched).
+// One lane per pixel in row-major order.  Neighbouring pixels mostly share their surface splat, so a wave issues ONE atomic per run of
+// equal indices, not one per pixel: a lane whose left neighbour holds another index is the head of a run (lane 0 always is: runs end at
+// the wave), the run's length is the distance to the next head in the ballot of the heads, its masked pixels are the mask ballot's bits
+// within the run.  An index outside 0 .. P-1 (-1: no surface) counts for nobody.  Integer adds, their results unused: the counts do not
+// depend on the order, two runs give the same bits.  Every lane of a workgroup reaches the shuffle and the ballots: no early return.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_surface_votes(int P, long long n, const int* __restrict__ index, const uint8_t* __restrict__ mask,
+                                                       int* __restrict__ seen, int* __restrict__ hits)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int idx = -1;
+    bool masked = false;
+    if (i < n) {
+        const int v = index[i];
+        if (v >= 0 && v < P) { idx = v; masked = mask != nullptr && mask[i] != 0; }
+    }
+    const int left = __shfl_up(idx, 1);
+    const bool head = lane == 0 || left != idx;
+    const unsigned long long heads = __builtin_amdgcn_ballot_w64(head);
+    const unsigned long long mbits = __builtin_amdgcn_ballot_w64(masked);
+    if (!head || idx < 0) return;
+    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);      // the heads to the right of this one
+    const int len = above ? __ffsll(above) : 64 - lane;                            // 1 .. 64
+    const unsigned long long run = (len == 64 ? ~0ull : (1ull << len) - 1ull) << lane;
+    atomicAdd(&seen[idx], len);
+    if (mask != nullptr) {
+        const int c = __popcll(mbits & run);
+        if (c) atomicAdd(&hits[idx], c);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
 // out_depth[N] <- 0, out_index[N] <- -1, out_pos[N] <- 0, then the tiles with instances (at most T workgroups have work)
@@ -152,6 +189,11 @@ void launch_median_bwd(hipStream_t st, const ImgState& s, const BinState& b, int
 {
     (void)hipMemsetAsync(dz_rows, 0, R * sizeof(float), st);
     if (T > 0) hipLaunchKernelGGL(k_median_bwd, dim3(T), dim3(256), 0, st, s, b, W, H, gx, (unsigned long long)R, median_pos, dL_dmedian, dz_rows);
+}
+// seen / hits are added to: the caller zero-fills them.  n > 0, and (n + 255) / 256 fits a grid (the caller checks)
+void launch_surface_votes(hipStream_t st, int P, long long n, const int* index, const uint8_t* mask, int* seen, int* hits)
+{
+    hipLaunchKernelGGL(k_surface_votes, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, P, n, index, mask, seen, hits);
 }
 
 }  // namespace tgs

@@ -95,6 +95,20 @@ def _load() -> C.CDLL:
     lib.tgs_median.argtypes = [vp, it, it, it, C.c_int64, vp, vp, vp, vp, vp, vp]
     lib.tgs_backward_median.restype = it
     lib.tgs_backward_median.argtypes = [vp, it, it, it, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    # the median of a batch's views (tgs_view_median_t) and the surface votes over their index maps
+    try:                                                     # (additive: an older A/B build of the same ABI version, TGS_LIBRARY, lacks them -- calling one raises)
+        lib.tgs_sizeof_view_median.restype = C.c_size_t
+        lib.tgs_median_views.restype = it
+        lib.tgs_median_views.argtypes = [vp, it, it, it, vp, vp]
+        lib.tgs_backward_median_views.restype = it
+        lib.tgs_backward_median_views.argtypes = [vp, it, it, it, vp, vp]
+        lib.tgs_backward_batch_median_range.restype = it
+        lib.tgs_backward_batch_median_range.argtypes = [vp, it, it, vp, vp, vp, it, it]
+        lib.tgs_surface_votes.restype = it
+        lib.tgs_surface_votes.argtypes = [vp, it, C.c_int64, vp, vp, vp, vp]
+    except AttributeError:
+        if "TGS_LIBRARY" not in os.environ:
+            raise
     lib.tgs_state_field.restype = C.c_int64
     lib.tgs_state_field.argtypes = [vp, C.c_char_p, it, it, it, C.c_int64, it, it, vp, vp, vp, vp, C.c_size_t]
     lib.tgs_set_sort_lds_cap.restype = it
@@ -438,6 +452,25 @@ def ViewFeaturesArray(n: int):
     return arr
 
 
+class _ViewMedianT(C.Structure):
+    """tgs_view_median_t (include/tgs_raster.h): the median maps and the median depth's gradient of one view, the fourth per-view array"""
+    _fields_ = [("struct_size", C.c_uint32), ("out_depth", C.c_void_p), ("out_index", C.c_void_p), ("out_pos", C.c_void_p),
+                ("dL_dmedian_depth", C.c_void_p), ("dz_scratch", C.c_void_p)]
+
+
+if hasattr(_lib, "tgs_sizeof_view_median") and _lib.tgs_sizeof_view_median() != C.sizeof(_ViewMedianT):
+    raise ImportError(f"tgs_view_median_t: the library says {_lib.tgs_sizeof_view_median()} bytes, this binding declares {C.sizeof(_ViewMedianT)} "
+                      "-- a stale library or binding")
+
+
+def ViewMedianArray(n: int):
+    """n zeroed tgs_view_median_t with struct_size set (every pointer NULL: nothing asked of any view)"""
+    arr = (_ViewMedianT * n)()
+    for x in arr:
+        x.struct_size = C.sizeof(_ViewMedianT)
+    return arr
+
+
 def state_sizes(P: int, width: int, height: int, has_sh: bool, has_scale_rot: bool, r_capacity: int) -> Tuple[int, int, int]:
     """tgs_state_sizes -> bytes of the (geometry, binning, image) state buffers of one view."""
     out = (C.c_size_t * 3)()
@@ -522,6 +555,69 @@ def backward_batch_features_raw(stream, P, views, feats, n_views, dL_dfeatures, 
                                                1 if accumulate else 0, int(first), int(P - first if count is None else count))
     if r < 0:
         raise _err(int(r))
+
+
+def median_views(stream_handles, P, views, med, n_views) -> None:
+    """tgs_median_views: median depth, surface index and list position of every view whose med[k] has the three output pointers, from the
+    frames of a finished forward_views call; view k on stream_handles[k mod n] -- streams ordered behind the views' k_render_fwd."""
+    _views_call(_lib.tgs_median_views, _NO_OPTIONS, stream_handles, int(P), int(n_views), _ptr(views), _ptr(med))
+
+
+def backward_median_views(stream_handles, P, views, med, n_views) -> None:
+    """tgs_backward_median_views: per view with med[k].dL_dmedian_depth, the upstream gradients of the pixels that share a median entry summed
+    into med[k].dz_scratch (out_pos: the map median_views wrote for the same frames).  The per-Gaussian half is backward_batch_median_raw."""
+    _views_call(_lib.tgs_backward_median_views, _NO_OPTIONS, stream_handles, int(P), int(n_views), _ptr(views), _ptr(med))
+
+
+def backward_batch_median_raw(stream, P, views, med, n_views, dL_dmean3D, first: int = 0, count: Optional[int] = None) -> None:
+    """tgs_backward_batch_median_range: the median depth's gradient of all views, ADDED to dL_dmean3D (a device pointer) for Gaussians
+    [first, first + count) -- on one stream, behind backward_median_views on every lane and behind whatever wrote dL_dmean3D."""
+    r = _lib.tgs_backward_batch_median_range(stream, int(P), int(n_views), C.cast(views, C.c_void_p), C.cast(med, C.c_void_p), dL_dmean3D,
+                                             int(first), int(P - first if count is None else count))
+    if r < 0:
+        raise _err(int(r))
+
+
+def backward_median_raw(stream, P, W, H, R, geom, binning, img, viewmatrix, radii, median_pos, dL_dmedian_depth, dz_scratch, dL_dmean3D) -> None:
+    """tgs_backward_median on device pointers: one view's median gradient ADDED to dL_dmean3D, on ``stream``."""
+    r = _lib.tgs_backward_median(stream, int(P), int(W), int(H), int(R), geom, binning, img, viewmatrix, radii, median_pos, dL_dmedian_depth, dz_scratch, dL_dmean3D)
+    if r < 0:
+        raise _err(int(r))
+
+
+def surface_votes(index: torch.Tensor, P: int, mask: Optional[torch.Tensor] = None, out=None):
+    """tgs_surface_votes over the pixels of ``index`` (int32, any shape, contiguous, on a HIP device): -> (seen[P], hits[P] or None), int32:
+    seen[p] += pixels whose index is p, hits[p] += those of them whose ``mask`` (uint8 or bool, as many elements as ``index``) is not zero.
+    ``out=(seen, hits)``: int32 [P] tensors that are ADDED to (hits may be None without a mask); otherwise new zeroed ones.  On the current
+    stream; nothing is read back."""
+    if not (torch.is_tensor(index) and index.is_cuda and index.dtype == torch.int32 and index.is_contiguous()):
+        raise RuntimeError("surface_votes: index must be a contiguous int32 tensor on a HIP device")
+    dev, P = index.device, int(P)
+    if P < 0:
+        raise RuntimeError("surface_votes: P must not be negative")
+    if mask is not None:
+        if not (torch.is_tensor(mask) and mask.device == dev and mask.dtype in (torch.uint8, torch.bool) and mask.is_contiguous() and
+                mask.numel() == index.numel()):
+            raise RuntimeError("surface_votes: mask must be a contiguous uint8 or bool tensor on the device of index, with as many elements")
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)                    # (a bool is one byte, 0 or 1: the same storage)
+    with torch.cuda.device(dev):
+        if out is None:
+            seen = torch.zeros(P, dtype=torch.int32, device=dev)
+            hits = torch.zeros(P, dtype=torch.int32, device=dev) if mask is not None else None
+        else:
+            seen, hits = out
+            for name, t in (("seen", seen), ("hits", hits)):
+                if t is None and (name == "hits" and mask is None):
+                    continue
+                if not (torch.is_tensor(t) and t.device == dev and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (P,)):
+                    raise RuntimeError(f"surface_votes: out {name} must be a contiguous int32 tensor [P] on the device of index")
+            if mask is None:
+                hits = None
+        r = _lib.tgs_surface_votes(torch.cuda.current_stream(dev).cuda_stream, P, int(index.numel()), index.data_ptr(), _p(mask), seen.data_ptr(), _p(hits))
+    if r < 0:
+        raise _err(int(r))
+    return seen, hits
 
 
 def backward_batch_raw(stream, P, D, M, views, n_views, means3D, shs, scales, scale_modifier, rotations, dL_dopacity, dL_dmean3D, dL_dsh, dL_dscale,

@@ -515,6 +515,45 @@ def _upstream_extras_checked(ret, c, names: Sequence[str], per_view: bool, requi
     return dL, out
 
 
+def _median_upstreams_checked(dL, c, require_gpu: bool = True) -> list:
+    """The argument of ``SyncFreeBatch.backward_median_views`` -> per view its upstream gradient [1,H,W] (contiguous) or None.  ``dL``: a
+    float32 GPU tensor [V,1,H,W], or [1,H,W] for all views, or a sequence of V entries, each [1,H,W] or None (that view takes no part).
+    ``c`` needs H, W and V only; ``require_gpu=False`` checks everything but the device (host tests)."""
+    one = (1, c.H, c.W)
+
+    def ok(g, shapes):
+        return torch.is_tensor(g) and g.dtype == torch.float32 and (g.is_cuda or not require_gpu) and tuple(g.shape) in shapes
+
+    if torch.is_tensor(dL):
+        if not ok(dL, [one, (c.V,) + one]):
+            raise RuntimeError(f"backward_median_views: dL must be a float32 GPU tensor {[c.V] + list(one)} or {list(one)}, or a sequence of {c.V} such maps or None")
+        dL = dL.contiguous()
+        return [_of_view(dL, v) for v in range(c.V)]
+    if not isinstance(dL, (tuple, list)) or len(dL) != c.V:
+        raise RuntimeError(f"backward_median_views: dL must be a float32 GPU tensor {[c.V] + list(one)} or {list(one)}, or a sequence of {c.V} such maps or None")
+    for v, g in enumerate(dL):
+        if g is not None and not ok(g, [one]):
+            raise RuntimeError(f"backward_median_views: dL[{v}] must be None or a float32 GPU tensor {list(one)}")
+    return [None if g is None else g.contiguous() for g in dL]
+
+
+def surface_votes(median_index: torch.Tensor, P: int, masks: Optional[torch.Tensor] = None, out=None):
+    """Which Gaussians are the visible surface, over all views and without a read-back: ``median_index`` is the int32 map [V,1,H,W] (or
+    [1,H,W]) of ``SyncFreeBatch.median_views`` / ``rasterize_gaussians(return_median=True)`` for a model of ``P`` Gaussians ->
+    ``(seen, hits)``, int32 [P]: seen[p] = the number of pixels, over all views, whose surface is Gaussian p; hits[p] = the number of
+    those that lie inside ``masks`` (``torch.bool`` or ``uint8``, the shape of ``median_index``; non-zero: inside) -- None without masks.
+    Pixels without a surface (-1) vote for nobody.  ``out=(seen, hits)``: int32 [P] tensors the counts are ADDED to (hits: None without
+    masks), so many cameras can be voted chunk by chunk; otherwise new zeroed tensors.  One kernel on the current stream (k_surface_votes:
+    one integer atomic per run of equal indices in a wave); the counts do not depend on the order, two runs give the same bits.
+    ``hits / seen`` above a threshold lifts 2-D edit masks to Gaussians."""
+    if not (torch.is_tensor(median_index) and median_index.dtype == torch.int32 and median_index.dim() in (3, 4) and int(median_index.shape[-3]) == 1):
+        raise RuntimeError("surface_votes: median_index must be an int32 tensor [V,1,H,W] or [1,H,W]")
+    if masks is not None and not (torch.is_tensor(masks) and masks.dtype in (torch.bool, torch.uint8) and masks.shape == median_index.shape and
+                                  masks.device == median_index.device):
+        raise RuntimeError("surface_votes: masks must be a torch.bool or uint8 tensor of the shape and on the device of median_index")
+    return _C.surface_votes(median_index.contiguous(), P, None if masks is None else masks.contiguous(), out)
+
+
 def _of_view(dL: torch.Tensor, v: int) -> torch.Tensor:
     """View v's part of an upstream gradient ([3,H,W] / [1,H,W] / [C,H,W]: the same for every view; None stays None)."""
     return dL if (dL is None or dL.dim() == 3) else dL[v]
@@ -557,6 +596,8 @@ class SyncFreeBatch:
         self._pool = None
         self.viewspace_grads: Optional[torch.Tensor] = None
         self.color_grads: Optional[torch.Tensor] = None      # run_views with colors_precomp: dL/d colours per view [V,P,3]
+        self._last: Optional[dict] = None       # the last run_views call, for median_views / backward_median_views (references, no buffers)
+        self._mpool: Optional[dict] = None      # the median maps [V,1,H,W] of median_views (allocated with its first call)
 
     def tile_capacity(self) -> int:
         """bound on the tiles with instances handed to the sync-free forward (0: none yet); a frame with more is rejected and rendered again"""
@@ -637,9 +678,11 @@ class SyncFreeBatch:
         instances are 512 MB.  ``features=None`` (the default) is the step of before: the same calls, buffers and return value.
 
         ``run`` / ``rasterize_accumulate`` / ``DeferredBackward`` carry none of these outputs (alpha, depth, feature channels); per-view
-        features [V,P,C], more than 16 channels and half precision are not part of this path either."""
+        features [V,P,C], more than 16 channels and half precision are not part of this path either.  The median depth and the surface index
+        of the views are no argument of this call: ``median_views()`` and ``backward_median_views(dL)`` behind it."""
         xnames = [n for n, on in (("alpha", return_alpha), ("depth", return_depth)) if on]      # the maps of tgs_view_extras_t
         c = _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_batch, upstream_view, colors_precomp, grad_chunks)
+        self._last = None                                   # (and with it the synchronous frames median_views kept)
         Cf = _check_features(features, c) if features is not None else 0
         names = xnames + (["features"] if Cf else [])      # every extra map, in the order of the return value and of the callables' tuples
         F = features.detach() if Cf else None
@@ -675,6 +718,7 @@ class SyncFreeBatch:
             self._learn(max(s[0] for s in states))
             for first, count in (c.ranges if on_chunk is not None else []):
                 on_chunk(first, count)
+            self._last = dict(c=c, pool=None, sync=list(range(V)), chunked=on_chunk is not None)
             return (images, *maps) if names else images
 
         pool = self._pooled(c, cap, names, Cf)
@@ -801,7 +845,105 @@ class SyncFreeBatch:
             for first, count in c.ranges:     # the same calls in the same order as on a rank that had nothing to render again (collectives must pair up)
                 on_chunk(first, count)
         self._learn(seen, [max(counts) for counts in zip(*(tiles for _R, _rejected, tiles in rows))])
+        self._last = dict(c=c, pool=pool, cap=cap, sync=redo, chunked=on_chunk is not None)
         return (images, *maps) if names else images
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # The median of the batch's views: calls of their own behind run_views.  The forward reads what the step's forward kernels left in the
+    # pooled frames (the step's backward writes none of it), the gradient reaches positions alone and replays nothing.
+    # ------------------------------------------------------------------------------------------------------------------
+    def median_views(self):
+        """``(median_depth[V,1,H,W] float32, median_index[V,1,H,W] int32)`` of the views of the LAST ``run_views`` call on this object, from
+        the frames that call left in the pool -- the outputs of ``rasterize_gaussians(return_median=True)`` for every view, bit for bit: the
+        view-space z and the Gaussian index of the first blended splat behind which the transmittance is below one half; 0 / -1 where no
+        surface exists.  Views of pooled buffers the next call reuses.  View k runs on lane k mod ``streams``, forked from and joined to the
+        current stream; no host synchronisation.  RuntimeError before any ``run_views`` call.  The maps describe the parameters ``run_views``
+        rendered: if they changed in between (an optimizer step), the results are undefined.
+
+        Frames the pool does not hold -- every view of a synchronous batch (the first one: no bound yet) and views that were rendered again
+        after a rejection -- are rendered once more by the synchronous forward from the inputs of the last call (kept by reference), and
+        their states are kept until the next ``run_views``.  The first call allocates the three maps (12 bytes per pixel and view)."""
+        last = self._last
+        if last is None:
+            raise RuntimeError("median_views: no finished run_views call on this object (call run_views first)")
+        c, pool, sync = last["c"], last["pool"], last["sync"]
+        V, P, H, W = c.V, c.P, c.H, c.W
+        dev = c.params["means3D"].device
+        key = (V, H, W, dev)
+        if self._mpool is None or self._mpool["key"] != key:
+            z = lambda dt: torch.empty((V, 1, H, W), dtype=dt, device=dev)
+            self._mpool = dict(key=key, depth=z(torch.float32), index=z(torch.int32), pos=z(torch.int32), marr=_C.ViewMedianArray(V))
+        mp = self._mpool
+        for v in range(V):
+            m, own = mp["marr"][v], v not in sync
+            m.out_depth = mp["depth"][v].data_ptr() if own else None
+            m.out_index = mp["index"][v].data_ptr() if own else None
+            m.out_pos = mp["pos"][v].data_ptr() if own else None
+            m.dL_dmedian_depth = m.dz_scratch = None
+        with torch.cuda.device(dev):
+            if pool is not None and len(sync) < V:
+                lanes = _lanes(torch.cuda.current_stream(dev), min(self.streams, V))
+                _fork(lanes)
+                _C.median_views([st.cuda_stream for st in lanes], P, pool["arr"], mp["marr"], V)
+                _join(lanes)
+            states = last.setdefault("states", {})
+            for v in sync:
+                if v not in states:
+                    states[v] = self._render_view(c, v)
+                R, _color, _radii, geom, binning, img = states[v][:6]
+                for name, t in zip(("depth", "index", "pos"), _C.median_from_state(geom, binning, img, P, H, W, int(R))):
+                    mp[name][v].copy_(t)
+        last["median"] = True
+        return mp["depth"], mp["index"]
+
+    def backward_median_views(self, dL) -> None:
+        """Adds the gradient of the median depths of all views into ``means3D.grad``, behind whatever ``run_views`` stored or accumulated
+        there (the median depth moves positions alone: d median_depth / d z of the median splat = 1, through the third row of each view's
+        transform; nothing reaches opacities, scales, rotations or colours).  ``dL``: dL/d median_depth, a float32 GPU tensor [V,1,H,W], or
+        [1,H,W] for all views, or a sequence of V entries, each [1,H,W] or None -- that view takes no part and no kernel runs for it;
+        anything else raises RuntimeError.  Call it after ``median_views()`` of the same step.  Per view the per-pixel half runs on the
+        lanes, then ONE pass over the Gaussians per range of the call (``grad_chunks``) on the current stream; views ``median_views`` had to
+        render synchronously go through the one-view call.  The first call grows the pool by a float scratch [V, capacity].
+
+        RuntimeError if the last ``run_views`` had ``on_chunk``: the gradients of its ranges were handed out as final (their all-reduce may
+        be in flight) and must not be added to."""
+        last = self._last
+        if last is None or not last.get("median"):
+            raise RuntimeError("backward_median_views: call median_views() after run_views first (its position maps are what this pass reads)")
+        if last["chunked"]:
+            raise RuntimeError("backward_median_views: the last run_views call had on_chunk -- its ranges were handed out as final")
+        c, pool, sync, mp = last["c"], last["pool"], last["sync"], self._mpool
+        gs = _median_upstreams_checked(dL, c)
+        V, P, H, W = c.V, c.P, c.H, c.W
+        means3D = c.params["means3D"]
+        dev = means3D.device
+        last["keep"] = gs                                   # (alive until the next batch)
+        with torch.cuda.device(dev):
+            main = torch.cuda.current_stream(dev)
+            own = [v for v in range(V) if v not in sync and gs[v] is not None]
+            if own:
+                if "mdz" not in pool:
+                    pool["mdz"] = torch.empty((V, last["cap"]), dtype=torch.float32, device=dev)      # one float per instance slot and view
+                for v in range(V):
+                    m = mp["marr"][v]
+                    m.dL_dmedian_depth = gs[v].data_ptr() if v in own else None
+                    m.dz_scratch = pool["mdz"][v].data_ptr() if v in own else None
+                lanes = _lanes(main, min(self.streams, V))
+                _fork(lanes)
+                _C.backward_median_views([st.cuda_stream for st in lanes], P, pool["arr"], mp["marr"], V)
+                _join(lanes)
+                for g0, gcount in c.ranges:
+                    _C.backward_batch_median_raw(main.cuda_stream, P, pool["arr"], mp["marr"], V, means3D.grad.data_ptr(), g0, gcount)
+            for v in sync:
+                if gs[v] is None:
+                    continue
+                R, _color, radii, geom, binning, img = last["states"][v][:6]
+                if int(R) == 0:
+                    continue
+                dz = torch.empty((int(R),), dtype=torch.float32, device=dev)
+                _C.backward_median_raw(main.cuda_stream, P, W, H, int(R), geom.data_ptr(), binning.data_ptr(), img.data_ptr(),
+                                       c.settings[v].viewmatrix.data_ptr(), radii.data_ptr(), mp["pos"][v].data_ptr(), gs[v].data_ptr(), dz.data_ptr(),
+                                       means3D.grad.data_ptr())
 
     def _pooled(self, c: _Call, cap: int, names: Sequence[str] = (), Cf: int = 0) -> dict:
         """The batch's buffers, one tensor per kind for all views, and its tgs_view_t array: kept while the shapes and the capacity stay.
