@@ -489,6 +489,35 @@ int tgs_dist2(void* stream, int P, const float* points, float* mean_dist2, void*
  * distances ascending (FLT_MAX and index -1 where P < K), idx[P,K] int64.  Same workspace as tgs_dist2. */
 int tgs_knn_self(void* stream, int P, int K, const float* points, float* dists, long long* idx, void* workspace, size_t workspace_bytes);
 
+/* ---- mesh rasterizer: the inpainter's masks ----
+ * What Edit_core/tetgs_inpainter/mask_mesh_0822.py asks of its third-party rasterizer (rasterize + interpolate, :94-134, :183-188, :350-364):
+ * forward only, one image per call.  pos[V,4] clip-space fp32, tri[F,3] int32, rast[height*width*4] = (u, v, z/w, triangle index + 1) per pixel,
+ * all zero where nothing is hit; image row 0 is the row at clip y = -1 (bottom-up).  No antialiasing, no gradients, no derivative output, no
+ * ranged mode, no near-plane clipping.
+ * The rule:
+ *   snapping    X = rint((x/w * 0.5 + 0.5) * width * 256), Y likewise with height; pixel (i, j) has its centre at (256 i + 128, 256 j + 128).
+ *   dropped     whole: a triangle with a vertex at w <= 0, with a non-finite coordinate, or with |X| or |Y| above 2^29.
+ *   orientation A = (X1-X0)(Y2-Y0) - (X2-X0)(Y1-Y0) in int64; A = 0 covers nothing; both windings rasterize (edge functions times sign(A)).
+ *   coverage    for the directed edge a->b of the oriented triangle E(P) = (Xb-Xa)(Py-Ya) - (Yb-Ya)(Px-Xa); a pixel is covered iff on every edge
+ *               E > 0, or E = 0 and the edge owns its boundary: dy < 0, or dy = 0 and dx > 0.  Of an edge and its reverse exactly one is an
+ *               owner, so a mesh is watertight along shared edges.
+ *   depth       z/w, linear in screen space at the pixel centre, from the unsnapped coordinates; a fragment outside [-1, 1] is discarded; the
+ *               smallest depth wins, the lower triangle index on equal depth bits.  The result does not depend on the order in which
+ *               triangles are processed: two runs give the same bits (one 64-bit integer atomic min per fragment, no float atomics).
+ *   u, v        perspective-correct barycentrics of vertices 0 and 1 at the pixel centre, from the unsnapped coordinates, each clamped to
+ *               [0, 1], then both divided by max(u + v, 1).
+ * The kernels never read pos or attr outside [0, V): a triangle with an index out of range produces nothing, and tgs_mesh_interpolate writes 0
+ * for an ID outside [1, F].  width, height <= 8192; F <= 2^24 - 1 (the ID travels in a float).
+ * workspace: device scratch of tgs_mesh_workspace_bytes(F, width, height) bytes (0 for sizes that are refused); the calls allocate nothing
+ * and synchronise nothing.  F == 0 or V == 0: rast is all zero.
+ * tgs_mesh_interpolate: out[p*C + c] = u a0 + v a1 + (1 - u - v) a2 with the rows attr[i*C + c] of the vertices of triangle ID - 1 of pixel p
+ * (n_pixels of them; rast as written above, possibly of several images one behind the other); exactly 0 where ID = 0.  Any C >= 1. */
+size_t tgs_mesh_workspace_bytes(int F, int width, int height);
+int tgs_mesh_rasterize(void* stream, int V, int F, const float* pos, const int32_t* tri,
+                       int width, int height, float* rast, void* workspace, size_t workspace_bytes);
+int tgs_mesh_interpolate(void* stream, int V, int F, int C, const float* attr, const int32_t* tri,
+                         int64_t n_pixels, const float* rast, float* out);
+
 /* ---- Batched backward (multi-view steps) ----
  * Rasterizer::backward runs its per-Gaussian half (computeCov2DCUDA + preprocessCUDA of backward.cu) once per view; with
  * in-place accumulation that is 192 B of SH read plus 192 B of dL_dsh read AND written per Gaussian per view.  A batch

@@ -215,3 +215,25 @@ def config_scene(index: int):
     cloud = config_cloud(index)
     cams = [orbit_camera(c["width"], c["height"], azimuth_deg=k * 360.0 / c["views"]) for k in range(c["views"])]
     return cloud, cams, upstream_gradient(c["width"], c["height"], seed=c["seed"] + 1000)
+
+
+def icosphere(subdivisions: int = 0, radius: float = 1.0):
+    """A unit icosahedron subdivided ``subdivisions`` times -> (verts [V,3] float32, faces [F,3] int32, outward winding); F = 20 * 4^subdivisions
+    (4: 5 120 faces, 8: 1 310 720).  The mesh of examples/mesh_masks.py, tools/mesh_raster_loop.py and the mesh rasterizer's tests."""
+    t = (1.0 + math.sqrt(5.0)) / 2.0
+    v = np.array([[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t],
+                  [t, 0, -1], [t, 0, 1], [-t, 0, -1], [-t, 0, 1]], np.float64)
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    f = np.array([[0, 11, 5], [0, 5, 1], [0, 1, 7], [0, 7, 10], [0, 10, 11], [1, 5, 9], [5, 11, 4], [11, 10, 2], [10, 7, 6], [7, 1, 8],
+                  [3, 9, 4], [3, 4, 2], [3, 2, 6], [3, 6, 8], [3, 8, 9], [4, 9, 5], [2, 4, 11], [6, 2, 10], [8, 6, 7], [9, 8, 1]], np.int64)
+    for _ in range(int(subdivisions)):
+        V = len(v)
+        e = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), axis=1)          # the three edges of every face, face-major per edge slot
+        uniq, inv = np.unique(e[:, 0] * V + e[:, 1], return_inverse=True)
+        mid = v[uniq // V] + v[uniq % V]
+        mid /= np.linalg.norm(mid, axis=1, keepdims=True)
+        v = np.concatenate([v, mid])
+        n = len(f)
+        m01, m12, m20 = V + inv[:n], V + inv[n:2 * n], V + inv[2 * n:]
+        f = np.concatenate([np.stack([f[:, 0], m01, m20], 1), np.stack([f[:, 1], m12, m01], 1), np.stack([f[:, 2], m20, m12], 1), np.stack([m01, m12, m20], 1)])
+    return (v * radius).astype(np.float32), f.astype(np.int32)
