@@ -242,3 +242,83 @@ def test_the_upstream_tuple_check_with_a_feature_map():
     # every case of the existing check behaves as before (no channels: one per name)
     from tests.test_batch_extras_abi import test_the_upstream_tuple_check
     test_the_upstream_tuple_check()
+
+
+def test_the_upstream_caller_of_run_views_without_a_device():
+    """multiview._Upstream, what every route of run_views asks the upstream callables through: it passes the extra maps when the call has
+    any, accepts what the docstring of run_views lists, and rejects the rest with the messages of the pooled route."""
+    import torch
+    from youreditableavatar_amd.multiview import _Upstream
+    H, W, V, C = 6, 10, 3, 5
+    f = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt)
+    images, maps3 = f(V, 3, H, W), [f(V, 1, H, W), f(V, 1, H, W), f(V, C, H, W)]
+    plain = types.SimpleNamespace(H=H, W=W, V=V, names=[], Cf=0)
+    full = types.SimpleNamespace(H=H, W=W, V=V, names=["alpha", "depth", "features"], Cf=C)
+    seen = []
+
+    def caller(c, ret):
+        def batch(*args):
+            seen.append(("batch", [tuple(a.shape) for a in args]))
+            return ret
+        def view(v, *args):
+            seen.append((v, [tuple(a.shape) for a in args]))
+            return ret
+        return _Upstream(c, batch, None, require_gpu=False), _Upstream(c, None, view, require_gpu=False)
+
+    # without extra maps: a bare tensor, [V,3,H,W] or [3,H,W] from the batch callable, [3,H,W] from the view callable; made contiguous
+    for ret in (f(V, 3, H, W), f(3, H, W), f(3, W, H).transpose(1, 2)):
+        b, _ = caller(plain, ret)
+        assert not b.per_view
+        dL, extra = b.batch(images, [])
+        assert dL.is_contiguous() and tuple(dL.shape) == tuple(ret.shape) and len(extra) == V and all(len(e) == 0 for e in extra)
+        g, gs = b.views(images, [])(1)
+        assert tuple(g.shape) == (3, H, W) and len(gs) == 0
+    _, w = caller(plain, f(3, H, W))
+    assert w.per_view
+    g, gs = w.view(2, images, [])
+    assert tuple(g.shape) == (3, H, W) and len(gs) == 0 and seen[-1] == (2, [(3, H, W)])
+    g, gs = w.views(images, [])(0)
+    assert tuple(g.shape) == (3, H, W) and seen[-1] == (0, [(3, H, W)])
+    # with extra maps: the tuple, every extra entry [V,C,H,W], [C,H,W] or None from the batch callable, [C,H,W] or None from the view callable
+    b, _ = caller(full, (f(V, 3, H, W), f(V, 1, H, W), None, f(C, H, W)))
+    dL, extra = b.batch(images, maps3)
+    assert seen[-1] == ("batch", [(V, 3, H, W), (V, 1, H, W), (V, 1, H, W), (V, C, H, W)])
+    assert len(extra) == V and all(tuple(e[0].shape) == (1, H, W) and e[1] is None and tuple(e[2].shape) == (C, H, W) for e in extra)
+    g, gs = b.views(images, maps3)(2)
+    assert tuple(g.shape) == (3, H, W) and tuple(gs[0].shape) == (1, H, W) and gs[1] is None
+    _, w = caller(full, (f(3, H, W), None, f(1, H, W), f(C, H, W)))
+    g, gs = w.view(1, images, maps3)
+    assert seen[-1] == (1, [(3, H, W), (1, H, W), (1, H, W), (C, H, W)])
+    assert tuple(g.shape) == (3, H, W) and gs[0] is None and tuple(gs[1].shape) == (1, H, W) and tuple(gs[2].shape) == (C, H, W)
+    # rejected, with the messages of the pooled route
+    bare = "upstream must return a float32 GPU tensor [V,3,H,W] or [3,H,W]"
+    tup = ("upstream must return the tuple (dL_dimages, dL_dalpha, dL_ddepth, dL_dfeatures) when run_views returns alpha and depth and features "
+           "(an entry may be None, the first may not)")
+    one = "upstream_view must return [3,H,W]"
+    bad = [
+        (plain, f(V, 3, H, W, dt=torch.float64), bare, bare),                                    # float64
+        (plain, f(V, 3, H, W + 1), bare, bare),                                                  # a wrong shape
+        (plain, (f(V, 3, H, W),), bare, bare),                                                   # a tuple where a bare tensor is due
+        (plain, f(V, 3, H, W), None, one),                                                       # [V,3,H,W] from the view callable
+        (full, f(V, 3, H, W), tup, tup),                                                         # a bare tensor where a tuple is due
+        (full, (f(3, H, W), None, None), tup, tup),                                              # wrong arity
+        (full, (f(3, H, W, dt=torch.float64), None, None, None), bare, bare),
+        (full, (f(3, H, W), None, f(1, H, W, dt=torch.float64), None),
+         f"upstream: dL_ddepth must be None or a float32 GPU tensor {[V, 1, H, W]} or {[1, H, W]}", f"upstream: dL_ddepth must be None or a float32 GPU tensor {[1, H, W]}"),
+        (full, (f(3, H, W), None, None, f(1, H, W)),
+         f"upstream: dL_dfeatures must be None or a float32 GPU tensor {[V, C, H, W]} or {[C, H, W]}", f"upstream: dL_dfeatures must be None or a float32 GPU tensor {[C, H, W]}"),
+        (full, (f(V, 3, H, W), None, None, None), None, one),                                    # [V,3,H,W] from the view callable
+    ]
+    for c, ret, batch_message, view_message in bad:
+        b, w = caller(c, ret)
+        m = maps3 if c.names else []
+        for ask, message in ((lambda: b.batch(images, m), batch_message), (lambda: b.views(images, m), batch_message),
+                             (lambda: w.view(0, images, m), view_message), (lambda: w.views(images, m)(0), view_message)):
+            if message is None:
+                ask()
+            else:
+                with pytest.raises(RuntimeError) as e:
+                    ask()
+                assert str(e.value) == message
+    with pytest.raises(RuntimeError, match="GPU"):                                               # the default: a device is required
+        _Upstream(plain, lambda images: f(V, 3, H, W), None).batch(images, [])

@@ -1,270 +1,33 @@
-"""View-sharded data parallelism for the rasterizer (BASELINE.json configs 4-5).
+"""The multi-view step of the rasterizer on one GPU: ``SyncFreeBatch`` renders and back-propagates the views of a step without a host
+synchronisation per frame (``run_views``: three trips into the native library per step; ``run``: one rasterizer call per view), with the
+fused gradient accumulation of ``rasterize_accumulate`` / ``DeferredBackward`` underneath.
 
-The reference never batches (one view per optimisation step, Edit_core/tetgs_texture/refine.py:54,
-257-275).  Frames are independent given the (replicated) Gaussian parameters, so a batch of V views
-shards by view: each rank renders its contiguous shard view after view, autograd accumulates the
-per-Gaussian gradients of every view into ONE flat fp32 buffer (parameter ``.grad`` tensors are views
-into it), and the step ends with ONE all-reduce(sum) of that buffer -- RCCL over xGMI on GPUs
-(backend "nccl"), gloo in the CPU tests.  There is no other data-path collective.
-
-``FlatGradients`` and ``render_batch_sharded`` are host logic only: they run on CPU with any per-view
-render function (the tests inject the CPU oracle).
+The data-parallel host side -- ``shard_views``, ``FlatGradients``, ``render_batch_sharded`` -- lives in ``sharding`` and is re-exported
+here, where callers have always imported it from.
 """
 from __future__ import annotations
 
 from collections import namedtuple
 from typing import Callable, Iterable, List, Optional, Sequence
 
-import ctypes as C
 import os
 import threading
 
 import torch
-import torch.distributed as dist
 
 from .diff_gaussian_rasterization import _C
+from .sharding import FlatGradients, _PackedReduce, _coalesced_all_reduce_supported, render_batch_sharded, shard_views  # noqa: F401
 
 
-def shard_views(num_views: int, rank: int, world_size: int) -> range:
-    """Contiguous shard of ``range(num_views)`` for ``rank``; sizes differ by at most one."""
-    if not (0 <= rank < world_size):
-        raise ValueError(f"rank {rank} outside world of {world_size}")
-    base, extra = divmod(num_views, world_size)
-    start = rank * base + min(rank, extra)
-    return range(start, start + base + (1 if rank < extra else 0))
-
-
-class FlatGradients:
-    """One contiguous gradient buffer for a list of leaf parameters.
-
-    ``p.grad`` of every parameter becomes a view into ``self.flat``; autograd accumulates in place
-    across the views of a shard, and ``all_reduce`` sums the whole step with a single collective
-    (236 B per Gaussian on the SH path = 118 MB at 500k Gaussians)."""
-
-    PLANE_ALIGN = 64      # floats: level-major planes start on 256-byte boundaries (16-byte stores of the kernel, aligned slices for the collective)
-
-    def __init__(self, params: Sequence[torch.Tensor], sh_params: Optional[dict] = None, level_major: bool = False):
-        """``sh_params``: which parameters hold SH coefficients, NAMED by the caller -- ``{index in params: first coefficient}``: ``{4: 0}``
-        for a full ``[P, 16, 3]`` tensor at position 4 (``sh_coordinates``, tetgs_model.py:268-272), ``{4: 0, 5: 1}`` for the model's
-        ``_sh_coordinates_dc`` ``[P, 1, 3]`` and ``_sh_coordinates_rest`` ``[P, 15, 3]`` (:234-239).  Only these are reduced over their
-        live coefficients by ``all_reduce_rows(..., sh_degree=D)``; nothing is inferred from shapes (round 6, ADVICE: a ``[P, 4, 3]``
-        parameter that is not SH would have been cut to its leading rows).
-
-        ``level_major`` (round 6): the gradients of the named SH parameters are stored coefficient by coefficient -- ``flat`` holds, per SH
-        parameter, M planes of ``plane_stride`` = 3 P (rounded up to 64) floats, and ``p.grad`` is the ``[P, M, 3]`` VIEW of them with strides
-        (3, plane_stride, 1).  The live coefficients of a step rendered below the stored degree are then the leading planes -- one contiguous
-        slice per range of Gaussians and coefficient, handed to the collective as it is: no staging copy in front of it, none behind it
-        (row-major: a strided pack and unpack of 28 MB per step at 500 k Gaussians and degree 0, 0.128 ms where no byte crosses a link).
-        ``SyncFreeBatch.run_views`` sees the strides and lets the per-Gaussian pass write that layout (tgs_backward_batch_range_planes).
-        An optimizer reads such a ``.grad`` like any other strided tensor."""
-        self.params = list(params)
-        if not self.params:
-            raise ValueError("no parameters")
-        self.sh_params = {int(k): int(v) for k, v in (sh_params or {}).items()}
-        for i, first in self.sh_params.items():
-            if not (0 <= i < len(self.params)) or self.params[i].dim() != 3 or int(self.params[i].shape[2]) != 3 or first < 0:
-                raise ValueError(f"sh_params[{i}]: not a [P, M, 3] parameter of this buffer")
-        dev, dt = self.params[0].device, self.params[0].dtype
-        for p in self.params:
-            if p.device != dev or p.dtype != dt or not p.is_leaf or not p.requires_grad:
-                raise ValueError("parameters must be leaf tensors requiring grad, on one device, of one dtype")
-        self.level_major = bool(level_major) and bool(self.sh_params)
-        # region of parameter i in `flat`: (offset, numel, plane_stride or 0)
-        self.regions, off = [], 0
-        A = self.PLANE_ALIGN
-        for i, p in enumerate(self.params):
-            if self.level_major and i in self.sh_params:
-                off = (off + A - 1) // A * A
-                stride = (3 * int(p.shape[0]) + A - 1) // A * A
-                n = int(p.shape[1]) * stride
-                self.regions.append((off, n, stride))
-            else:
-                n = p.numel()
-                self.regions.append((off, n, 0))
-            off += n
-        self.flat = torch.zeros(off, dtype=dt, device=dev)
-        for p, (o, n, stride) in zip(self.params, self.regions):
-            if stride:
-                P, M = int(p.shape[0]), int(p.shape[1])
-                p.grad = self.flat[o:o + n].view(M, stride)[:, :3 * P].view(M, P, 3).permute(1, 0, 2)     # [P, M, 3], strides (3, stride, 1)
-            else:
-                p.grad = self.flat[o:o + n].view_as(p)
-
-    def zero_(self) -> None:
-        self.flat.zero_()
-
-    def all_reduce(self, group=None, async_op: bool = False, sh_degree: Optional[int] = None):
-        """Sum over ranks (no-op without an initialised process group or with world size 1).  ``sh_degree``: the step's active SH degree --
-        SH parameters stored for a higher one are reduced over their live coefficients only (all_reduce_rows)."""
-        if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
-            return None
-        if sh_degree is not None and any(self._sh_live(i, sh_degree) is not None for i in range(len(self.params))):
-            P = int(self.params[0].shape[0])
-            if any(int(p.shape[0]) != P for p in self.params):
-                raise ValueError("all_reduce(sh_degree=...) reduces by rows: every parameter must be [P, ...] with the same P")
-            works = self.all_reduce_rows(0, P, group=group, sh_degree=sh_degree)
-            if async_op:
-                return works[0] if len(works) == 1 else _PackedReduce(works, [])
-            for w in works:
-                w.wait()
-            return None
-        return dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=group, async_op=async_op)
-
-    def row_slices(self, first: int, count: int) -> List[torch.Tensor]:
-        """The pieces of ``flat`` that hold the gradients of Gaussians [first, first + count): one contiguous slice per parameter
-        (every parameter is [P, ...] row-major, so a range of Gaussians is a range of rows)."""
-        out = []
-        for p, (off, n, stride) in zip(self.params, self.regions):
-            if stride:                                       # level-major: one slice per coefficient plane
-                out.extend(self.flat[off + k * stride + 3 * first: off + k * stride + 3 * (first + count)] for k in range(int(p.shape[1])))
-            else:
-                row = p.numel() // max(int(p.shape[0]), 1)
-                out.append(self.flat[off + first * row: off + (first + count) * row])
-        return out
-
-    # ---- live SH rows ------------------------------------------------------------------------------------------------------------
-    # 192 of the 236 B a Gaussian's gradients take on the SH path are dL_dsh, and the reference trains most of its iterations below the
-    # stored degree: the refine stage raises `sh_levels` step by step (refine_3dgs.py:165-166), the inpainting stage stays at one level
-    # (paint_2dgs.py:61-63).  Coefficients above the active degree get exactly zero gradient on every rank (backward.cu:20-139 writes
-    # only the active ones), so their sum over ranks is known without moving a byte: only the (D + 1)^2 live coefficients of each SH
-    # parameter are reduced -- packed into a contiguous staging slice, reduced, unpacked on wait().
-    def _sh_live(self, index: int, sh_degree: Optional[int]) -> Optional[int]:
-        """Live leading entries of dim 1 of parameter `index` at the active SH degree: an SH parameter whose first entry is coefficient
-        `first` (``sh_params``) keeps (D + 1)^2 - first of them; None: not an SH parameter, or every entry is live.  The dead entries
-        must be exactly zero on every rank (the kernels write zeros there: backward.cu:20-139 touches the active coefficients only)."""
-        if sh_degree is None:
-            return None
-        if not self.sh_params:
-            raise ValueError("sh_degree given, but this FlatGradients was built without sh_params: name the SH parameters")
-        first = self.sh_params.get(index)
-        if first is None:
-            return None
-        M = int(self.params[index].shape[1])
-        live = min(max((int(sh_degree) + 1) ** 2 - first, 0), M)
-        return None if live >= M else live
-
-    def reduced_bytes(self, count: Optional[int] = None, sh_degree: Optional[int] = None) -> int:
-        """Bytes per rank that all_reduce_rows(first, count, sh_degree=...) hands to the collective (count None: all Gaussians)."""
-        total = 0
-        for i, p in enumerate(self.params):
-            P = max(int(p.shape[0]), 1)
-            row = p.numel() // P
-            live = self._sh_live(i, sh_degree)
-            if live is not None:
-                row = live * 3
-            total += row * (P if count is None else int(count)) * p.element_size()
-        return total
-
-    def all_reduce_rows(self, first: int, count: int, group=None, even_alone: bool = False, sh_degree: Optional[int] = None):
-        """Asynchronous sum over ranks of the gradients of Gaussians [first, first + count) -- one coalesced collective over the
-        parameters' slices (a single RCCL group launch), enqueued behind whatever the current stream holds, so it runs beside the kernels
-        that follow (the per-Gaussian pass over the next range, ``SyncFreeBatch.run_views(grad_chunks=..., on_chunk=...)``).  Returns the
-        handles to ``wait()`` on before the gradients are used (empty without a process group).
-
-        ``sh_degree``: the ACTIVE SH degree of the step.  SH parameters stored for a higher degree are reduced over their live
-        coefficients only (see above): 44 + 12 (D + 1)^2 bytes per Gaussian instead of 236 -- 28 MB instead of 118 MB per step at 500 k
-        Gaussians and degree 0.  Every rank must pass the same value.
-
-        Coalesced or one collective per slice is decided ONCE per backend, before anything is issued and identically on every rank
-        (``_coalesced_all_reduce_supported``): no exception handling around collectives that may already be in flight -- a fallback taken
-        by one rank only, or after a partial issue, would double-sum or unpair them.  ``even_alone``: issue the collectives at world size 1
-        too (tests: the RCCL path on a one-GPU box)."""
-        if not dist.is_available() or not dist.is_initialized() or (dist.get_world_size(group) == 1 and not even_alone):
-            return []
-        pieces, packed = [], []
-        for i, (p, (off, n, stride)) in enumerate(zip(self.params, self.regions)):
-            P = max(int(p.shape[0]), 1)
-            row = p.numel() // P
-            live = self._sh_live(i, sh_degree)
-            if stride:                                       # level-major: the live coefficients are the leading planes -- slices of `flat`, no staging
-                planes = int(p.shape[1]) if live is None else live
-                if count > 0 and planes > 0:
-                    if first == 0 and count == P:            # all Gaussians: the planes, padding included (zeros), are ONE slice
-                        pieces.append(self.flat[off: off + planes * stride])
-                    else:
-                        pieces.extend(self.flat[off + k * stride + 3 * first: off + k * stride + 3 * (first + count)] for k in range(planes))
-            elif live is None:
-                t = self.flat[off + first * row: off + (first + count) * row]
-                if t.numel():
-                    pieces.append(t)
-            elif live > 0 and count > 0:
-                src = self.flat[off + first * row: off + (first + count) * row].view(count, int(p.shape[1]), 3)[:, :live, :]
-                stage = self._staging(i, first, count * live * 3)
-                stage.view(count, live, 3).copy_(src)
-                pieces.append(stage)
-                packed.append((src, stage.view(count, live, 3)))
-        if not pieces:
-            return []
-        if _coalesced_all_reduce_supported(group):
-            with dist._coalescing_manager(group=group, async_ops=True) as cm:
-                for t in pieces:
-                    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-            works = [cm]
-        else:
-            works = [dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group, async_op=True) for t in pieces]
-        return [_PackedReduce(works, packed)] if packed else works
-
-    def _staging(self, index: int, first: int, numel: int) -> torch.Tensor:
-        """contiguous staging slice for the live coefficients of parameter `index`, range starting at `first` (kept from step to step;
-        one per range: several ranges are in flight at once)"""
-        pool = self.__dict__.setdefault("_stage", {})
-        t = pool.get((index, first))
-        if t is None or t.numel() != numel:
-            t = pool[(index, first)] = torch.empty(numel, dtype=self.flat.dtype, device=self.flat.device)
-        return t
-
-
-class _PackedReduce:
-    """Handle of a range whose SH parameters were reduced through staging slices: wait() waits for the collectives, then puts the summed
-    live coefficients back into the flat buffer (on the current stream, behind the wait)."""
-
-    def __init__(self, works, packed):
-        self.works, self.packed = works, packed
-
-    def wait(self):
-        for w in self.works:
-            w.wait()
-        for dst, stage in self.packed:
-            dst.copy_(stage)
-        return True
-
-
-_COALESCE_DECISION = {}
-
-
-def _coalesced_all_reduce_supported(group=None) -> bool:
-    """One group launch for several tensors (``allreduce_coalesced`` behind torch's coalescing context) exists for device tensors on the
-    ``nccl`` (= RCCL) backend; gloo rejects device tensors there.  A pure function of the backend's name and of the torch build, so every
-    rank decides the same; cached per backend.  ``TGS_COALESCE_ALLREDUCE=0`` forces one collective per slice (same on all ranks: the
-    launcher passes the environment on)."""
-    backend = str(dist.get_backend(group)).lower()
-    hit = _COALESCE_DECISION.get(backend)
-    if hit is None:
-        hit = backend == "nccl" and hasattr(dist, "_coalescing_manager") and os.environ.get("TGS_COALESCE_ALLREDUCE", "1") != "0"
-        _COALESCE_DECISION[backend] = hit
-    return hit
-
-
-def render_batch_sharded(render_view: Callable[[int], torch.Tensor], upstream: Callable[[int, torch.Tensor], torch.Tensor],
-                         num_views: int, grads: FlatGradients, group=None, rank: Optional[int] = None,
-                         world_size: Optional[int] = None, sh_degree: Optional[int] = None) -> List[int]:
-    """One data-parallel step over a batch of ``num_views`` views.
-
-    ``render_view(v)`` returns the image of view ``v`` (built on the parameters held by ``grads``);
-    ``upstream(v, image)`` returns dL/d image.  After the call every rank's ``grads.flat`` holds the
-    gradient of the whole batch.  Returns the views this rank rendered.  ``sh_degree``: the active SH degree the views are rendered
-    with (the same on every rank) -- only the live SH coefficients are reduced (FlatGradients.all_reduce_rows)."""
-    if rank is None:
-        rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
-    if world_size is None:
-        world_size = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-    mine = shard_views(num_views, rank, world_size)
-    grads.zero_()
-    for v in mine:
-        img = render_view(v)
-        img.backward(upstream(v, img.detach()))
-    grads.all_reduce(group, sh_degree=sh_degree)
-    return list(mine)
+def _grad_buffers(leaves: dict) -> dict:
+    """The ``.grad`` buffers the fused backward adds into: of every tensor of ``leaves`` that has elements and requires a gradient."""
+    into = {}
+    for name, t in leaves.items():
+        if t.numel() and t.requires_grad:
+            if not t.is_leaf or t.grad is None:
+                raise RuntimeError(f"rasterize_accumulate: {name} must be a leaf parameter with an allocated .grad (see FlatGradients)")
+            into[name] = t.grad
+    return into
 
 
 class DeferredBackward:
@@ -294,12 +57,7 @@ class DeferredBackward:
         L = self.leaves
         if L["colors_precomp"].numel():
             raise RuntimeError("DeferredBackward supports the SH path (per-view colours have per-view gradients)")
-        into = {}
-        for name, t in L.items():
-            if t.numel() and t.requires_grad:
-                if not t.is_leaf or t.grad is None:
-                    raise RuntimeError(f"rasterize_accumulate: {name} must be a leaf parameter with an allocated .grad (see FlatGradients)")
-                into[name] = t.grad
+        into = _grad_buffers(L)
         st = torch.cuda.current_stream()
         for v in self.views:                                 # buffers that were allocated on another stream of the batch
             for k in ("radii", "geom", "binning", "img"):
@@ -354,12 +112,7 @@ class _RasterizeAccumulate(torch.autograd.Function):
             _C.rasterize_gaussians_backward_render(rs.bg, grad_out_color, ctx.num_rendered, binning, img, L["means3D"].size(0))
             ctx.collector.add(rs, L, radii, geom, binning, img, ctx.num_rendered, ctx.means2D)
             return None, None, None, None, None, None, None, None, None, None
-        into = {}
-        for name, t in L.items():
-            if t.numel() and t.requires_grad:
-                if not t.is_leaf or t.grad is None:
-                    raise RuntimeError(f"rasterize_accumulate: {name} must be a leaf parameter with an allocated .grad (see FlatGradients)")
-                into[name] = t.grad
+        into = _grad_buffers(L)
         g2d = _C.rasterize_gaussians_backward_accumulate(
             rs.bg, L["means3D"].detach(), radii, L["colors_precomp"].detach(), L["scales"].detach(), L["rotations"].detach(), rs.scale_modifier,
             L["cov3D_precomp"].detach(), rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, L["sh"].detach(), rs.sh_degree,
@@ -432,12 +185,15 @@ def _read_verdicts(ready: Sequence[torch.cuda.Event], host: torch.Tensor) -> lis
 # A checked SyncFreeBatch.run_views call.  M: SH coefficients per Gaussian (0: per-view colours); precomp: per-view colours instead of SH;
 # dsh_plane > 0: shs.grad is level-major, its coefficient planes this many floats apart; params: the leaves whose .grad the batch writes
 # (means3D, opacities, scales, rotations, + sh); colors: colors_precomp [V,P,3], detached; ranges: (first, count) of the per-Gaussian
-# launches, multiples of 256 Gaussians, the same on every rank.
-_Call = namedtuple("_Call", "settings V P H W D M precomp dsh_plane params colors ranges")
+# launches, multiples of 256 Gaussians, the same on every rank.  The extra outputs: names: the maps asked for, of "alpha", "depth", "features",
+# in the order of the return value and of the upstream callables' tuples; Cf: the feature channels (0: none); features: [P,Cf], detached;
+# fgrad: features.grad where dL/d features goes, None when the features need no gradient.
+_Call = namedtuple("_Call", "settings V P H W D M precomp dsh_plane params colors ranges names Cf features fgrad")
 
 
-def _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_batch, upstream_view, colors_precomp, grad_chunks) -> _Call:
-    """Checks the arguments of ``SyncFreeBatch.run_views``, the consistency of the views' settings first."""
+def _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_batch, upstream_view, colors_precomp, grad_chunks,
+                return_alpha=False, return_depth=False, features=None) -> _Call:
+    """Checks the arguments of ``SyncFreeBatch.run_views``, the consistency of the views' settings first, the features last."""
     rs0 = settings[0]
     V, P, H, W, D = len(settings), int(means3D.size(0)), int(rs0.image_height), int(rs0.image_width), int(rs0.sh_degree)
     for rs in settings:
@@ -472,14 +228,16 @@ def _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_b
     n_chunks = max(1, min(int(grad_chunks), (P + 255) // 256))
     per = ((P + n_chunks - 1) // n_chunks + 255) // 256 * 256
     ranges = [(first, min(per, P - first)) for first in range(0, P, per)]
-    return _Call(settings, V, P, H, W, D, M, precomp, dsh_plane, params, colors_precomp, ranges)
+    Cf = _check_features(features, P, means3D.device) if features is not None else 0
+    names = [n for n, on in (("alpha", return_alpha), ("depth", return_depth), ("features", Cf)) if on]
+    return _Call(settings, V, P, H, W, D, M, precomp, dsh_plane, params, colors_precomp, ranges, names, Cf,
+                 features.detach() if Cf else None, features.grad if (Cf and features.requires_grad) else None)
 
 
-def _check_features(features, c: _Call) -> int:
+def _check_features(features, P: int, dev: torch.device) -> int:
     """``run_views(features=)``: [P, C] float32, contiguous, on the model's device, 1 <= C <= 16; with requires_grad a leaf with an allocated
     ``.grad`` of the same shape (the rule of the parameters) -> C"""
-    dev = c.params["means3D"].device
-    if not (torch.is_tensor(features) and features.dim() == 2 and int(features.size(0)) == c.P and features.dtype == torch.float32 and
+    if not (torch.is_tensor(features) and features.dim() == 2 and int(features.size(0)) == P and features.dtype == torch.float32 and
             features.device == dev and features.is_contiguous() and 1 <= int(features.size(1)) <= _C.FEATURE_MAX_CHANNELS):
         raise RuntimeError(f"run_views: features must be a contiguous float32 tensor [P,C] on the model's device, 1 <= C <= {_C.FEATURE_MAX_CHANNELS}")
     if features.requires_grad and not (features.is_leaf and features.grad is not None and features.grad.shape == features.shape and
@@ -557,6 +315,48 @@ def surface_votes(median_index: torch.Tensor, P: int, masks: Optional[torch.Tens
 def _of_view(dL: torch.Tensor, v: int) -> torch.Tensor:
     """View v's part of an upstream gradient ([3,H,W] / [1,H,W] / [C,H,W]: the same for every view; None stays None)."""
     return dL if (dL is None or dL.dim() == 3) else dL[v]
+
+
+class _Upstream:
+    """The upstream callables of one checked ``run_views`` call (built once per call): the one place that decides whether the extra maps
+    are passed, checks what comes back and holds the view callable to [3,H,W].  Every route of ``run_views`` asks through it, so a wrong
+    return fails with the same message on each.  ``c`` needs H, W, V, names and Cf only; ``require_gpu=False``: host tests."""
+
+    def __init__(self, c, upstream_batch, upstream_view, require_gpu: bool = True):
+        self.c, self.upstream_batch, self.upstream_view, self.require_gpu = c, upstream_batch, upstream_view, require_gpu
+        self.per_view, self.channels = upstream_view is not None, {"features": c.Cf}
+
+    def view(self, v: Optional[int], images: torch.Tensor, maps: Sequence[torch.Tensor]) -> tuple:
+        """Asks for view v, on the current stream -> (dL/d image [3,H,W], the gradients of its extra maps in the order of ``c.names``, each
+        [C,H,W] or None).  (``v`` None, for ``batch``: the batch callable, its gradients as they came, [V,...] or for all views.)"""
+        c = self.c
+        if v is None:
+            ret = self.upstream_batch(images, *maps)
+        elif maps:
+            ret = self.upstream_view(v, images[v], *[m[v] for m in maps])
+        else:
+            ret = self.upstream_view(v, images[v])
+        if c.names:
+            dL, gs = _upstream_extras_checked(ret, c, c.names, v is not None, self.require_gpu, self.channels)
+        else:
+            dL, gs = _upstream_checked(ret, c, self.require_gpu), ()
+        if v is not None and dL.dim() != 3:
+            raise RuntimeError("upstream_view must return [3,H,W]")
+        return dL, gs
+
+    def batch(self, images: torch.Tensor, maps: Sequence[torch.Tensor]) -> tuple:
+        """Asks for the whole batch -> (dL/d images, [V,3,H,W] or [3,H,W] for all views; per view the gradients of its extra maps, each
+        [C,H,W] or None)."""
+        dL, gs = self.view(None, images, maps)
+        return dL, [[_of_view(g, v) for g in gs] for v in range(self.c.V)] if gs else [()] * self.c.V
+
+    def views(self, images: torch.Tensor, maps: Sequence[torch.Tensor]) -> Callable[[int], tuple]:
+        """For the routes that take the views one by one -> ``of(v) = (dL/d image, extra gradients)`` of view v: the batch callable is asked
+        here, once; the view callable when ``of(v)`` is called."""
+        if self.per_view:
+            return lambda v: self.view(v, images, maps)
+        dL, extra = self.batch(images, maps)
+        return lambda v: (_of_view(dL, v), extra[v])
 
 
 class SyncFreeBatch:
@@ -680,89 +480,111 @@ class SyncFreeBatch:
         ``run`` / ``rasterize_accumulate`` / ``DeferredBackward`` carry none of these outputs (alpha, depth, feature channels); per-view
         features [V,P,C], more than 16 channels and half precision are not part of this path either.  The median depth and the surface index
         of the views are no argument of this call: ``median_views()`` and ``backward_median_views(dL)`` behind it."""
-        xnames = [n for n, on in (("alpha", return_alpha), ("depth", return_depth)) if on]      # the maps of tgs_view_extras_t
-        c = _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_batch, upstream_view, colors_precomp, grad_chunks)
+        c = _check_call(settings, means3D, opacities, shs, scales, rotations, upstream_batch, upstream_view, colors_precomp, grad_chunks, return_alpha, return_depth, features)
         self._last = None                                   # (and with it the synchronous frames median_views kept)
-        Cf = _check_features(features, c) if features is not None else 0
-        names = xnames + (["features"] if Cf else [])      # every extra map, in the order of the return value and of the callables' tuples
-        F = features.detach() if Cf else None
-        fgrad = features.grad if (Cf and features.requires_grad) else None
-        checked = lambda ret, per_view: _upstream_extras_checked(ret, c, names, per_view=per_view, channels={"features": Cf})
-        V, P, D, M, precomp = c.V, c.P, c.D, c.M, c.precomp
-        dev = means3D.device
+        ask = _Upstream(c, upstream_batch, upstream_view)
         cap = self.capacity()
-        if cap is None:                                     # no bound yet (or cooling down after an LDS-sort overflow): synchronous frames
-            if not accumulate:
-                for t in c.params.values():
-                    t.grad.zero_()
-                if fgrad is not None:
-                    fgrad.zero_()
-            states = [self._render_view(c, v) for v in range(V)]
-            images = torch.stack([s[1] for s in states])
-            maps = [torch.stack([self._map_of(c, name, states[v], F) for v in range(V)]) for name in names]
-            extra = [None] * V                               # per view: [dL/d map or None, per name]
-            if not names:
-                dL = upstream_batch(images) if upstream_batch is not None else torch.stack([upstream_view(v, images[v]) for v in range(V)])
-            elif upstream_batch is not None:
-                dL, gs = checked(upstream_batch(images, *maps), False)
-                extra = [[_of_view(g, v) for g in gs] for v in range(V)]
-            else:
-                rets = [checked(upstream_view(v, images[v], *[m[v] for m in maps]), True) for v in range(V)]
-                if any(r[0].dim() != 3 for r in rets):
-                    raise RuntimeError("upstream_view must return [3,H,W]")
-                dL, extra = torch.stack([r[0] for r in rets]), [r[1] for r in rets]
-            gcol = torch.empty((V, P, 3), dtype=torch.float32, device=dev) if precomp else None
-            scratch = torch.empty_like(shs) if c.dsh_plane else None
-            self.viewspace_grads = torch.stack([self._backward_view(c, v, states[v], _of_view(dL, v), gcol, scratch, names, extra[v], F, fgrad) for v in range(V)])
-            self.color_grads = gcol
-            self._learn(max(s[0] for s in states))
-            for first, count in (c.ranges if on_chunk is not None else []):
+        if cap is None:                                     # no bound yet: synchronous frames
+            images, maps, seen = self._step_synchronous(c, ask, accumulate)
+            tiles, eager = None, False
+            last = dict(c=c, pool=None, sync=list(range(c.V)), chunked=on_chunk is not None)
+        else:
+            pool, rows, eager = self._step_pooled(c, ask, cap, accumulate, on_chunk)
+            images, maps = pool["images"], [pool[name] for name in c.names]
+            seen = max(R for R, _rejected, _tiles in rows)
+            redo = [v for v, (_R, rejected, _tiles) in enumerate(rows) if rejected]
+            if redo:
+                self.rejected += len(redo)
+                seen = max(seen, self._render_again(c, ask, pool, redo))
+            tiles = [max(counts) for counts in zip(*(tiles for _R, _rejected, tiles in rows))]
+            last = dict(c=c, pool=pool, cap=cap, sync=redo, chunked=on_chunk is not None)
+        if on_chunk is not None and not eager:
+            for first, count in c.ranges:     # the same calls in the same order as on a rank that had nothing to render again (collectives must pair up)
                 on_chunk(first, count)
-            self._last = dict(c=c, pool=None, sync=list(range(V)), chunked=on_chunk is not None)
-            return (images, *maps) if names else images
+        self._learn(seen, tiles)
+        self._last = last
+        return (images, *maps) if c.names else images
 
-        pool = self._pooled(c, cap, names, Cf)
-        self._fill_views(c, pool, F)
-        arr, images, gcol = pool["arr"], pool["images"], pool["gcol"]
+    # ---- the three routes of run_views ----
+    def _step_synchronous(self, c: _Call, ask: _Upstream, accumulate: bool) -> tuple:
+        """The step of a batch that has no bound yet: every view through the synchronous forward, every loss, then every view's backward
+        -> (images [V,3,H,W], the extra maps, the largest instance count)."""
+        views = range(c.V)
+        if not accumulate:
+            for t in c.params.values():
+                t.grad.zero_()
+            if c.fgrad is not None:
+                c.fgrad.zero_()
+        states = [self._render_view(c, v) for v in views]
+        images = torch.stack([s[1] for s in states])
+        maps = [torch.stack([self._map_of(c, name, states[v]) for v in views]) for name in c.names]
+        grads = list(map(ask.views(images, maps), views))   # (every loss in front of the first backward)
+        z = lambda: torch.empty((c.V, c.P, 3), dtype=torch.float32, device=images.device)
+        self.viewspace_grads, self.color_grads = z(), (z() if c.precomp else None)
+        self._backward_views(c, views, states, grads.__getitem__, self.viewspace_grads, self.color_grads)
+        return images, maps, max(s[0] for s in states)
+
+    def _render_again(self, c: _Call, ask: _Upstream, pool: dict, redo: Sequence[int]) -> int:
+        """The views ``redo`` of a pooled step, rejected on the device (they rendered the background and accumulated nothing): through the
+        synchronous forward into their slices of the pooled images and maps, then loss and backward view by view -- the batch callable is
+        asked again first: its gradients depend on the corrected frames -> the largest instance count."""
+        states = {v: self._render_view(c, v) for v in redo}
+        images, maps = pool["images"], [pool[name] for name in c.names]
+        for v in redo:
+            images[v].copy_(states[v][1])
+            for name, m in zip(c.names, maps):
+                m[v].copy_(self._map_of(c, name, states[v]))
+        self._backward_views(c, redo, states, ask.views(images, maps), pool["g2d"], pool["gcol"])
+        return max(states[v][0] for v in redo)
+
+    def _backward_views(self, c: _Call, views: Sequence[int], states, grads_of: Callable[[int], tuple], g2d: torch.Tensor, gcol: Optional[torch.Tensor]) -> None:
+        """The backward of synchronously rendered views, one after the other on the current stream: ``grads_of(v)`` gives view v's upstream
+        gradients (_Upstream.views), its dL/d means2D lands in ``g2d[v]``, its colour gradients (per-view colours) in ``gcol[v]``."""
+        scratch = torch.empty_like(c.params["sh"]) if c.dsh_plane else None
+        for v in views:
+            g, gs = grads_of(v)
+            g2d[v].copy_(self._backward_view(c, v, states[v], g, gcol, scratch, gs))
+
+    def _step_pooled(self, c: _Call, ask: _Upstream, cap: int, accumulate: bool, on_chunk) -> tuple:
+        """The sync-free step on the pooled buffers, sized for ``cap`` instances per view: forward and extra outputs of every view on the
+        lanes, the upstream callables, the per-pixel backward on the lanes, then the per-Gaussian pass range by range on the calling stream
+        with ``on_chunk`` behind each range -> (the pool, the views' verdicts (_read_verdicts), whether on_chunk has been called)."""
+        p, s0 = c.params, c.settings[0]
+        means3D, opacities, scales, rotations, shs = p["means3D"], p["opacities"], p["scales"], p["rotations"], p.get("sh")
+        V, P, D, M, precomp, names, fgrad = c.V, c.P, c.D, c.M, c.precomp, c.names, c.fgrad
+        dev = means3D.device
+        pool = self._pooled(c, cap)
+        self._fill_views(c, pool)
+        arr, images = pool["arr"], pool["images"]
         xarr, farr, maps = pool.get("xarr"), pool.get("farr"), [pool[name] for name in names]
-        with_depth = False                                  # a view has a depth gradient: the z-path pass follows every range of the per-Gaussian pass
-        with_feat = False                                   # a view has a feature gradient: dL/d features follows every range as well
         main = torch.cuda.current_stream(dev)
         lanes = _lanes(main, min(self.streams, V))
         with torch.cuda.device(dev):
-            split = self.split and upstream_view is not None and len(lanes) >= 4
+            split = self.split and ask.per_view and len(lanes) >= 4
             bin_lanes, ren_lanes = (lanes[:len(lanes) // 2], lanes[len(lanes) // 2:]) if split else (lanes, lanes)
             _fork(lanes)
             _C.set_render_streams([st.cuda_stream for st in ren_lanes] if split else [])
             try:
                 _C.forward_views([st.cuda_stream for st in bin_lanes], cap, P, D, M, means3D.data_ptr(), None if precomp else shs.data_ptr(), opacities.data_ptr(),
-                                 scales.data_ptr(), settings[0].scale_modifier, rotations.data_ptr(), arr, V, prefiltered=settings[0].prefiltered, opt=self.options)
+                                 scales.data_ptr(), s0.scale_modifier, rotations.data_ptr(), arr, V, prefiltered=s0.prefiltered, opt=self.options)
             finally:
                 _C.set_render_streams([])
-            if xnames:
+            if xarr is not None:
                 # the maps read what k_render_fwd wrote: on the lane each view composited on, behind it without an event
                 _C.outputs_views([st.cuda_stream for st in ren_lanes], P, arr, xarr, V)
-            if Cf:
+            if farr is not None:
                 _C.features_views([st.cuda_stream for st in ren_lanes], P, arr, farr, V)
-            if upstream_view is None:
+            if not ask.per_view:
                 _join(lanes)
                 ready = [torch.cuda.Event()]                # (the verdicts are in pinned memory once the scans have run: tgs_view_t.host_meta)
                 ready[0].record(main)
-                if names:
-                    dL, gs = checked(upstream_batch(images, *maps), False)
-                    for v in range(V):
-                        gv = [_of_view(g, v) for g in gs]
-                        with_depth |= bool(xnames) and self._set_extra_grads(pool, v, names, gv)
-                        with_feat |= bool(Cf) and self._set_feature_grad(pool, v, gv[-1])
-                    self._keep = gs                              # (alive until the next batch)
-                else:
-                    dL = _upstream_checked(upstream_batch(images), c)
-                for v in range(V):
-                    arr[v].dL_dpix = _of_view(dL, v).data_ptr()
+                dL, extra = ask.batch(images, maps)
+                grads = [(v, _of_view(dL, v), extra[v]) for v in range(V)]
+                self._keep = extra                          # (alive until the next batch)
                 _fork(lanes)
             else:
                 # every lane: the verdicts of its views leave for the host, then loss and backward of each view follow on the same stream
-                ready, dLs = [], []
+                ready, grads, ask_view = [], [], ask.view
                 for st in bin_lanes:
                     with torch.cuda.stream(st):
                         ev = torch.cuda.Event()             # behind the lane's forwards: their scans have written the verdicts to pinned memory
@@ -771,23 +593,19 @@ class SyncFreeBatch:
                 for l, st in enumerate(ren_lanes):
                     with torch.cuda.stream(st):
                         for v in range(l, V, len(ren_lanes)):
-                            if names:
-                                g, gs = checked(upstream_view(v, images[v], *[m[v] for m in maps]), True)
-                            else:
-                                g, gs = _upstream_checked(upstream_view(v, images[v]), c), []
-                            if g.dim() != 3:
-                                raise RuntimeError("upstream_view must return [3,H,W]")
-                            for t in [g] + [x for x in gs if x is not None]:
-                                t.record_stream(st)
-                            dLs.append((v, g, gs))
-                for v, g, gs in dLs:
-                    arr[v].dL_dpix = g.data_ptr()
-                    if names:
-                        with_depth |= bool(xnames) and self._set_extra_grads(pool, v, names, gs)
-                        with_feat |= bool(Cf) and self._set_feature_grad(pool, v, gs[-1])
-                self._keep = dLs                                 # (alive until the next batch)
-            bwd_lanes = [st.cuda_stream for st in (lanes if upstream_view is None else ren_lanes)]
-            if Cf:                                          # colour + alpha, then depth, then the features' share, per view on its lane
+                            g, gs = ask_view(v, images, maps)
+                            g.record_stream(st)
+                            for x in gs:
+                                if x is not None:
+                                    x.record_stream(st)
+                            grads.append((v, g, gs))
+                self._keep = grads                          # (alive until the next batch)
+            for v, g, _gs in grads:
+                arr[v].dL_dpix = g.data_ptr()
+            # a view has a depth gradient: the z-path pass follows every range of the per-Gaussian pass; a feature gradient: dL/d features too
+            with_depth, with_feat = self._set_extra_grads(c, pool, grads) if names else (False, False)
+            bwd_lanes = [st.cuda_stream for st in (ren_lanes if ask.per_view else lanes)]
+            if farr is not None:                            # colour + alpha, then depth, then the features' share, per view on its lane
                 _C.backward_render_views_features(bwd_lanes, P, arr, xarr, farr, V, opt=self.options)
             elif names:
                 _C.backward_render_views_extras(bwd_lanes, P, arr, xarr, V, opt=self.options)
@@ -801,7 +619,7 @@ class SyncFreeBatch:
             # the one per-Gaussian pass of the step, range by range: a range's gradients are final behind its launch
             for g0, gcount in c.ranges:
                 _C.backward_batch_raw(main.cuda_stream, P, D, M, arr, V, means3D.data_ptr(), None if precomp else shs.data_ptr(), scales.data_ptr(),
-                                      settings[0].scale_modifier, rotations.data_ptr(), opacities.grad.data_ptr(), means3D.grad.data_ptr(),
+                                      s0.scale_modifier, rotations.data_ptr(), opacities.grad.data_ptr(), means3D.grad.data_ptr(),
                                       None if precomp else shs.grad.data_ptr(), scales.grad.data_ptr(), rotations.grad.data_ptr(), accumulate, g0, gcount,
                                       dsh_plane_stride=c.dsh_plane)
                 if with_depth:                              # dz . (third row of each view's transform), behind the range's stored / accumulated dL_dmeans3D
@@ -810,43 +628,8 @@ class SyncFreeBatch:
                     _C.backward_batch_features_raw(main.cuda_stream, P, arr, farr, V, fgrad.data_ptr(), accumulate, g0, gcount)
                 if eager:
                     on_chunk(g0, gcount)
-        self.viewspace_grads = pool["g2d"]
-        self.color_grads = gcol
-        if rows is None:
-            rows = _read_verdicts(ready, pool["host"])
-        seen = max(R for R, _rejected, _tiles in rows)
-        redo = [v for v, (_R, rejected, _tiles) in enumerate(rows) if rejected]
-        if redo:
-            self.rejected += len(redo)
-            states = {v: self._render_view(c, v) for v in redo}
-            for v in redo:
-                images[v].copy_(states[v][1])
-                for name, m in zip(names, maps):
-                    m[v].copy_(self._map_of(c, name, states[v], F))
-            gs2 = [None] * len(names)
-            if upstream_view is not None:
-                dL2 = None
-            elif names:                                     # the gradient images depend on the re-rendered frames (and maps)
-                dL2, gs2 = checked(upstream_batch(images, *maps), False)
-            else:
-                dL2 = upstream_batch(images).contiguous()
-            scratch = torch.empty_like(shs) if c.dsh_plane else None
-            for v in redo:
-                gs = [_of_view(g, v) for g in gs2]
-                if dL2 is not None:
-                    g = _of_view(dL2, v)
-                elif names:
-                    g, gs = checked(upstream_view(v, images[v], *[m[v] for m in maps]), True)
-                else:
-                    g = _upstream_checked(upstream_view(v, images[v]), c)
-                pool["g2d"][v].copy_(self._backward_view(c, v, states[v], g, gcol, scratch, names, gs, F, fgrad))
-                seen = max(seen, states[v][0])
-        if on_chunk is not None and not eager:
-            for first, count in c.ranges:     # the same calls in the same order as on a rank that had nothing to render again (collectives must pair up)
-                on_chunk(first, count)
-        self._learn(seen, [max(counts) for counts in zip(*(tiles for _R, _rejected, tiles in rows))])
-        self._last = dict(c=c, pool=pool, cap=cap, sync=redo, chunked=on_chunk is not None)
-        return (images, *maps) if names else images
+        self.viewspace_grads, self.color_grads = pool["g2d"], pool["gcol"]
+        return pool, (rows if rows is not None else _read_verdicts(ready, pool["host"])), eager
 
     # ------------------------------------------------------------------------------------------------------------------
     # The median of the batch's views: calls of their own behind run_views.  The forward reads what the step's forward kernels left in the
@@ -945,13 +728,13 @@ class SyncFreeBatch:
                                        c.settings[v].viewmatrix.data_ptr(), radii.data_ptr(), mp["pos"][v].data_ptr(), gs[v].data_ptr(), dz.data_ptr(),
                                        means3D.grad.data_ptr())
 
-    def _pooled(self, c: _Call, cap: int, names: Sequence[str] = (), Cf: int = 0) -> dict:
+    def _pooled(self, c: _Call, cap: int) -> dict:
         """The batch's buffers, one tensor per kind for all views, and its tgs_view_t array: kept while the shapes and the capacity stay.
-        ``names`` (of "alpha", "depth", "features"): the extra maps asked for -- their buffers [V,1,H,W], the depth's dz scratch [V, cap] and
-        the tgs_view_extras_t array exist only then, and a call without them keeps the key (and the pool) it always had.  ``Cf`` > 0 (with
-        "features" in ``names``): the feature map's buffer [V,Cf,H,W] and the tgs_view_features_t array; the feature scratch [V, cap * Cf]
-        comes with the first feature gradient (_set_feature_grad)."""
-        dev = c.params["means3D"].device
+        ``c.names`` (of "alpha", "depth", "features"): the extra maps asked for -- their buffers [V,1,H,W], the depth's dz scratch [V, cap] and
+        the tgs_view_extras_t array exist only then, and a call without them keeps the key (and the pool) it always had.  ``c.Cf`` > 0 (with
+        "features" in ``c.names``): the feature map's buffer [V,Cf,H,W] and the tgs_view_features_t array; the feature scratch [V, cap * Cf]
+        comes with the first feature gradient (_set_extra_grads)."""
+        dev, names, Cf = c.params["means3D"].device, c.names, c.Cf
         key = (c.P, c.H, c.W, c.V, c.M, cap, dev, c.precomp) + ((tuple(names),) if names else ()) + ((Cf,) if Cf else ())
         if self._pool is None or self._pool["key"] != key:
             V, P = c.V, c.P
@@ -971,7 +754,7 @@ class SyncFreeBatch:
                     self._pool["dz"] = z(V, cap)            # one float per instance slot and view (tgs_view_extras_t.dz_scratch)
         return self._pool
 
-    def _fill_views(self, c: _Call, pool: dict, F: Optional[torch.Tensor] = None) -> None:
+    def _fill_views(self, c: _Call, pool: dict) -> None:
         """The pooled tgs_view_t array: each view's camera, its slices of the pooled buffers and its grid bounds (dL_dpix comes later)."""
         gb, bb, ib = pool["sizes"]
         tcap = self.tile_capacity()
@@ -995,43 +778,44 @@ class SyncFreeBatch:
                 x.out_alpha = pool["alpha"][v].data_ptr() if "alpha" in pool else None
                 x.out_depth = pool["depth"][v].data_ptr() if "depth" in pool else None
                 x.dL_dalpha = x.dL_ddepth = x.dz_scratch = None
-            if "farr" in pool:                              # the model's features and the map's slice; the gradient comes later (_set_feature_grad)
+            if "farr" in pool:                              # the model's features and the map's slice; the gradient comes later (_set_extra_grads)
                 f = pool["farr"][v]
-                f.C, f.features, f.out_features = int(F.size(1)), F.data_ptr(), pool["features"][v].data_ptr()
+                f.C, f.features, f.out_features = c.Cf, c.features.data_ptr(), pool["features"][v].data_ptr()
                 f.dL_dfeature_map = f.feature_scratch = None
 
     @staticmethod
-    def _set_extra_grads(pool: dict, v: int, names: Sequence[str], grads: Sequence[Optional[torch.Tensor]]) -> bool:
-        """View v's upstream gradients of the extra maps into the pooled tgs_view_extras_t array; -> whether it has a depth gradient."""
-        x, g = pool["xarr"][v], dict(zip(names, grads))
-        gA, gD = g.get("alpha"), g.get("depth")
-        x.dL_dalpha = gA.data_ptr() if gA is not None else None
-        x.dL_ddepth = gD.data_ptr() if gD is not None else None
-        x.dz_scratch = pool["dz"][v].data_ptr() if gD is not None else None
-        return gD is not None
+    def _set_extra_grads(c: _Call, pool: dict, grads: Sequence[tuple]) -> tuple:
+        """The views' upstream gradients of the extra maps -- ``grads``: per view (v, dL/d image, the extra gradients in the order of
+        ``c.names``, any of them None) -- into the pooled tgs_view_extras_t and tgs_view_features_t arrays -> (a view has a depth gradient,
+        a view has a feature gradient).  The feature scratch [V, cap * C] (C floats per instance slot and view) is allocated with the first
+        feature gradient the pool sees."""
+        with_depth = with_feat = False
+        for v, _g, gs in grads:
+            g = dict(zip(c.names, gs))
+            gA, gD, gF = g.get("alpha"), g.get("depth"), g.get("features")
+            if "xarr" in pool:
+                x = pool["xarr"][v]
+                x.dL_dalpha = gA.data_ptr() if gA is not None else None
+                x.dL_ddepth = gD.data_ptr() if gD is not None else None
+                x.dz_scratch = pool["dz"][v].data_ptr() if gD is not None else None
+                with_depth |= gD is not None
+            if "farr" in pool:
+                f = pool["farr"][v]
+                if gF is not None and pool["fscratch"] is None:
+                    pool["fscratch"] = torch.empty(pool["fscratch_shape"], dtype=torch.float32, device=gF.device)
+                f.dL_dfeature_map = gF.data_ptr() if gF is not None else None
+                f.feature_scratch = pool["fscratch"][v].data_ptr() if gF is not None else None
+                with_feat |= gF is not None
+        return with_depth, with_feat
 
     @staticmethod
-    def _set_feature_grad(pool: dict, v: int, g: Optional[torch.Tensor]) -> bool:
-        """View v's upstream gradient [C,H,W] of the feature map (or None) into the pooled tgs_view_features_t array; -> whether it has one.
-        The scratch [V, cap * C] (C floats per instance slot and view) is allocated with the first gradient the pool sees."""
-        f = pool["farr"][v]
-        if g is None:
-            f.dL_dfeature_map = f.feature_scratch = None
-            return False
-        if pool["fscratch"] is None:
-            pool["fscratch"] = torch.empty(pool["fscratch_shape"], dtype=torch.float32, device=g.device)
-        f.dL_dfeature_map, f.feature_scratch = g.data_ptr(), pool["fscratch"][v].data_ptr()
-        return True
-
-    @staticmethod
-    def _map_of(c: _Call, name: str, state: tuple, F: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The alpha / depth map [1,H,W] or the feature map [C,H,W] (of the features ``F``) of a view from _render_view (the synchronous
-        frame's state)."""
+    def _map_of(c: _Call, name: str, state: tuple) -> torch.Tensor:
+        """The alpha / depth map [1,H,W] or the feature map [C,H,W] of a view from _render_view (the synchronous frame's state)."""
         R, _color, _radii, geom, binning, img = state[:6]
         if name == "alpha":
             return _C.alpha_from_state(img, c.H, c.W)
         if name == "features":
-            return _C.features_from_state(geom, binning, img, F, c.P, c.H, c.W, int(R))
+            return _C.features_from_state(geom, binning, img, c.features, c.P, c.H, c.W, int(R))
         return _C.depth_from_state(geom, binning, img, c.P, c.H, c.W, int(R))
 
     def _render_view(self, c: _Call, v: int) -> tuple:
@@ -1041,21 +825,19 @@ class SyncFreeBatch:
                                       p["rotations"].detach(), rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, c.H, c.W,
                                       e if c.precomp else p["sh"].detach(), c.D, rs.campos, rs.prefiltered, rs.debug, pruning=self._pruning)
 
-    def _backward_view(self, c: _Call, v: int, state: tuple, dL: torch.Tensor, gcol: Optional[torch.Tensor],
-                       scratch: Optional[torch.Tensor], names: Sequence[str] = (), extra: Optional[Sequence] = None,
-                       F: Optional[torch.Tensor] = None, fgrad: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _backward_view(self, c: _Call, v: int, state: tuple, dL: torch.Tensor, gcol, scratch, extra: Sequence = ()) -> torch.Tensor:
         """The backward of a view from _render_view, in place: adds into the parameters' .grad (per-view colours: this view's alone, in gcol[v])
         and returns dL/d means2D.  The one-view kernel writes dL_dsh by rows: a level-major .grad gets it through the row-major ``scratch``.
-        ``names`` / ``extra``: the view's upstream gradients [1,H,W] / [C,H,W] (or None) of the extra maps; with one of the feature map, ``F``
-        are the features and dL/d features is added into ``fgrad`` (None: features that need no gradient -- it goes to a buffer of its own
-        that is dropped, the through-alpha share still reaches the parameters)."""
+        ``extra``: the view's upstream gradients [1,H,W] / [C,H,W] (or None) of the extra maps ``c.names``; with one of the feature map,
+        dL/d features is added into ``c.fgrad`` (None: features that need no gradient -- it goes to a buffer of its own that is dropped, the
+        through-alpha share still reaches the parameters)."""
         rs, p, e = c.settings[v], c.params, torch.Tensor([])
         R, _color, radii, geom, binning, img = state[:6]
-        kw = {"grad_out_" + n: g for n, g in zip(names, extra or ()) if g is not None}
+        kw = {"grad_out_" + n: g for n, g in zip(c.names, extra) if g is not None}
         into = {name: t.grad for name, t in p.items()}
         if "grad_out_features" in kw:
-            kw["features"] = F
-            into["features"] = fgrad if fgrad is not None else torch.zeros_like(F)
+            kw["features"] = c.features
+            into["features"] = c.fgrad if c.fgrad is not None else torch.zeros_like(c.features)
         if c.precomp:
             gcol[v].zero_()
             into["colors_precomp"] = gcol[v]
