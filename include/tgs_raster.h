@@ -518,6 +518,48 @@ int tgs_mesh_rasterize(void* stream, int V, int F, const float* pos, const int32
 int tgs_mesh_interpolate(void* stream, int V, int F, int C, const float* attr, const int32_t* tri,
                          int64_t n_pixels, const float* rast, float* out);
 
+/* ---- mesh rasterizer: antialias ----
+ * The third call of the painting stage on its mesh rasterizer (mask_mesh_0822.py :98, :139-141, :188, :356, :364; the geometry stage's
+ * part_nvdiff_rasterizer.py :108-191): blend across silhouette edges between horizontally and vertically adjacent pixels, by the position at
+ * which the edge crosses the segment between the two pixel centres.  Forward only, one image per call.  color[height*width*C] fp32, rast as
+ * tgs_mesh_rasterize writes it, pos[V,4], tri[F,3], topo[F,3] int32 (tgs_mesh_topology), out[height*width*C].
+ * The rule:
+ *   snapping    as the rasterizer's: the snapped X, Y, the `ok` test of a vertex (w > 0, finite, |X|, |Y| <= 2^29), the orientation sign
+ *               s = sign(A), and the edge function E_ab(P) = s [(Xb-Xa)(Py-Ya) - (Yb-Ya)(Px-Xa)].  Everything is int64; all products stay below 2^62.
+ *               Edge k of a triangle runs from vertex k to vertex (k+1) mod 3; its opposite vertex is (k+2) mod 3.
+ *   topology    topo[t][k] counts the OTHER triangles of tri that have the same unordered vertex pair as an edge: -1 no other triangle shares
+ *               the edge; o >= 0 exactly one other triangle shares it and o is that triangle's opposite vertex; -2 more than one other
+ *               triangle shares it.  A triangle with a repeated index or an index outside [0, V) is ignored as a neighbour and every entry of
+ *               its own row is -1.  topo depends on tri alone.
+ *   pairs       every pair of horizontally or vertically adjacent pixels inside the image.  The ID of a pixel is rast.w truncated to an integer
+ *               (0 if it is not a number of magnitude <= 2^24).  Equal IDs (including both 0): nothing happens.  Otherwise the chosen triangle T
+ *               is the one with an ID if only one pixel has one, else the one with the smaller rast.z (compared as fp32 values), on equal
+ *               (or unordered) z the lower ID.  P is the pixel that shows T, Q the other pixel, u = Q - P in snapped units: (+-256, 0) or
+ *               (0, +-256).  The pair contributes nothing if T's ID is outside [1, F], if one of its vertex indices is outside [0, V), if one
+ *               of its vertices is not ok, or if A = 0.
+ *   exit edge   the first k in 0, 1, 2 with D = s [(Xb-Xa) uy - (Yb-Ya) ux] < 0 (E falls from P towards Q), 0 <= E(P) <= -D (the edge line
+ *               crosses between the two centres) and the crossing within the edge's extent: min(Ya,Yb) <= Py <= max(Ya,Yb) for a horizontal
+ *               pair, min(Xa,Xb) <= Px <= max(Xa,Xb) for a vertical pair.  No such k: the pair contributes nothing.
+ *   silhouette  the exit edge is a silhouette if topo = -1, if topo = -2, or if topo = o >= 0, vertex o is ok and E_ab(o) >= 0 (the neighbour
+ *               folds to T's side, or is edge-on).  o not ok (or not a vertex), any other topo value, or not a silhouette: the pair contributes
+ *               nothing.  Interior edges of a front-facing surface never blend.
+ *   blend       t = E(P) / (-D), both converted to double, one division, rounded to fp32; a = t - 0.5 in fp32.  a > 0: Q receives
+ *               a (color[P] - color[Q]) per channel; a < 0: P receives (-a) (color[Q] - color[P]); a = 0: nothing.
+ *   output      out[p] = color[p] plus the contributions p receives from its up to four pairs, each rounded on its own and added in fp32 in
+ *               the fixed order: pair with the left neighbour, right, row below (j-1), row above.  color is read only, so contributions never
+ *               chain; a pixel that receives nothing is a bit-exact copy (NaN payloads aside).  No float atomics: two runs give the same bits.
+ * tgs_mesh_topology builds topo once per mesh (a hash on the 64-bit (lo, hi) vertex pair with integer CAS, count and min / max atomics; the
+ * table does not depend on the order in which threads ran); F == 0 writes nothing.  The kernels never read pos, tri or topo through an index
+ * out of range.  width, height <= 8192; F <= 2^24 - 1; any C >= 1.  Workspaces: device scratch of tgs_mesh_topology_workspace_bytes(F) /
+ * tgs_mesh_antialias_workspace_bytes(width, height) bytes (0 for sizes that are refused); the calls allocate nothing and synchronise nothing.
+ * F == 0 or V == 0: out is a copy of color.  out may not alias color. */
+size_t tgs_mesh_topology_workspace_bytes(int F);
+int tgs_mesh_topology(void* stream, int V, int F, const int32_t* tri, int32_t* topo, void* workspace, size_t workspace_bytes);
+size_t tgs_mesh_antialias_workspace_bytes(int width, int height);
+int tgs_mesh_antialias(void* stream, int V, int F, int C, const float* pos, const int32_t* tri, const int32_t* topo,
+                       int width, int height, const float* rast, const float* color, float* out,
+                       void* workspace, size_t workspace_bytes);
+
 /* ---- Batched backward (multi-view steps) ----
  * Rasterizer::backward runs its per-Gaussian half (computeCov2DCUDA + preprocessCUDA of backward.cu) once per view; with
  * in-place accumulation that is 192 B of SH read plus 192 B of dL_dsh read AND written per Gaussian per view.  A batch

@@ -19,18 +19,16 @@
 // list with its number of MESH_REGION^2-pixel screen regions), k_mesh_large (persistent workgroups over the flattened (large triangle,
 // region) items; a region is walked in 8x8-pixel blocks, one lane per pixel, four blocks per wave), k_mesh_resolve (one lane per pixel).
 // No lane walks an unbounded box, and a screen-filling triangle becomes (W / 32) x (H / 32) independent items.
-#include "tgs_device.hpp"
+#include "tgs_mesh_snap.hpp"
 
 namespace tgs {
 
 constexpr int MESH_SMALL = 4;             // boxes up to this many pixels a side are walked by the triangle's own lane
 constexpr int MESH_MEDIUM = 32;           // boxes up to this many pixels a side are walked by the triangle's wave
 constexpr int MESH_REGION = 32;           // a work item of the large path: one workgroup, 16 blocks of 8x8 pixels
-constexpr int MESH_MAX_DIM = 8192;        // width / height: (8192 / 32)^2 = 2^16 regions, times < 2^24 triangles, fits the 40-bit item count
 constexpr int MESH_LARGE_WGS = 2048;      // persistent workgroups of k_mesh_large
 constexpr unsigned long long MESH_EMPTY = ~0ull;
 constexpr unsigned long long MESH_ITEM_MASK = (1ull << 40) - 1ull;
-constexpr float MESH_SNAP_MAX = 536870912.0f;     // 2^29
 
 struct MeshWork {
     unsigned long long* keys;             // [W*H] winner per pixel
@@ -52,10 +50,6 @@ struct MeshTri {
     float zw0, dz1, dz2, iw0, iw1, iw2;
 };
 
-__device__ __forceinline__ bool mesh_finite4(float4 p)
-{
-    return fabsf(p.x) <= 3.4028234e38f && fabsf(p.y) <= 3.4028234e38f && fabsf(p.z) <= 3.4028234e38f && fabsf(p.w) <= 3.4028234e38f;      // (false for NaN)
-}
 __device__ __forceinline__ int floor_div256(int a) { return a >> 8; }              // arithmetic shift: floor for negative a as well
 
 // Everything about triangle t that does not depend on the pixel.  false: the triangle produces nothing.
@@ -69,12 +63,7 @@ __device__ __forceinline__ bool mesh_setup(int V, const float4* __restrict__ pos
     int X[3], Y[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        if (!mesh_finite4(p[k]) || !(p[k].w > 0.f)) return false;
-        sx[k] = (p[k].x / p[k].w * 0.5f + 0.5f) * (float)W;
-        sy[k] = (p[k].y / p[k].w * 0.5f + 0.5f) * (float)H;
-        const float fx = rintf(sx[k] * 256.0f), fy = rintf(sy[k] * 256.0f);
-        if (!(fabsf(fx) <= MESH_SNAP_MAX) || !(fabsf(fy) <= MESH_SNAP_MAX)) return false;
-        X[k] = (int)fx; Y[k] = (int)fy;
+        if (!mesh_snap(p[k], W, H, sx[k], sy[k], X[k], Y[k])) return false;
         zw[k] = p[k].z / p[k].w;
         iw[k] = 1.0f / p[k].w;
     }
@@ -321,7 +310,7 @@ int tgs_mesh_rasterize(void* stream, int V, int F, const float* pos, const int32
 {
     using namespace tgs;
     hipStream_t st = (hipStream_t)stream;
-    if (V < 0 || F < 0 || width <= 0 || height <= 0 || width > MESH_MAX_DIM || height > MESH_MAX_DIM || F > (1 << 24) - 1 || !rast || !workspace ||
+    if (V < 0 || F < 0 || width <= 0 || height <= 0 || width > MESH_MAX_DIM || height > MESH_MAX_DIM || F > MESH_MAX_FACES || !rast || !workspace ||
         (F > 0 && (!tri || (V > 0 && !pos))))
         return set_error(TGS_ERR_INVALID, "tgs_mesh_rasterize: V >= 0, 0 <= F < 2^24, 1 <= width, height <= 8192 and non-NULL pos / tri / rast / workspace required");
     MeshWork w;
