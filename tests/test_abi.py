@@ -63,6 +63,29 @@ def test_bindings_check_abi_version_and_struct_sizes():
     assert "could not be rebuilt" in src and "older than its sources" in src        # a failed rebuild of a stale library raises, it is not swallowed
 
 
+def test_the_accumulating_backward_is_a_forward_to_the_compiled_export():
+    """The one-view backward has one implementation, in the compiled module: _C.rasterize_gaussians_backward_accumulate keeps its signature and
+    hands it to rasterize_gaussians_backward_into; _C.py declares no ctypes signature of the library's one-view backward entry points."""
+    import inspect
+    import types
+    from diff_gaussian_rasterization import _C
+    into = _C._ext.rasterize_gaussians_backward_into
+    assert isinstance(into, types.BuiltinFunctionType)
+    for k in ("grad_out_alpha", "grad_out_depth", "grad_out_features", "grad_out_median", "features", "median_pos", "into"):
+        assert k in into.__doc__, k
+    POS, KW, empty = inspect.Parameter.POSITIONAL_OR_KEYWORD, inspect.Parameter.KEYWORD_ONLY, inspect.Parameter.empty
+    frame = ["background", "means3D", "radii", "colors", "scales", "rotations", "scale_modifier", "cov3D_precomp", "viewmatrix", "projmatrix", "tan_fovx", "tan_fovy",
+             "dL_dout_color", "sh", "degree", "campos", "geomBuffer", "R", "binningBuffer", "imageBuffer", "debug", "into"]
+    expected = [(n, POS, empty) for n in frame] + [("tile_bound", POS, 0), ("deterministic", POS, None), ("mid_bound", POS, 0)] + \
+               [(n, KW, None) for n in ("grad_out_alpha", "grad_out_depth", "grad_out_features", "features", "grad_out_median", "median_pos")]
+    got = [(p.name, p.kind, p.default) for p in inspect.signature(_C.rasterize_gaussians_backward_accumulate).parameters.values()]
+    assert got == expected
+    src = open(os.path.join(ROOT, "youreditableavatar_amd", "diff_gaussian_rasterization", "_C.py")).read()
+    for name in ("tgs_backward_features_opt", "tgs_backward_depth_opt", "tgs_backward_opt"):
+        assert name not in src, f"_C.py still mentions {name}"
+    assert "_ext.rasterize_gaussians_backward_into(" in inspect.getsource(_C.rasterize_gaussians_backward_accumulate)
+
+
 def test_library_is_independent_of_torch_and_oracle():
     out = subprocess.run(["ldd", lib_path()], capture_output=True, text=True).stdout
     assert "libtorch" not in out and "libc10" not in out, "the C ABI must not depend on torch"

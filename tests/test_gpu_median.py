@@ -21,8 +21,10 @@ import torch
 
 from tests import test_gpu_alpha as A
 from tests import test_gpu_depth as D
+from tests import test_gpu_features as Fe
 from tests import util
 from tests.test_depth_abi import z_row
+from tests.test_features_abi import make_features
 from tests.test_median_abi import yardstick
 
 pytestmark = pytest.mark.gpu
@@ -221,6 +223,117 @@ def test_backward_without_the_keyword_is_todays_call_and_the_accumulating_call_a
     _C.rasterize_gaussians_backward_accumulate(*args, deterministic=True, grad_out_median=_t(s["g_M"], gpu_device).reshape(1, s["H"], s["W"]), median_pos=pos)
     assert np.array_equal(into["means3D"].cpu().numpy(), m["dL_dmeans3D"])
     assert np.array_equal(into["opacities"].cpu().numpy(), m["dL_dopacity"])
+    # ... and so for every gradient, with every upstream in one call, on both kinds of model
+    for name in ("cloud_600_sparse", "g05_precomp_cov3d"):
+        _stored_against_accumulated(name, gpu_device)
+
+
+INTO = {"means3D": "dL_dmeans3D", "opacities": "dL_dopacity", "sh": "dL_dsh", "colors_precomp": "dL_dcolors", "scales": "dL_dscales", "rotations": "dL_drotations",
+        "cov3D_precomp": "dL_dcov3D", "features": "dL_dfeatures"}          # key of ``into`` -> the storing call's name for that gradient
+F_NAMES = NAMES[:8] + ("dL_dfeatures",)                   # the storing call's tuple without _with_conic, with a feature gradient
+C_ALL = 3
+
+
+def _all_upstreams(name, dev):
+    """-> the scene, a frame of it, the accumulating call's positional arguments without ``into``, and colour + alpha + depth + median +
+    features (C = 3) as the keywords of both exports"""
+    from diff_gaussian_rasterization import _C
+    s = scene(name)
+    H, W = s["H"], s["W"]
+    f = Fe.Frame(s["inp"], dev)
+    pos = _C.median_from_state(f.geom, f.binning, f.img, f.P, H, W, int(f.R))[2]
+    g_F = (np.random.Generator(np.random.PCG64(5153)).standard_normal((C_ALL, H, W)) / (H * W)).astype(np.float32)
+    maps = {"grad_out_" + k: _t(s[g], dev).reshape(1, H, W) for k, g in (("alpha", "g_A"), ("depth", "g_D"), ("median", "g_M"))}
+    kw = dict(maps, median_pos=pos, grad_out_features=_t(g_F, dev), features=_t(make_features(f.P, C_ALL, seed=103), dev))
+    args = (f.bg, f.means, f.radii, f.colors, f.scales, f.rots, f.sm, f.cov, f.view, f.proj, f.tfx, f.tfy, _t(s["dL"], dev), f.sh, f.D, f.campos, f.geom, f.R, f.binning,
+            f.img, False)
+    return s, f, args, kw
+
+
+def _into(f, fill, dev):
+    """every destination the frame's model has, filled with ``fill``"""
+    M = int(f.sh.shape[1]) if f.has_sh else 0
+    shapes = dict(means3D=(f.P, 3), opacities=(f.P, 1), features=(f.P, C_ALL))
+    shapes.update(dict(sh=(f.P, M, 3)) if f.has_sh else dict(colors_precomp=(f.P, 3)))
+    shapes.update(dict(scales=(f.P, 3), rotations=(f.P, 4)) if f.has_sr else dict(cov3D_precomp=(f.P, 6)))
+    return {k: torch.full(shape, fill, dtype=torch.float32, device=dev) for k, shape in shapes.items()}
+
+
+def _stored_against_accumulated(name, dev):
+    """One implementation under both exports: into zeroed buffers the accumulating call leaves the storing call's bits (0 + x = x), in every
+    gradient; into buffers of 0.25 it leaves 0.25 + x -- one fp32 addition per element (relative error <= 2^-24 each), the bar the two
+    paths of tests/test_gpu_api.py are held to: rel-L2 <= 1e-6."""
+    from diff_gaussian_rasterization import _C
+    s, f, args, kw = _all_upstreams(name, dev)
+    assert (f.has_sh, f.has_sr) == ((True, True) if name == "cloud_600_sparse" else (False, False)) and f.R > 0
+    assert name != "cloud_600_sparse" or (s["W"] % 16 and s["H"] % 16)      # 72 x 40: partial tiles at both edges (the fixture is 48 x 64: whole tiles)
+    stored = [dict(zip(F_NAMES, (g.cpu().numpy() for g in _C.rasterize_gaussians_backward(*args, deterministic=True, **kw)))) for _ in range(2)]
+    assert len(stored[0]) == 9
+    for k in F_NAMES:
+        assert np.array_equal(stored[0][k], stored[1][k]), f"{name} {k}: two deterministic storing calls differ"
+    assert np.any(stored[0]["dL_dfeatures"]) and np.any(stored[0]["dL_dmeans3D"])
+    for run in range(2):
+        into = _into(f, 0.0, dev)
+        g2d = _C.rasterize_gaussians_backward_accumulate(*args, into, deterministic=True, **kw)
+        assert np.array_equal(g2d.cpu().numpy(), stored[0]["dL_dmeans2D"]), f"{name} dL_dmeans2D (run {run})"
+        for k, g in into.items():
+            assert np.array_equal(g.cpu().numpy(), stored[0][INTO[k]].reshape(g.shape)), f"{name} into[{k}] (run {run}) is not the storing call's {INTO[k]}"
+    into = _into(f, 0.25, dev)
+    g2d = _C.rasterize_gaussians_backward_accumulate(*args, into, deterministic=True, **kw)
+    assert np.array_equal(g2d.cpu().numpy(), stored[0]["dL_dmeans2D"])
+    for k, g in into.items():
+        e = util.rel_l2(g.cpu().numpy(), 0.25 + stored[0][INTO[k]].reshape(g.shape).astype(np.float64))
+        print(f"{name}: into[{k}] = 0.25 + {INTO[k]}: rel-L2 {e:.3e}")
+        assert e <= 1e-6, (name, k, e)
+
+
+def test_both_backward_exports_reject_a_mistake_in_the_same_words_before_any_launch(gpu_device):
+    from diff_gaussian_rasterization import _C
+    dev = gpu_device
+    s, f, args, ok = _all_upstreams("cloud_600_sparse", dev)
+    H, W, P = s["H"], s["W"], f.P
+    z = lambda *shape, **k: torch.zeros(*shape, device=dev, **k)
+    into = _into(f, 0.25, dev)
+
+    def message(fn):
+        with pytest.raises(RuntimeError) as e:
+            fn()
+        return str(e.value)
+
+    feat = dict(grad_out_features=ok["grad_out_features"], features=ok["features"])
+    med = dict(grad_out_median=ok["grad_out_median"], median_pos=ok["median_pos"])
+    upstream = [("grad_out_alpha", dict(grad_out_alpha=z(1, 3, 3))), ("grad_out_depth", dict(grad_out_depth=z(1, H, W + 1))),
+                ("grad_out_features", dict(feat, grad_out_features=z(C_ALL, 3, 3))), ("grad_out_median", dict(med, grad_out_median=z(1, 3, 3))),
+                ("features", dict(grad_out_features=ok["grad_out_features"])),
+                ("features", dict(grad_out_features=z(0, H, W), features=z(P, 0))), ("features", dict(grad_out_features=z(17, H, W), features=z(P, 17))),
+                ("median_pos", dict(grad_out_median=ok["grad_out_median"])), ("median_pos", dict(med, median_pos=ok["median_pos"].float()))]
+    for word, kw in upstream:
+        a = message(lambda: _C.rasterize_gaussians_backward(*args, **kw))
+        b = message(lambda: _C.rasterize_gaussians_backward_accumulate(*args, into, **kw))
+        assert a == b and word in a and next(iter(kw)) in a, (kw.keys(), a, b)
+    wrong = [("means3D", dict(into, means3D=z(P, 4)), {}), ("means3D", dict(into, means3D=z(P, 3, dtype=torch.float64)), {}),
+             ("means3D", dict(into, means3D=z(3, P).t()), {}), ('into["features"]', {k: v for k, v in into.items() if k != "features"}, feat)]
+    for word, bad, kw in wrong:
+        text = message(lambda: _C.rasterize_gaussians_backward_accumulate(*args, bad, **kw))
+        assert word in text and (word != "means3D" or f"[{P}, 3]" in text), text
+    torch.cuda.synchronize()
+    for k, g in into.items():
+        assert bool((g == 0.25).all()), f"a rejected call wrote into[{k}]"
+
+
+def test_the_accumulating_backward_of_an_empty_model_touches_nothing(gpu_device):
+    from diff_gaussian_rasterization import _C
+    dev = gpu_device
+    inp = scene("cloud_600_sparse")["inp"]
+    empty = dict(inp, means3D=np.zeros((0, 3), np.float32), opacities=np.zeros((0, 1), np.float32), scales=np.zeros((0, 3), np.float32),
+                 rotations=np.zeros((0, 4), np.float32), shs=np.zeros((0, 4, 3), np.float32))
+    f = Frame(empty, dev)
+    into = {k: torch.full((5, n), 0.25, device=dev) for k, n in (("means3D", 3), ("opacities", 1), ("scales", 3), ("rotations", 4))}
+    g2d = _C.rasterize_gaussians_backward_accumulate(f.bg, f.means, f.radii, f.colors, f.scales, f.rots, f.sm, f.cov, f.view, f.proj, f.tfx, f.tfy,
+                                                     torch.zeros(3, f.H, f.W, device=dev), f.sh, f.D, f.campos, f.geom, f.R, f.binning, f.img, False, into, deterministic=True)
+    assert tuple(g2d.shape) == (0, 3) and g2d.dtype == torch.float32 and g2d.device == f.means.device
+    torch.cuda.synchronize()
+    assert all(bool((g == 0.25).all()) for g in into.values())
 
 
 # ---- the public API ----

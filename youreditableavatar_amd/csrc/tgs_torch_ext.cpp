@@ -15,6 +15,7 @@
 #include <stdexcept>
 #include <string>
 #include <tuple>
+#include <vector>
 
 #include "../../include/tgs_raster.h"
 
@@ -114,6 +115,91 @@ py::tuple rasterize_gaussians(const torch::Tensor& background, const torch::Tens
     return py::make_tuple(r, out_color, radii, bufs[0], bufs[1], bufs[2]);
 }
 
+// ---- the one-view backward: ONE implementation (BackwardFrame + Upstream -> backward_call) under two exports, rasterize_gaussians_backward
+// (gradients stored into fresh tensors, returned) and rasterize_gaussians_backward_into (gradients added into the caller's tensors) ----
+// the frame arguments both exports take (rasterize_points.h:42-64), tensors first
+struct BackwardFrame {
+    const torch::Tensor &background, &means3D, &radii, &colors, &scales, &rotations, &cov3D_precomp, &viewmatrix, &projmatrix, &dL_dout_color, &sh, &campos, &geomBuffer,
+        &binningBuffer, &imageBuffer;
+    float scale_modifier, tan_fovx, tan_fovy;
+    int degree;
+    int64_t R;
+    bool debug;
+    int P() const { return (int)means3D.size(0); }
+    int H() const { return (int)dL_dout_color.size(1); }
+    int W() const { return (int)dL_dout_color.size(2); }
+};
+
+using OptTensor = c10::optional<torch::Tensor>;       // (None = absent)
+
+// an upstream gradient of `count` elements, or absent (None): one sentence for the one mistake, `what` = how the sentence names the count
+Arg upstream_arg(const OptTensor& g, int64_t count, const c10::Device& dev, const char* name, const char* what)
+{
+    if (g && g->numel() != count) throw std::runtime_error(std::string(name) + " must have " + what);
+    return Arg(g ? *g : torch::Tensor(), dev, name);
+}
+
+// The upstream gradients of a frame's extra outputs (the extension keywords of both exports), validated once, and the scratch that travels with
+// them: dz (R floats) with a depth gradient, R * C floats with a feature gradient; the median's call runs behind the main one on the same
+// stream, where the depth's dz is free again, so it takes the same buffer.
+struct Upstream {
+    int C;                      // channels of the feature gradient (0: none)
+    Arg dA, dD, dF, feat, dM;
+    torch::Tensor mpos, dz, feat_scratch;
+    static int channels(const OptTensor& grad_out_features, const OptTensor& features, int P)
+    {
+        if (!grad_out_features) return 0;
+        if (!features || features->dim() != 2 || features->size(0) != P || features->size(1) < 1 || features->size(1) > TGS_FEATURE_MAX_CHANNELS)
+            throw std::runtime_error("grad_out_features needs features of shape [P,C], 1 <= C <= " + std::to_string(TGS_FEATURE_MAX_CHANNELS));
+        return (int)features->size(1);
+    }
+    Upstream(const BackwardFrame& f, const c10::Device& dev, const OptTensor& grad_out_alpha, const OptTensor& grad_out_depth, const OptTensor& grad_out_features,
+             const OptTensor& features, const OptTensor& grad_out_median, const OptTensor& median_pos)
+        : C(channels(grad_out_features, features, f.P())), dA(upstream_arg(grad_out_alpha, (int64_t)f.H() * f.W(), dev, "grad_out_alpha", "H*W elements ([1,H,W])")),
+          dD(upstream_arg(grad_out_depth, (int64_t)f.H() * f.W(), dev, "grad_out_depth", "H*W elements ([1,H,W])")),
+          dF(upstream_arg(grad_out_features, (int64_t)C * f.H() * f.W(), dev, "grad_out_features", "C*H*W elements ([C,H,W])")),
+          feat(C ? *features : torch::Tensor(), dev, "features"),
+          dM(upstream_arg(grad_out_median, (int64_t)f.H() * f.W(), dev, "grad_out_median", "H*W elements ([1,H,W])"))
+    {
+        const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
+        if (dM.p) {
+            if (!median_pos || median_pos->numel() != (int64_t)f.H() * f.W() || median_pos->scalar_type() != torch::kInt32)
+                throw std::runtime_error("grad_out_median needs median_pos, the int32 map [1,H,W] of median_from_state");
+            mpos = (median_pos->device() == dev ? *median_pos : median_pos->to(dev)).contiguous();
+        }
+        if (dD.p || dM.p) dz = torch::empty({f.R > 0 ? f.R : 1}, f32);
+        if (C) feat_scratch = torch::empty({f.R > 0 ? f.R * C : 1}, f32);
+    }
+};
+
+// where the gradients go, in the library's order; NULL: not wanted (features, conic, colors, cov3D, sh, scales, rotations may be)
+struct Dest { float *features, *means2D, *conic, *opacity, *colors, *means3D, *cov3D, *sh, *scales, *rotations; };
+
+// The call of both exports (P != 0): gradients stored (accumulate = 0) or added (1) at `d`.  One library call whatever upstreams there are: NULL / 0
+// where one is absent, and without a feature gradient the library takes this for its depth call (tgs_backward_depth_opt, the name its errors then
+// carry), without that for the alpha call's, without that for today's.  The median's share is a call of its own behind it, added into d.means3D.
+void backward_call(const BackwardFrame& f, const c10::Device& dev, const Upstream& up, const tgs_options_t& opt, int accumulate, const Dest& d)
+{
+    const Arg bg(f.background, dev, "background"), means(f.means3D, dev, "means3D"), col(f.colors, dev, "colors"), sc(f.scales, dev, "scales"),
+        rot(f.rotations, dev, "rotations"), cov(f.cov3D_precomp, dev, "cov3D_precomp"), view(f.viewmatrix, dev, "viewmatrix"), proj(f.projmatrix, dev, "projmatrix"),
+        shs(f.sh, dev, "sh"), cam(f.campos, dev, "campos"), dL(f.dL_dout_color, dev, "dL_dout_color");
+    const torch::Tensor radii_c = f.radii.contiguous();
+    void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+    int r;
+    {
+        py::gil_scoped_release nogil;
+        r = tgs_backward_features_opt(&opt, accumulate, stream, f.P(), f.degree, sh_coeffs(f.sh), f.R, bg.p, f.W(), f.H(), means.p, shs.p, col.p, sc.p, f.scale_modifier, rot.p,
+                                      cov.p, view.p, proj.p, cam.p, f.tan_fovx, f.tan_fovy, radii_c.data_ptr<int>(), f.geomBuffer.data_ptr(), f.binningBuffer.data_ptr(),
+                                      f.imageBuffer.data_ptr(), dL.p, up.dA.p, up.dD.p, up.dD.p ? up.dz.data_ptr<float>() : nullptr, up.C, up.feat.p, up.dF.p,
+                                      up.C ? up.feat_scratch.data_ptr<float>() : nullptr, d.features, d.means2D, d.conic, d.opacity, d.colors, d.means3D, d.cov3D, d.sh,
+                                      d.scales, d.rotations, f.debug);
+        if (r >= 0 && up.dM.p && f.R > 0)
+            r = tgs_backward_median(stream, f.P(), f.W(), f.H(), f.R, f.geomBuffer.data_ptr(), f.binningBuffer.data_ptr(), f.imageBuffer.data_ptr(), view.p,
+                                    radii_c.data_ptr<int>(), up.mpos.data_ptr<int>(), up.dM.p, up.dz.data_ptr<float>(), d.means3D);
+    }
+    if (r < 0) raise_last(r);
+}
+
 // RasterizeGaussiansBackwardCUDA (rasterize_points.cu:117-196); return order of :195.  The library writes every element, so the outputs
 // are torch::empty (the reference needs nine torch::zeros memsets, :151-159).  with_conic (tests) appends the scratch dL_dconic[P,2,2].
 py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
@@ -122,99 +208,89 @@ py::tuple rasterize_gaussians_backward(const torch::Tensor& background, const to
                                        const torch::Tensor& dL_dout_color, const torch::Tensor& sh, int degree, const torch::Tensor& campos,
                                        const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, bool debug,
                                        bool with_conic, int64_t tile_bound, c10::optional<bool> deterministic, int64_t mid_bound, c10::optional<bool> light_tiles,
-                                       bool need_colors, bool need_cov3D, const c10::optional<torch::Tensor>& grad_out_alpha,
-                                       const c10::optional<torch::Tensor>& grad_out_depth, const c10::optional<torch::Tensor>& grad_out_features,
-                                       const c10::optional<torch::Tensor>& features, const c10::optional<torch::Tensor>& grad_out_median,
-                                       const c10::optional<torch::Tensor>& median_pos)
+                                       bool need_colors, bool need_cov3D, const OptTensor& grad_out_alpha, const OptTensor& grad_out_depth,
+                                       const OptTensor& grad_out_features, const OptTensor& features, const OptTensor& grad_out_median, const OptTensor& median_pos)
 {
     // grad_out_median (extension keyword): upstream gradient of the median depth (median_from_state), [1,H,W] or [H,W], with median_pos, the int32 map
     // [1,H,W] that median_from_state returned for this frame; None launches no median kernel, a tensor runs tgs_backward_median behind the main call
     // and adds its share into the returned dL_dmeans3D.  No other gradient gets anything from it.
     // grad_out_features (extension keyword): upstream gradient of the feature map (features_from_state), [C,H,W], with features [P,C]; None launches no
-    // feature kernel and returns today's tuple, a tensor travels with a scratch of R * C floats allocated here, and dL_dfeatures[P,C] is appended to
+    // feature kernel and returns today's tuple, a tensor travels with a scratch of R * C floats (Upstream), and dL_dfeatures[P,C] is appended to
     // the tuple.
     // grad_out_depth (extension keyword): upstream gradient of the expected depth (depth_from_state), [1,H,W] or [H,W]; None launches no depth kernel,
-    // a tensor travels with a scratch of R floats allocated here.
+    // a tensor travels with a scratch of R floats (Upstream).
     // grad_out_alpha (extension keyword): upstream gradient of the accumulated alpha (alpha_from_state), [1,H,W] or [H,W]; None: the colour's alone.
     // need_colors / need_cov3D = false (extension keywords; the reference's signature has neither): the caller will discard dL_dcolors / dL_dcov3D --
     // GaussianRasterizer's backward does when the forward was given shs / scales + rotations (__init__.py:137-152 hands them to inputs that are None) --
     // so they are neither allocated nor written (empty tensors come back); dL_dconic, an intermediate of the reference's two kernels, only on request.
     const c10::Device dev = require_gpu(means3D);
-    const int P = (int)means3D.size(0), H = (int)dL_dout_color.size(1), W = (int)dL_dout_color.size(2), M = sh_coeffs(sh);
+    const int P = (int)means3D.size(0), M = sh_coeffs(sh);
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
-    const Arg sc(scales, dev, "scales"), rot(rotations, dev, "rotations");
-    const bool has_sr = sc.p != nullptr;
+    const bool has_sr = scales.numel() != 0;
     const bool want_col = need_colors || M == 0, want_cov = need_cov3D || !has_sr;      // (required outputs on the colors_precomp / cov3D_precomp paths)
     torch::Tensor dL_dmeans3D = torch::empty({P, 3}, f32), dL_dmeans2D = torch::empty({P, 3}, f32), dL_dcolors = torch::empty({want_col ? P : 0, 3}, f32),
                   dL_dconic = torch::empty({with_conic ? P : 0, 2, 2}, f32), dL_dopacity = torch::empty({P, 1}, f32), dL_dcov3D = torch::empty({want_cov ? P : 0, 6}, f32),
                   dL_dsh = torch::empty({P, M, 3}, f32);
     // the reference leaves these at zero on the cov3D_precomp path
     torch::Tensor dL_dscales = has_sr ? torch::empty({P, 3}, f32) : torch::zeros({P, 3}, f32), dL_drotations = has_sr ? torch::empty({P, 4}, f32) : torch::zeros({P, 4}, f32);
-    const bool with_feat = grad_out_features.has_value() && grad_out_features->defined();
-    int C = 0;
-    torch::Tensor dL_dfeatures;
-    if (with_feat) {
-        if (!features.has_value() || !features->defined() || features->dim() != 2 || features->size(0) != P)
-            throw std::runtime_error("grad_out_features needs features of shape [P,C]");
-        C = (int)features->size(1);
-        if (C < 1 || C > TGS_FEATURE_MAX_CHANNELS) throw std::runtime_error("grad_out_features: features must have 1 .. 16 channels");
-        if (grad_out_features->numel() != (int64_t)C * H * W) throw std::runtime_error("grad_out_features must have C*H*W elements ([C,H,W])");
-        dL_dfeatures = torch::empty({P, C}, f32);
-    }
-    if (P != 0) {
-        const Arg bg(background, dev, "background"), means(means3D, dev, "means3D"), col(colors, dev, "colors"), cov(cov3D_precomp, dev, "cov3D_precomp"),
-            view(viewmatrix, dev, "viewmatrix"), proj(projmatrix, dev, "projmatrix"), shs(sh, dev, "sh"), cam(campos, dev, "campos"),
-            dL(dL_dout_color, dev, "dL_dout_color");
-        const bool with_alpha = grad_out_alpha.has_value() && grad_out_alpha->defined();
-        if (with_alpha && grad_out_alpha->numel() != (int64_t)H * W) throw std::runtime_error("grad_out_alpha must have H*W elements ([1,H,W])");
-        const Arg dA(with_alpha ? *grad_out_alpha : torch::Tensor(), dev, "grad_out_alpha");
-        const bool with_depth = grad_out_depth.has_value() && grad_out_depth->defined();
-        if (with_depth && grad_out_depth->numel() != (int64_t)H * W) throw std::runtime_error("grad_out_depth must have H*W elements ([1,H,W])");
-        const Arg dD(with_depth ? *grad_out_depth : torch::Tensor(), dev, "grad_out_depth");
-        const torch::Tensor dz_scratch = with_depth ? torch::empty({R > 0 ? R : 1}, dL_dmeans3D.options()) : torch::Tensor();
-        const Arg dF(with_feat ? *grad_out_features : torch::Tensor(), dev, "grad_out_features"), feat(with_feat ? *features : torch::Tensor(), dev, "features");
-        const torch::Tensor feat_scratch = with_feat ? torch::empty({R > 0 ? R * C : 1}, dL_dmeans3D.options()) : torch::Tensor();
-        const bool with_median = grad_out_median.has_value() && grad_out_median->defined();
-        torch::Tensor mpos;
-        if (with_median) {
-            if (grad_out_median->numel() != (int64_t)H * W) throw std::runtime_error("grad_out_median must have H*W elements ([1,H,W])");
-            if (!median_pos.has_value() || !median_pos->defined() || median_pos->numel() != (int64_t)H * W || median_pos->scalar_type() != torch::kInt32)
-                throw std::runtime_error("grad_out_median needs median_pos, the int32 map [1,H,W] of median_from_state");
-            mpos = (median_pos->device() == dev ? *median_pos : median_pos->to(dev)).contiguous();
-        }
-        const Arg dM(with_median ? *grad_out_median : torch::Tensor(), dev, "grad_out_median");
-        const torch::Tensor radii_c = radii.contiguous();
-        void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
-        const tgs_options_t opt = make_options(tile_bound, c10::nullopt, deterministic, 0, mid_bound, light_tiles);
-        int r;
-        {
-            py::gil_scoped_release nogil;
-            // one call whatever upstreams there are: NULL / 0 where one is absent, and without a feature gradient the library takes this for its
-            // depth call (tgs_backward_depth_opt, the name its errors then carry), without that for the alpha call's, without that for today's
-            r = tgs_backward_features_opt(&opt, 0, stream, P, degree, M, R, bg.p, W, H, means.p, shs.p, col.p, sc.p, scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p,
-                                          tan_fovx, tan_fovy, radii_c.data_ptr<int>(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), dL.p,
-                                          dA.p, dD.p, with_depth ? dz_scratch.data_ptr<float>() : nullptr,
-                                          C, feat.p, dF.p, with_feat ? feat_scratch.data_ptr<float>() : nullptr, with_feat ? dL_dfeatures.data_ptr<float>() : nullptr,
-                                          dL_dmeans2D.data_ptr<float>(), with_conic ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
-                                          want_col ? dL_dcolors.data_ptr<float>() : nullptr, dL_dmeans3D.data_ptr<float>(), want_cov ? dL_dcov3D.data_ptr<float>() : nullptr,
-                                          M ? dL_dsh.data_ptr<float>() : nullptr,
-                                          has_sr ? dL_dscales.data_ptr<float>() : nullptr, has_sr ? dL_drotations.data_ptr<float>() : nullptr, debug);
-            // the median's share: a call of its own behind the main one, added into dL_dmeans3D (the depth's dz scratch is free again by then:
-            // the same stream)
-            if (r >= 0 && with_median && R > 0) {
-                const torch::Tensor mz = with_depth ? dz_scratch : torch::empty({R}, dL_dmeans3D.options());
-                r = tgs_backward_median(stream, P, W, H, R, geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), view.p, radii_c.data_ptr<int>(),
-                                        mpos.data_ptr<int>(), dM.p, mz.data_ptr<float>(), dL_dmeans3D.data_ptr<float>());
-            }
-        }
-        if (r < 0) raise_last(r);
-    }
+    const BackwardFrame f{background, means3D, radii, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, dL_dout_color, sh, campos, geomBuffer,
+                          binningBuffer, imageBuffer, scale_modifier, tan_fovx, tan_fovy, degree, R, debug};
+    const Upstream up(f, dev, grad_out_alpha, grad_out_depth, grad_out_features, features, grad_out_median, median_pos);
+    torch::Tensor dL_dfeatures = up.C ? torch::empty({P, up.C}, f32) : torch::Tensor();
+    const auto ptr = [](bool wanted, const torch::Tensor& t) { return wanted ? t.data_ptr<float>() : nullptr; };
+    if (P != 0)
+        backward_call(f, dev, up, make_options(tile_bound, c10::nullopt, deterministic, 0, mid_bound, light_tiles), 0,
+                      {ptr(up.C != 0, dL_dfeatures), ptr(true, dL_dmeans2D), ptr(with_conic, dL_dconic), ptr(true, dL_dopacity), ptr(want_col, dL_dcolors),
+                       ptr(true, dL_dmeans3D), ptr(want_cov, dL_dcov3D), ptr(M != 0, dL_dsh), ptr(has_sr, dL_dscales), ptr(has_sr, dL_drotations)});
     py::list out;
     for (const torch::Tensor& g : {dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations}) out.append(g);
     if (with_conic) out.append(dL_dconic);
-    if (with_feat) out.append(dL_dfeatures);
+    if (up.C) out.append(dL_dfeatures);
     return py::tuple(out);
+}
+
+// The accumulating export (multi-view extension; _C.rasterize_gaussians_backward_accumulate forwards to it): the same call with accumulate = 1,
+// the parameter gradients ADDED into the tensors of `into` -- keys means3D, opacities, sh | colors_precomp, scales + rotations | cov3D_precomp,
+// features; a missing key or None is a NULL destination, colors_precomp is not looked at on the SH path nor cov3D_precomp on the scales +
+// rotations path -- and dL_dmeans2D[P,3], the only per-view gradient, returned.  The upstream keywords are rasterize_gaussians_backward's; with
+// grad_out_features, into["features"] ([P,C]) is required.  An empty model returns the empty [0,3] tensor and looks at nothing else.
+torch::Tensor rasterize_gaussians_backward_into(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
+                                                const torch::Tensor& scales, const torch::Tensor& rotations, float scale_modifier, const torch::Tensor& cov3D_precomp,
+                                                const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, float tan_fovx, float tan_fovy,
+                                                const torch::Tensor& dL_dout_color, const torch::Tensor& sh, int degree, const torch::Tensor& campos,
+                                                const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, bool debug,
+                                                const py::dict& into, int64_t tile_bound, c10::optional<bool> deterministic, int64_t mid_bound,
+                                                const OptTensor& grad_out_alpha, const OptTensor& grad_out_depth, const OptTensor& grad_out_features, const OptTensor& features,
+                                                const OptTensor& grad_out_median, const OptTensor& median_pos)
+{
+    const c10::Device dev = require_gpu(means3D);
+    const int P = (int)means3D.size(0), M = sh_coeffs(sh);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
+    torch::Tensor dL_dmeans2D = torch::empty({P, 3}, f32);
+    if (P == 0) return dL_dmeans2D;
+    const BackwardFrame f{background, means3D, radii, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, dL_dout_color, sh, campos, geomBuffer,
+                          binningBuffer, imageBuffer, scale_modifier, tan_fovx, tan_fovy, degree, R, debug};
+    const Upstream up(f, dev, grad_out_alpha, grad_out_depth, grad_out_features, features, grad_out_median, median_pos);
+    std::vector<torch::Tensor> held;                        // (the destinations stay alive while the GIL is released)
+    const auto dst = [&](const char* name, std::initializer_list<int64_t> shape) -> float* {
+        const py::object g = into.attr("get")(name);
+        if (g.is_none()) return nullptr;
+        const torch::Tensor t = g.cast<torch::Tensor>();
+        if (t.scalar_type() != torch::kFloat32 || t.device() != dev || !t.is_contiguous() || t.sizes() != c10::IntArrayRef(shape))
+            throw std::runtime_error(c10::str("accumulation buffer for ", name, " must be a contiguous fp32 tensor of shape ", c10::IntArrayRef(shape), " on ", dev));
+        held.push_back(t);
+        return t.data_ptr<float>();
+    };
+    if (up.C && into.attr("get")("features").is_none()) throw std::runtime_error("grad_out_features: into[\"features\"] ([P,C]) is required");
+    const bool has_sh = M != 0, has_sr = scales.numel() != 0;
+    torch::Tensor dL_dconic = torch::empty({P, 4}, f32);      // (the scratch this call has always handed the library; whether it can go is a measurement of its own)
+    backward_call(f, dev, up, make_options(tile_bound, c10::nullopt, deterministic, 0, mid_bound, c10::nullopt), 1,
+                  {up.C ? dst("features", {P, up.C}) : nullptr, dL_dmeans2D.data_ptr<float>(), dL_dconic.data_ptr<float>(), dst("opacities", {P, 1}),
+                   has_sh ? nullptr : dst("colors_precomp", {P, 3}), dst("means3D", {P, 3}), has_sr ? nullptr : dst("cov3D_precomp", {P, 6}),
+                   has_sh ? dst("sh", {P, M, 3}) : nullptr, has_sr ? dst("scales", {P, 3}) : nullptr, has_sr ? dst("rotations", {P, 4}) : nullptr});
+    return dL_dmeans2D;
 }
 
 // What depth_from_state, median_from_state and features_from_state share: the frame of a finished forward on `dev`, its sizes checked, the
@@ -337,13 +413,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("tan_fovy"), py::arg("image_height"), py::arg("image_width"), py::arg("sh"), py::arg("degree"), py::arg("campos"), py::arg("prefiltered"),
           py::arg("debug"), py::arg("r_capacity") = py::none(), py::arg("r_guess") = py::none(), py::arg("tile_bound") = 0, py::arg("pruning") = py::none(),
           py::arg("sort_lds_cap") = 0, py::arg("info") = false, py::arg("mid_bound") = 0, py::arg("light_tiles") = py::none());
-    m.def("rasterize_gaussians_backward", &rasterize_gaussians_backward, py::arg("background"), py::arg("means3D"), py::arg("radii"), py::arg("colors"),
-          py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"), py::arg("cov3D_precomp"), py::arg("viewmatrix"), py::arg("projmatrix"),
-          py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("dL_dout_color"), py::arg("sh"), py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"),
-          py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"), py::arg("_with_conic") = false, py::arg("tile_bound") = 0,
-          py::arg("deterministic") = py::none(), py::arg("mid_bound") = 0, py::arg("light_tiles") = py::none(), py::arg("need_colors") = true,
-          py::arg("need_cov3D") = true, py::arg("grad_out_alpha") = py::none(), py::arg("grad_out_depth") = py::none(),
-          py::arg("grad_out_features") = py::none(), py::arg("features") = py::none(), py::arg("grad_out_median") = py::none(), py::arg("median_pos") = py::none());
+    // both exports of the one-view backward: the frame arguments, what the export adds (`own`), the upstream keywords
+    const auto def_backward = [&m](const char* name, auto fn, auto... own) {
+        m.def(name, fn, py::arg("background"), py::arg("means3D"), py::arg("radii"), py::arg("colors"), py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"),
+              py::arg("cov3D_precomp"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("dL_dout_color"), py::arg("sh"),
+              py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"), py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"), own...,
+              py::arg("grad_out_alpha") = py::none(), py::arg("grad_out_depth") = py::none(), py::arg("grad_out_features") = py::none(), py::arg("features") = py::none(),
+              py::arg("grad_out_median") = py::none(), py::arg("median_pos") = py::none());
+    };
+    def_backward("rasterize_gaussians_backward", &rasterize_gaussians_backward, py::arg("_with_conic") = false, py::arg("tile_bound") = 0, py::arg("deterministic") = py::none(),
+                 py::arg("mid_bound") = 0, py::arg("light_tiles") = py::none(), py::arg("need_colors") = true, py::arg("need_cov3D") = true);
+    def_backward("rasterize_gaussians_backward_into", &rasterize_gaussians_backward_into, py::arg("into"), py::arg("tile_bound") = 0, py::arg("deterministic") = py::none(),
+                 py::arg("mid_bound") = 0);
     m.def("median_from_state", &median_from_state, py::arg("geomBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("P"), py::arg("H"), py::arg("W"), py::arg("R"));
     m.def("features_from_state", &features_from_state, py::arg("geomBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("features"), py::arg("P"),
           py::arg("H"), py::arg("W"), py::arg("R"));

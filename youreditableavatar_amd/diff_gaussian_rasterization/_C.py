@@ -45,9 +45,6 @@ def _load() -> C.CDLL:
     lib.tgs_frame_status.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(it)]
     lib.tgs_state_sizes.restype = None
     lib.tgs_state_sizes.argtypes = [it, it, it, it, it, C.c_int64, C.POINTER(C.c_size_t)]
-    lib.tgs_backward_opt.restype = it
-    lib.tgs_backward_opt.argtypes = [vp, it, vp, it, it, it, C.c_int64, vp, it, it, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, fl, fl, vp,
-                                     vp, vp, vp, vp] + [vp] * 9 + [it]
     lib.tgs_set_render_streams.restype = it
     lib.tgs_set_render_streams.argtypes = [vp, it]
     lib.tgs_forward_views_opt.restype = it
@@ -78,9 +75,7 @@ def _load() -> C.CDLL:
     lib.tgs_backward_render_views_extras_opt.argtypes = [vp, vp, it, it, it, vp, vp]
     lib.tgs_backward_batch_depth_range.restype = it
     lib.tgs_backward_batch_depth_range.argtypes = [vp, it, it, vp, vp, vp, it, it]
-    lib.tgs_backward_depth_opt.restype = it
-    lib.tgs_backward_depth_opt.argtypes = lib.tgs_backward_opt.argtypes[:27] + [vp, vp, vp] + [vp] * 9 + [it]
-    # feature channels in the whole-batch path (tgs_view_features_t), and the one-view backward that carries them
+    # feature channels in the whole-batch path (tgs_view_features_t)
     lib.tgs_sizeof_view_features.restype = C.c_size_t
     lib.tgs_features_views.restype = it
     lib.tgs_features_views.argtypes = [vp, it, it, it, vp, vp]
@@ -88,8 +83,6 @@ def _load() -> C.CDLL:
     lib.tgs_backward_render_views_features_opt.argtypes = [vp, vp, it, it, it, vp, vp, vp]
     lib.tgs_backward_batch_features_range.restype = it
     lib.tgs_backward_batch_features_range.argtypes = [vp, it, it, vp, vp, vp, it, it, it]
-    lib.tgs_backward_features_opt.restype = it
-    lib.tgs_backward_features_opt.argtypes = lib.tgs_backward_opt.argtypes[:27] + [vp, vp, vp] + [it, vp, vp, vp, vp] + [vp] * 9 + [it]
     # median depth of one view: the map and the call that adds its share behind a backward
     lib.tgs_median.restype = it
     lib.tgs_median.argtypes = [vp, it, it, it, C.c_int64, vp, vp, vp, vp, vp, vp]
@@ -319,82 +312,18 @@ def rasterize_gaussians_backward_accumulate(background, means3D, radii, colors, 
     """Multi-view extension (tgs_backward_accumulate): parameter gradients are ADDED into the fp32 tensors of ``into``
     (keys: means3D, opacities, and sh|colors_precomp, scales+rotations|cov3D_precomp; contiguous, on the device).
     Returns dL_dmeans2D[P,3], the only per-view gradient.  ``grad_out_alpha`` / ``grad_out_depth`` ([1,H,W]): upstream gradients of the
-    frame's accumulated alpha / expected depth as well (what tgs_backward_depth_opt with accumulate = 1 does; the dz scratch of R floats is
-    allocated here); both None: what tgs_backward_opt does, bit for bit.  ``grad_out_features`` ([C,H,W]) with ``features`` ([P,C],
-    float32, 1 <= C <= 16): the upstream gradient of the frame's feature map as well (tgs_backward_features_opt with accumulate = 1; the
-    scratch of R * C floats is allocated here); dL/d features is ADDED into ``into["features"]`` ([P,C]), which is required then.
+    frame's accumulated alpha / expected depth as well (the library's depth call with accumulate = 1; the dz scratch of R floats is
+    allocated by the binding); both None: the plain accumulating call, bit for bit.  ``grad_out_features`` ([C,H,W]) with ``features``
+    ([P,C], float32, 1 <= C <= 16): the upstream gradient of the frame's feature map as well (the library's feature call with accumulate = 1;
+    the scratch of R * C floats is allocated by the binding); dL/d features is ADDED into ``into["features"]`` ([P,C]), which is required then.
     ``grad_out_median`` ([1,H,W]) with ``median_pos`` (the int32 map [1,H,W] of ``median_from_state`` for this frame): the upstream gradient
-    of the frame's median depth as well -- tgs_backward_median behind the main call adds its share into ``into["means3D"]`` (a scratch of R
-    floats is allocated here); no other gradient gets anything from it.  None: today's calls and today's kernels."""
-    dev = _require_gpu(means3D)
-    P = int(means3D.size(0))
-    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
-    M = int(sh.size(1)) if (sh.dim() > 1 and sh.size(0) != 0) else 0
-    with torch.cuda.device(dev):
-        dL_dmeans2D = torch.empty((P, 3), dtype=torch.float32, device=dev)
-        if P == 0:
-            return dL_dmeans2D
-        dL_dconic = torch.empty((P, 4), dtype=torch.float32, device=dev)
-        t = dict(bg=_dev_f32(background, dev, "background"), means=_dev_f32(means3D, dev, "means3D"),
-                 colors=_dev_f32(colors, dev, "colors"), scales=_dev_f32(scales, dev, "scales"),
-                 rots=_dev_f32(rotations, dev, "rotations"), cov=_dev_f32(cov3D_precomp, dev, "cov3D_precomp"),
-                 view=_dev_f32(viewmatrix, dev, "viewmatrix"), proj=_dev_f32(projmatrix, dev, "projmatrix"),
-                 sh=_dev_f32(sh, dev, "sh"), campos=_dev_f32(campos, dev, "campos"), dL=_dev_f32(dL_dout_color, dev, "dL_dout_color"))
-
-        def dst(name, shape):
-            g = into.get(name)
-            if g is None:
-                return None
-            if g.dtype != torch.float32 or g.device != dev or not g.is_contiguous() or tuple(g.shape) != shape:
-                raise RuntimeError(f"accumulation buffer for {name} must be a contiguous fp32 tensor of shape {shape} on {dev}")
-            return g.data_ptr()
-
-        has_sh, has_sr = t["sh"] is not None, t["scales"] is not None
-        opt = options(tile_bound=tile_bound, deterministic=deterministic, mid_bound=mid_bound)
-        for name, g in (("grad_out_alpha", grad_out_alpha), ("grad_out_depth", grad_out_depth)):
-            if g is not None and g.numel() != H * W:
-                raise RuntimeError(f"{name} must have H*W elements ([1,H,W])")
-        dA, dD = _dev_f32(grad_out_alpha, dev, "grad_out_alpha"), _dev_f32(grad_out_depth, dev, "grad_out_depth")
-        dz = torch.empty((max(int(R), 1),), dtype=torch.float32, device=dev) if dD is not None else None
-        Cf, F, dF, fscratch, dL_dfeatures = 0, None, None, None, None
-        if grad_out_features is not None:
-            F = _dev_f32(features, dev, "features")
-            if F is None or F.dim() != 2 or int(F.size(0)) != P or not 1 <= int(F.size(1)) <= FEATURE_MAX_CHANNELS:
-                raise RuntimeError(f"grad_out_features needs features of shape [P,C], 1 <= C <= {FEATURE_MAX_CHANNELS}")
-            Cf = int(F.size(1))
-            if grad_out_features.numel() != Cf * H * W:
-                raise RuntimeError("grad_out_features must have C*H*W elements ([C,H,W])")
-            if into.get("features") is None:
-                raise RuntimeError("grad_out_features: into[\"features\"] ([P,C]) is required")
-            dF = _dev_f32(grad_out_features, dev, "grad_out_features")
-            fscratch = torch.empty((max(int(R), 1) * Cf,), dtype=torch.float32, device=dev)
-            dL_dfeatures = dst("features", (P, Cf))
-        # one call whatever upstreams there are: None where one is absent (the library then launches what the call without it launches)
-        r = _lib.tgs_backward_features_opt(
-            C.byref(opt), 1, torch.cuda.current_stream(dev).cuda_stream, P, int(degree), M, int(R), _p(t["bg"]), W, H, _p(t["means"]), _p(t["sh"]), _p(t["colors"]),
-            _p(t["scales"]), float(scale_modifier), _p(t["rots"]), _p(t["cov"]), _p(t["view"]), _p(t["proj"]), _p(t["campos"]),
-            float(tan_fovx), float(tan_fovy), radii.contiguous().data_ptr(), geomBuffer.data_ptr(), binningBuffer.data_ptr(),
-            imageBuffer.data_ptr(), _p(t["dL"]), _p(dA), _p(dD), _p(dz), Cf, _p(F), _p(dF), _p(fscratch), dL_dfeatures,
-            dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dst("opacities", (P, 1)),
-            None if has_sh else dst("colors_precomp", (P, 3)), dst("means3D", (P, 3)), None if has_sr else dst("cov3D_precomp", (P, 6)),
-            dst("sh", (P, M, 3)) if has_sh else None, dst("scales", (P, 3)) if has_sr else None, dst("rotations", (P, 4)) if has_sr else None,
-            int(bool(debug)))
-        if r < 0:
-            raise _err(int(r))
-        if grad_out_median is not None:
-            if grad_out_median.numel() != H * W:
-                raise RuntimeError("grad_out_median must have H*W elements ([1,H,W])")
-            if median_pos is None or median_pos.numel() != H * W or median_pos.dtype != torch.int32:
-                raise RuntimeError("grad_out_median needs median_pos, the int32 map [1,H,W] of median_from_state")
-            if int(R) > 0:
-                dM, mpos = _dev_f32(grad_out_median, dev, "grad_out_median"), median_pos.to(dev).contiguous()
-                mz = torch.empty((int(R),), dtype=torch.float32, device=dev)
-                r = _lib.tgs_backward_median(torch.cuda.current_stream(dev).cuda_stream, P, W, H, int(R), geomBuffer.data_ptr(), binningBuffer.data_ptr(),
-                                             imageBuffer.data_ptr(), _p(t["view"]), radii.contiguous().data_ptr(), mpos.data_ptr(), _p(dM), mz.data_ptr(),
-                                             dst("means3D", (P, 3)))
-                if r < 0:
-                    raise _err(int(r))
-    return dL_dmeans2D
+    of the frame's median depth as well -- tgs_backward_median behind the main call adds its share into ``into["means3D"]`` (its scratch of R
+    floats is the depth's where there is one); no other gradient gets anything from it.  None: today's calls and today's kernels.
+    A forward to the compiled ``rasterize_gaussians_backward_into``: the implementation ``rasterize_gaussians_backward`` stores through."""
+    return _ext.rasterize_gaussians_backward_into(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+                                                  tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, into,
+                                                  tile_bound, deterministic, mid_bound, grad_out_alpha, grad_out_depth, grad_out_features, features,
+                                                  grad_out_median, median_pos)
 
 
 class _ViewT(C.Structure):
@@ -731,7 +660,9 @@ def state_field(name: str, P: int, width: int, height: int, R: int, has_sh: bool
 
 
 # The reference's three exports (ext.cpp:15-19): the compiled module's functions, positional signatures of rasterize_points.h:18-67
-# (+ the keyword-only extensions r_capacity / r_guess / _with_conic / grad_out_alpha / grad_out_depth / grad_out_features + features / grad_out_median + median_pos documented in csrc/tgs_torch_ext.cpp).
+# (+ the keyword extensions documented in csrc/tgs_torch_ext.cpp: r_capacity / r_guess of the forward; _with_conic, need_colors / need_cov3D and the
+# upstream gradients grad_out_alpha / grad_out_depth / grad_out_features + features / grad_out_median + median_pos of the backward, which
+# rasterize_gaussians_backward_accumulate above hands to the same compiled backward).
 rasterize_gaussians = _ext.rasterize_gaussians
 rasterize_gaussians_backward = _ext.rasterize_gaussians_backward
 mark_visible = _ext.mark_visible

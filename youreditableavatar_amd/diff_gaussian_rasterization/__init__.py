@@ -180,13 +180,14 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
-        return _RasterizeGaussians.native_backward(ctx, grad_out_color, None)
+        return _RasterizeGaussians.native_backward(ctx, grad_out_color)
 
     @staticmethod
-    def native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth=None, grad_out_features=None, features=None, grad_out_median=None, median_pos=None):
-        """grad_out_alpha / grad_out_depth / grad_out_features / grad_out_median None: today's native call, today's kernels; a tensor: the
-        extension keyword of the same call.  With grad_out_features (and the forward's features) the gradient of the features follows the nine
-        of today; grad_out_median travels with the forward's median_pos and adds to the means' gradient alone."""
+    def native_backward(ctx, grad_out_color, **upstream):
+        """``upstream``: the native backward's own extension keywords (grad_out_alpha, grad_out_depth, grad_out_features + features,
+        grad_out_median + median_pos).  One that is None is dropped here -- absent from the native call, not None in it: today's call, today's
+        kernels.  With grad_out_features the gradient of the features follows the nine of today; grad_out_median adds to the means' gradient
+        alone."""
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:                           # the image did not take part in the loss (gradients not materialised, see forward)
@@ -202,20 +203,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         # dL_dcolors / dL_dcov3D go to inputs that were None in the forward (empty tensors here, __init__.py:137-152): autograd drops them, so the
         # native backward neither allocates nor writes them (36 of the ~300 B per Gaussian its per-Gaussian kernel stores; round 6)
         need_col, need_cov = colors_precomp.numel() != 0 or _KEEP_ALL_OUTPUTS, cov3Ds_precomp.numel() != 0 or _KEEP_ALL_OUTPUTS
-        extra = {} if grad_out_alpha is None else {"grad_out_alpha": grad_out_alpha}
-        if grad_out_depth is not None:
-            extra["grad_out_depth"] = grad_out_depth
-        if grad_out_features is not None:
-            extra["grad_out_features"], extra["features"] = grad_out_features, features
-        if grad_out_median is not None:
-            extra["grad_out_median"], extra["median_pos"] = grad_out_median, median_pos
+        extra = {k: v for k, v in upstream.items() if v is not None}
         (g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rots, *g_feat) = _call_native(
             lambda *a: _C.rasterize_gaussians_backward(*a, tile_bound=bound, mid_bound=mid, light_tiles=ctx.light, need_colors=need_col, need_cov3D=need_cov, **extra),
             args, rs.debug, "snapshot_bw.dump", "backward")
         # forward-argument order (__init__.py:143-153)
-        tail = (g_feat[0],) if grad_out_features is not None else ()
         return (g_means3D, g_means2D, g_sh if sh.numel() != 0 else None, g_colors if need_col else None, g_opac, g_scales if scales.numel() != 0 else None,
-                g_rots if rotations.numel() != 0 else None, g_cov3D if need_cov else None, None) + tail
+                g_rots if rotations.numel() != 0 else None, g_cov3D if need_cov else None, None) + tuple(g_feat)
 
 
 class _RasterizeGaussiansExt(torch.autograd.Function):
@@ -237,51 +231,44 @@ class _RasterizeGaussiansExt(torch.autograd.Function):
         rs = raster_settings
         color, radii, img, geom, binning = _RasterizeGaussians.native_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs,
                                                                               with_state=True)
-        H, W, P = int(rs.image_height), int(rs.image_width), int(means3D.shape[0])
-        ctx.want_alpha, ctx.want_depth = bool(want_alpha), bool(want_depth)
+        H, W, P, R = int(rs.image_height), int(rs.image_width), int(means3D.shape[0]), int(ctx.num_rendered)
+        ctx.want_alpha, ctx.want_depth, ctx.want_median, ctx.want_features = bool(want_alpha), bool(want_depth), bool(want_median), features is not None
+        # (an empty model or a frame without instances: depth_, median_ and features_from_state, given P and R, return the fill and launch nothing;
+        # alpha_from_state has the image buffer alone, which an empty model's speculative forward sizes like a frame's and leaves unwritten: filled here)
         out = [color, radii]
         if want_alpha:
-            if P == 0:                                          # (the forward of an empty model writes no image state)
-                out.append(torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device))
-            else:
-                out.append(_C.alpha_from_state(img, H, W))
+            out.append(_C.alpha_from_state(img, H, W) if P else torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device))
         if want_depth:
-            if P == 0:
-                out.append(torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device))
-            else:
-                out.append(_C.depth_from_state(geom, binning, img, P, H, W, int(ctx.num_rendered)))
-        ctx.want_median = bool(want_median)
+            out.append(_C.depth_from_state(geom, binning, img, P, H, W, R))
         if want_median:
-            if P == 0:                                          # zeros and -1 without a native call
-                md, mi, ctx.median_pos = torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device), torch.full((1, H, W), -1, dtype=torch.int32, device=means3D.device), None
-            else:
-                md, mi, ctx.median_pos = _C.median_from_state(geom, binning, img, P, H, W, int(ctx.num_rendered))      # (median_pos: kept for the backward)
+            md, mi, ctx.median_pos = _C.median_from_state(geom, binning, img, P, H, W, R)      # (median_pos: kept for the backward)
             ctx.mark_non_differentiable(radii, mi)
             out += [md, mi]
-        ctx.want_features = features is not None
         if features is not None:
             ctx.features = features                             # (an input: held as save_for_backward holds the others, without a second call of it)
-            if P == 0:
-                out.append(torch.zeros((int(features.shape[1]), H, W), dtype=torch.float32, device=means3D.device))
-            else:
-                out.append(_C.features_from_state(geom, binning, img, features, P, H, W, int(ctx.num_rendered)))
+            out.append(_C.features_from_state(geom, binning, img, features, P, H, W, R))
         return tuple(out)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, *extra):
-        extra = list(extra)
-        grad_out_alpha = extra.pop(0) if ctx.want_alpha else None
-        grad_out_depth = extra.pop(0) if ctx.want_depth else None
-        med = {}
+        # the extra outputs' gradients under the native backward's keywords, in the forward's order (plain statements: a table of names cost 1.4 us per step)
+        extra, up = iter(extra), {}
+        if ctx.want_alpha:
+            up["grad_out_alpha"] = next(extra)
+        if ctx.want_depth:
+            up["grad_out_depth"] = next(extra)
+        # (median_pos and the features go only with a gradient: of a map the loss did not use nothing reaches the native call, no kernel of it runs)
         if ctx.want_median:
-            grad_out_median, _grad_index = extra.pop(0), extra.pop(0)
-            # a median depth the loss did not use, or an empty model: no median kernel runs
-            if grad_out_median is not None and ctx.median_pos is not None:
-                med = dict(grad_out_median=grad_out_median, median_pos=ctx.median_pos)
-        grad_out_features = extra.pop(0) if ctx.want_features else None
-        if grad_out_features is None:                       # no feature map, or one the loss did not use: no feature kernel runs
-            return _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth, **med) + (None, None, None, None)
-        g = _RasterizeGaussians.native_backward(ctx, grad_out_color, grad_out_alpha, grad_out_depth, grad_out_features, ctx.features, **med)
+            up["grad_out_median"], _grad_index = next(extra), next(extra)
+            if up["grad_out_median"] is not None:
+                up["median_pos"] = ctx.median_pos
+        if ctx.want_features:
+            up["grad_out_features"] = next(extra)
+            if up["grad_out_features"] is not None:
+                up["features"] = ctx.features
+        g = _RasterizeGaussians.native_backward(ctx, grad_out_color, **up)
+        if "features" not in up:                            # (no feature gradient: the nine of today, nothing appended)
+            return g + (None, None, None, None)
         return g[:-1] + (None, None, g[-1] if ctx.needs_input_grad[11] else None, None)
 
 
