@@ -560,6 +560,54 @@ int tgs_mesh_antialias(void* stream, int V, int F, int C, const float* pos, cons
                        int width, int height, const float* rast, const float* color, float* out,
                        void* workspace, size_t workspace_bytes);
 
+/* ---- mesh rasterizer: gradients ----
+ * The backward of the three calls above, for the geometry stage, which trains through them (tetgs_spatial/utils/rasterize.py;
+ * models/renderers/part_nvdiff_rasterizer.py :101-198, models/geometry/implicit_sdf.py :266-317).  One image per call; pos, tri, topo, rast and
+ * color are what the forward call took and wrote.  Every output is optional in the sense of the conventions above: pass NULL for a gradient
+ * that is not wanted and nothing is launched for it.  Outputs are stored, not accumulated: every element is defined, with exact zeros for
+ * rows nothing reaches.  Not here: rast_db, a gradient on z/w, near-plane clipping.
+ * The rules:
+ *   interpolate  for a pixel with ID in [1, F], vertex indices in [0, V) and upstream row g[C]: vertex 0's row of dL_dattr[V,C] receives u g,
+ *                vertex 1's v g, vertex 2's (1 - u - v) g; every other pixel contributes nothing.  dL_drast[n_pixels,4]: channel 0 gets
+ *                sum_c g_c (a0_c - a2_c), channel 1 sum_c g_c (a1_c - a2_c), channels 2 and 3 exact zeros (and all four where the pixel
+ *                contributes nothing).
+ *   rasterize    dL_dpos[V,4] from channels 0 and 1 of dL_drast[height*width*4]; what arrives on z/w and on the ID channel is ignored.
+ *                It is the derivative of the expressions that define u, v with respect to x, y, w of the winning triangle's three vertices:
+ *                screen positions from x/w, y/w; screen barycentrics b_k; q_k = b_k / w_k; u = q0/d, v = q1/d with d = q0 + q1 + q2; clamp to
+ *                [0, 1]; division by max(u + v, 1).  clamp and max have the derivative 1 inside and at the bounds, 0 outside.  The z column
+ *                gets exact zeros.  The triangle is recomputed from the pixel's ID and the unsnapped pos; coverage is not decided again.
+ *   antialias, color  out is linear in color with the forward's pair records as weights, so dL_dcolor[height*width*C] is a gather over the
+ *                pixel and its up to four pairs, in the forward's fixed order (left, right, below, above): per pair, with receiver R, other
+ *                pixel O and weight |a|, row R gets -|a| g[R] and row O gets +|a| g[R].  One writer per element, no atomics.
+ *   antialias, pos    every integer decision (which face, exit edge, silhouette or not, receiver) is the forward's, on the snapped coordinates,
+ *                and is held fixed.  The blend weight is differentiated through t~ = E(P) / (-D) evaluated on the real-valued screen
+ *                coordinates X = (x/w 0.5 + 0.5) width 256, Y likewise: the derivative of snapping is taken as 1.  Only the exit edge's two
+ *                vertices a, b get a gradient, in x, y, w.  The scalar reaching t~ is +- sum_c g[R,c] (color[O,c] - color[R,c]) with the
+ *                sign of a, times pos_gradient_boost.  A pair that contributes nothing forward contributes nothing backward.
+ * The scatters into the [V,C] and [V,4] rows use fixed point with one exponent per call, and no float atomics on gradient memory:
+ *   bound        B >= max |contribution| is found on the device and never read back (the largest |g| for dL_dattr, whose three weights lie in
+ *                [0, 1]; a measuring pass for the two pos gradients), reduced with an integer atomicMax on the float's bits;
+ *   accumulate   with 2^(e-1) <= B < 2^e a contribution c is converted to llrint(c 2^(34 - e)): below 2^34 in magnitude, so 2^28
+ *                contributions cannot overflow 63 bits.  Lanes of a wave are pre-reduced in integers over runs of equal destination, and each
+ *                run is added with one no-return 64-bit integer atomic per element;
+ *   convert      a last pass converts the accumulators to fp32 (one rounding).
+ * Integer sums commute: two runs give the same bits, and the result does not depend on the order in which pixels were processed.
+ * Resolution: fixed-point rounding adds at most n 2^(e-35) <= n B 2^-34 to an element that n contributions reach (0.5 unit per contribution),
+ * in front of the one rounding to fp32; the contributions themselves are evaluated in double from the fp32 inputs.
+ * Non-finite bound: if a contribution is a NaN or an infinity, every element of that gradient is NaN (loud, not partial); the per-pixel
+ * outputs (dL_drast, dL_dcolor) are NaN where their own arithmetic makes them.
+ * workspace: device scratch of tgs_mesh_grad_workspace_bytes(V, C, n_pixels) bytes (C = 4 for tgs_mesh_rasterize_backward, n_pixels = width *
+ * height; 0 for sizes that are refused: V < 0, C < 1, n_pixels outside [0, 8192^2]); the calls allocate nothing and synchronise nothing.
+ * F == 0 or V == 0: the gradients are zeros, and dL_dcolor is a copy of dL_dout.  dL_dcolor may not alias dL_dout. */
+size_t tgs_mesh_grad_workspace_bytes(int V, int C, int64_t n_pixels);
+int tgs_mesh_interpolate_backward(void* stream, int V, int F, int C, const float* attr, const int32_t* tri, int64_t n_pixels, const float* rast,
+                                  const float* dL_dout, float* dL_dattr, float* dL_drast, void* workspace, size_t workspace_bytes);
+int tgs_mesh_rasterize_backward(void* stream, int V, int F, const float* pos, const int32_t* tri, int width, int height, const float* rast,
+                                const float* dL_drast, float* dL_dpos, void* workspace, size_t workspace_bytes);
+int tgs_mesh_antialias_backward(void* stream, int V, int F, int C, const float* pos, const int32_t* tri, const int32_t* topo, int width, int height,
+                                const float* rast, const float* color, const float* dL_dout, float* dL_dcolor, float* dL_dpos,
+                                float pos_gradient_boost, void* workspace, size_t workspace_bytes);
+
 /* ---- Batched backward (multi-view steps) ----
  * Rasterizer::backward runs its per-Gaussian half (computeCov2DCUDA + preprocessCUDA of backward.cu) once per view; with
  * in-place accumulation that is 192 B of SH read plus 192 B of dL_dsh read AND written per Gaussian per view.  A batch

@@ -19,12 +19,11 @@
 // unordered vertex pair: integer CAS for the key, add for the count, min / max of the edge number 3 t + k), k_topo_resolve (count 1: -1,
 // count 2: the opposite vertex of the other edge, which is the min or the max, more: -2).  Count, min and max do not depend on the order the
 // lanes arrive in; the slot a key lands in does, but no output reads it.
-#include "tgs_mesh_snap.hpp"
+#include "tgs_mesh_aa_pair.hpp"
 
 namespace tgs {
 
 constexpr unsigned long long TOPO_EMPTY = ~0ull;       // no key: lo < hi < 2^31 never gives all ones
-constexpr int TOPO_NONE = -1, TOPO_MANY = -2;
 
 struct TopoWork {
     unsigned long long* keys;             // [cap] (lo << 32 | hi) of the edge's vertex pair
@@ -122,72 +121,13 @@ __global__ __launch_bounds__(256) void k_topo_resolve(int V, int F, const int* _
 }
 
 // ---- antialias ------------------------------------------------------------------------------------------------------------------------
-// the ID of a pixel: rast.w truncated; 0 (no triangle) for anything that is not a number of at most 2^24 in magnitude
-__device__ __forceinline__ int aa_id(float w) { return fabsf(w) <= 16777216.0f ? (int)w : 0; }
-
-struct AaVertex { int X, Y; bool ok; };
-__device__ __forceinline__ AaVertex aa_vertex(const float4* __restrict__ pos, int i, int W, int H)
-{
-    AaVertex v = {0, 0, false};
-    float sx, sy;
-    v.ok = mesh_snap(pos[i], W, H, sx, sy, v.X, v.Y);
-    return v;
-}
-
-// The whole decision of one pair.  (i, j) is the pair's first pixel, (i + di, j + dj) its second, (di, dj) = (1, 0) or (0, 1); r1, r2 are
-// (z/w, ID) of the two.  -> the record: +|a| the second pixel receives |a| (color[first] - color[second]), -|a| the first receives
-// |a| (color[second] - color[first]), 0 nothing.
+// The whole decision of one pair is aa_pair_full (tgs_mesh_aa_pair.hpp: the backward of tgs_mesh_grad.hip replays it); the forward keeps its
+// record: +|a| the second pixel receives |a| (color[first] - color[second]), -|a| the first receives |a| (color[second] - color[first]),
+// 0 nothing.
 __device__ __forceinline__ float aa_pair(int V, int F, const float4* __restrict__ pos, const int* __restrict__ tri, const int* __restrict__ topo,
                                          int W, int H, int i, int j, int di, int dj, float2 r1, float2 r2)
 {
-#pragma clang fp contract(off)
-    const int id1 = aa_id(r1.y), id2 = aa_id(r2.y);
-    if (id1 == id2) return 0.f;
-    // T: the only one with an ID, else the smaller z/w, else (equal or unordered) the lower ID
-    const bool first = (id1 != 0 && id2 != 0) ? (r1.x < r2.x || (!(r2.x < r1.x) && id1 < id2)) : id1 != 0;
-    const int id = first ? id1 : id2;
-    if (id < 1 || id > F) return 0.f;
-    const size_t T = (size_t)(id - 1);
-    const int idx[3] = {tri[3 * T], tri[3 * T + 1], tri[3 * T + 2]};
-    if ((unsigned)idx[0] >= (unsigned)V || (unsigned)idx[1] >= (unsigned)V || (unsigned)idx[2] >= (unsigned)V) return 0.f;
-    const AaVertex v[3] = {aa_vertex(pos, idx[0], W, H), aa_vertex(pos, idx[1], W, H), aa_vertex(pos, idx[2], W, H)};
-    if (!v[0].ok || !v[1].ok || !v[2].ok) return 0.f;
-    // every factor below is a difference of two coordinates of magnitude <= 2^29 (or a pixel centre, < 2^22): it fits an int, and a product
-    // is one 32 x 32 -> 64-bit multiply-add; the sign s is applied by negation.
-    const long long A = (long long)(v[1].X - v[0].X) * (v[2].Y - v[0].Y) - (long long)(v[2].X - v[0].X) * (v[1].Y - v[0].Y);
-    if (A == 0) return 0.f;
-    const bool ccw = A > 0;                                                       // s = +1
-    // P shows T, Q is the other pixel; u = Q - P in snapped units
-    const int pi = first ? i : i + di, pj = first ? j : j + dj;
-    const int Px = 256 * pi + 128, Py = 256 * pj + 128;
-    const int ux = (first ? 256 : -256) * di, uy = (first ? 256 : -256) * dj;
-    int kexit = -1, dXe = 0, dYe = 0;
-    long long Ee = 0, De = 0;
-#pragma unroll
-    for (int k = 2; k >= 0; k--) {                                                // descending: the FIRST qualifying k is what remains
-        const AaVertex a = v[k], b = v[(k + 1) % 3];
-        const int dX = b.X - a.X, dY = b.Y - a.Y;
-        const long long Du = (long long)dX * uy - (long long)dY * ux, Eu = (long long)dX * (Py - a.Y) - (long long)dY * (Px - a.X);
-        const long long D = ccw ? Du : -Du, E = ccw ? Eu : -Eu;
-        const bool extent = dj == 0 ? (min(a.Y, b.Y) <= Py && Py <= max(a.Y, b.Y)) : (min(a.X, b.X) <= Px && Px <= max(a.X, b.X));
-        if (D < 0 && E >= 0 && E <= -D && extent) { kexit = k; Ee = E; De = D; dXe = dX; dYe = dY; }
-    }
-    if (kexit < 0) return 0.f;
-    const int o = topo[3 * T + kexit];
-    if (o >= 0) {                                                                 // one neighbour: a silhouette only if it folds to T's side
-        if (o >= V) return 0.f;
-        const AaVertex vo = aa_vertex(pos, o, W, H);
-        if (!vo.ok) return 0.f;
-        const AaVertex a = v[kexit];
-        const long long Eo = (long long)dXe * (vo.Y - a.Y) - (long long)dYe * (vo.X - a.X);
-        if ((ccw ? Eo : -Eo) < 0) return 0.f;
-    } else if (o != TOPO_NONE && o != TOPO_MANY) return 0.f;
-    const float t = (float)((double)Ee / (double)(-De));
-    const float a = t - 0.5f;
-    if (a == 0.f) return 0.f;
-    // a > 0: Q receives; a < 0: P receives.  The record is positive when the receiver is the pair's second pixel.
-    const bool second_receives = (a > 0.f) == first;
-    return second_receives ? fabsf(a) : -fabsf(a);
+    return aa_pair_full(V, F, pos, tri, topo, W, H, i, j, di, dj, r1, r2).rec;
 }
 
 __global__ __launch_bounds__(256) void k_aa_pairs(int V, int F, const float4* __restrict__ pos, const int* __restrict__ tri, const int* __restrict__ topo,

@@ -6,7 +6,7 @@ rasterizer's calling convention, forward only, on ``tgs_mesh_rasterize`` / ``tgs
 written down in include/tgs_raster.h).  HIP device only.
 
 Not here: ``antialias`` (INTEGRATION.md 4j gives the edit per call site), gradients, ``rast_db`` (the second result is ``None``), ranged mode and
-near-plane clipping.  An input that requires a gradient is refused, not detached.
+near-plane clipping.  An input that requires a gradient is refused, not detached.  The same calls with gradients are in ``mesh_raster_grad``.
 """
 from __future__ import annotations
 

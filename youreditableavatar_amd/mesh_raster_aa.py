@@ -6,7 +6,8 @@ without call-site edits.
 ``antialias_construct_topology_hash``, on ``tgs_mesh_antialias`` / ``tgs_mesh_topology`` (csrc/tgs_mesh_aa.hip; the rule is written down in
 include/tgs_raster.h, "mesh rasterizer: antialias").  HIP device only, forward only: an input that requires a gradient is refused, not detached.
 
-Not here: gradients (``pos_gradient_boost`` is accepted and ignored), ``rast_db``, near-plane clipping.
+Not here: gradients (``pos_gradient_boost`` is accepted and ignored), ``rast_db``, near-plane clipping.  The same calls with gradients are in
+``mesh_raster_grad``.
 """
 from __future__ import annotations
 
