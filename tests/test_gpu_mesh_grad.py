@@ -368,6 +368,70 @@ def test_nothing_is_launched_for_an_input_without_a_gradient():
         assert np.array_equal(_np(c.grad), both_color) if want_color else np.array_equal(_np(p.grad), both_pos)
 
 
+@pytest.mark.parametrize("folded,n_pairs,n_covered", [(False, 28, (48, 24)), (True, 32, (27, 3))])
+def test_the_two_id_rules_stay_two(folded, n_pairs, n_covered):
+    """An ID of F + 0.5: antialias truncates it and still sees triangle F (aa_id), interpolate sees nothing (mesh_pixel_triangle); forward and
+    backward of both.  The counts are the restatements' own, so that nothing here passes vacuously."""
+    dr, C = _dr(), 3
+    pos, tri, rast = A.quad_case(folded)
+    H, W, F, V = rast.shape[0], rast.shape[1], len(tri), len(pos)
+    hit = rast[..., 3] == F
+    half = rast.copy()
+    half[hit, 3] = F + 0.5
+    rng = np.random.default_rng(11 + folded)
+    color, attr, g = (rng.uniform(-1.0, 1.0, s).astype(np.float32) for s in ((H, W, C), (V, C), (H, W, C)))
+    topo = A.topology(tri, V)
+    assert int(hit.sum()) == 24 and len(G.aa_pairs(rast, pos, tri, topo)["R"]) == len(G.aa_pairs(half, pos, tri, topo)["R"]) == n_pairs
+    assert (len(G.covered(rast, tri, V)[0]), len(G.covered(half, tri, V)[0])) == n_covered
+
+    def both(r):
+        c, p, a, rd = _dev(color, True), _dev(pos, True), _dev(attr, True), _dev(r, True)
+        out = dr.antialias(c[None], _dev(r)[None], p, _dev(tri))
+        out.backward(_dev(g)[None])
+        val, _ = dr.interpolate(a, rd[None], _dev(tri))
+        val.backward(_dev(g)[None])
+        return [_np(t) for t in (out[0], c.grad, p.grad, val[0], a.grad, rd.grad)]
+    (aa0, dc0, dp0, val0, _, _), (aa1, dc1, dp1, val1, d_attr, d_rast) = both(rast), both(half)
+    for got, want in ((aa1, aa0), (dc1, dc0), (dp1, dp0)):                    # antialias: the bits of the unmodified rast
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.abs(dp0).max() > 0 and not np.array_equal(aa0, color)
+    assert not val1[hit].any() and np.array_equal(val1[~hit].view(np.uint32), val0[~hit].view(np.uint32)) and val0[hit].any()
+    assert not d_rast[hit].any()
+    r64, r32 = (G.interpolate_grads(f, attr, half, tri, g) for f in (F64, F32))
+    G.check_bars(f"quad folded={folded} ID F + 0.5 interpolate dL_dattr", d_attr, r64["d_attr"], r32["d_attr"], G.fixed_point_term(r64["B"], r64["n"]))
+
+
+def test_a_parameter_goes_where_a_tensor_goes():
+    """pos [V,4] and attr [V,C] as torch.nn.Parameter, the usual leaf of a mesh fit: trainable through the three calls, frozen through the
+    forward-only modules.  Outputs and gradients have the bits of the plain-tensor calls."""
+    import youreditableavatar_amd.mesh_raster_aa as fwd
+    name, C = "flaps_64x48", 3
+    s, dr = G.scene(name), _dr()
+    H, W, tri = s["H"], s["W"], _dev(s["tri"])
+    g4, g = _dev(G.upstream(name, (1, H, W, 4), "par4")), _dev(G.upstream(name, (1, H, W, C), "par"))
+    color = _dev(A.colors(name, C))[None]
+    bits = lambda t: t.detach().view(torch.int32)
+
+    def run(leaf):
+        p, a = leaf(_dev(s["pos"])), leaf(_dev(attrs(name, C)))
+        rast, _ = dr.rasterize(None, p, tri, (H, W))
+        rast.backward(g4)
+        d_pos_rast, p.grad = p.grad, None
+        out, _ = dr.interpolate(a, rast.detach(), tri)
+        out.backward(g)
+        aa = dr.antialias(color, rast.detach(), p, tri)
+        aa.backward(g)
+        return rast, d_pos_rast, out, a.grad, aa, p.grad
+    plain, param = run(lambda t: t.requires_grad_(True)), run(torch.nn.Parameter)
+    for x, y in zip(plain, param):
+        assert torch.equal(bits(x), bits(y))
+    assert plain[1].any() and plain[3].any() and plain[5].any()
+    pos_f, attr_f = (torch.nn.Parameter(_dev(a), requires_grad=False) for a in (s["pos"], attrs(name, C)))
+    rast, _ = fwd.rasterize(None, pos_f, tri, (H, W))
+    assert torch.equal(bits(rast), bits(plain[0])) and torch.equal(bits(fwd.interpolate(attr_f, rast, tri)[0]), bits(plain[2]))
+    assert torch.equal(bits(fwd.antialias(color, rast, pos_f, tri)), bits(plain[4]))
+
+
 # ---- the chain and the example ---------------------------------------------------------------------------------------------------------
 def _chain(pos, vn, uv, vid, pix, pr, HW, g_n, g_o):
     """rasterize -> interpolate -> normalize / lerp -> antialias -> loss, in torch, on given decisions (pos, vn: leaves of any dtype)"""

@@ -22,17 +22,9 @@ def lib_path():
 
 
 def _lib():
-    lib = ctypes.CDLL(lib_path())
-    vp, it, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+    from youreditableavatar_amd import _mesh
+    lib = _mesh.declare(ctypes.CDLL(lib_path()))            # its own handle, the package's signature table
     lib.tgs_last_error.restype = ctypes.c_char_p
-    lib.tgs_mesh_topology_workspace_bytes.restype = sz
-    lib.tgs_mesh_topology_workspace_bytes.argtypes = [it]
-    lib.tgs_mesh_topology.restype = it
-    lib.tgs_mesh_topology.argtypes = [vp, it, it, vp, vp, vp, sz]
-    lib.tgs_mesh_antialias_workspace_bytes.restype = sz
-    lib.tgs_mesh_antialias_workspace_bytes.argtypes = [it, it]
-    lib.tgs_mesh_antialias.restype = it
-    lib.tgs_mesh_antialias.argtypes = [vp, it, it, it, vp, vp, vp, it, it, vp, vp, vp, vp, sz]
     return lib
 
 

@@ -22,17 +22,9 @@ def lib_path():
 
 
 def _lib():
-    lib = ctypes.CDLL(lib_path())
-    vp, it, sz, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int64
+    from youreditableavatar_amd import _mesh
+    lib = _mesh.declare(ctypes.CDLL(lib_path()))            # its own handle, the package's signature table
     lib.tgs_last_error.restype = ctypes.c_char_p
-    lib.tgs_mesh_grad_workspace_bytes.restype = sz
-    lib.tgs_mesh_grad_workspace_bytes.argtypes = [it, it, i64]
-    lib.tgs_mesh_interpolate_backward.restype = it
-    lib.tgs_mesh_interpolate_backward.argtypes = [vp, it, it, it, vp, vp, i64, vp, vp, vp, vp, vp, sz]
-    lib.tgs_mesh_rasterize_backward.restype = it
-    lib.tgs_mesh_rasterize_backward.argtypes = [vp, it, it, vp, vp, it, it, vp, vp, vp, vp, sz]
-    lib.tgs_mesh_antialias_backward.restype = it
-    lib.tgs_mesh_antialias_backward.argtypes = [vp, it, it, it, vp, vp, vp, it, it, vp, vp, vp, vp, vp, ctypes.c_float, vp, sz]
     return lib
 
 

@@ -21,15 +21,9 @@ def lib_path():
 
 
 def _lib():
-    lib = ctypes.CDLL(lib_path())
-    vp, it, i64, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
+    from youreditableavatar_amd import _mesh
+    lib = _mesh.declare(ctypes.CDLL(lib_path()))            # its own handle, the package's signature table
     lib.tgs_last_error.restype = ctypes.c_char_p
-    lib.tgs_mesh_workspace_bytes.restype = sz
-    lib.tgs_mesh_workspace_bytes.argtypes = [it, it, it]
-    lib.tgs_mesh_rasterize.restype = it
-    lib.tgs_mesh_rasterize.argtypes = [vp, it, it, vp, vp, it, it, vp, vp, sz]
-    lib.tgs_mesh_interpolate.restype = it
-    lib.tgs_mesh_interpolate.argtypes = [vp, it, it, it, vp, vp, i64, vp, vp]
     return lib
 
 
@@ -50,6 +44,29 @@ def test_header_declares_and_library_exports_the_mesh_entry_points():
     assert set(NEW) <= exported, sorted(set(NEW) - exported)
     from youreditableavatar_amd import build
     assert "tgs_mesh.hip" in build.SOURCES
+
+
+def test_the_signature_table_agrees_with_the_header():
+    """every tgs_mesh_* prototype of the header, comments stripped: its return type and each parameter, in order, are the ctypes kinds of
+    youreditableavatar_amd._mesh.SIGNATURES (any pointer a c_void_p), and the table names nothing the header lacks"""
+    from youreditableavatar_amd import _mesh
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float}
+
+    def kind(decl):
+        decl = decl.strip()
+        if "*" in decl:
+            return ctypes.c_void_p
+        words = [w for w in decl.split() if w != "const"]
+        return kinds[words[0]]                                     # (the type; a parameter's name follows it)
+    protos = re.findall(r"([A-Za-z_0-9]+[\s\*]+)(tgs_mesh_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src)
+    declared = {name: (kind(ret), [kind(p) for p in params.split(",")]) for ret, name, params in protos}
+    assert len(protos) == len(declared) == 11, sorted(declared)
+    assert set(_mesh.SIGNATURES) == set(declared), set(_mesh.SIGNATURES) ^ set(declared)
+    for name, (restype, argtypes) in declared.items():
+        assert _mesh.SIGNATURES[name][0] is restype, name
+        assert list(_mesh.SIGNATURES[name][1]) == argtypes, (name, _mesh.SIGNATURES[name][1], argtypes)
 
 
 def test_workspace_size():

@@ -1,0 +1,205 @@
+"""The host layer under ``mesh_raster``, ``mesh_raster_aa`` and ``mesh_raster_grad`` (private: those three are what callers import).
+
+Written once here: the ctypes signatures of the eleven ``tgs_mesh_*`` entry points (``SIGNATURES``, ``declare``); the argument checks of the four calls
+(``rasterize``, ``interpolate``, ``antialias``, ``topology``: types, shapes and dtypes, then ``tri``, the gradient refusal, resolution or extent, the device
+last), each returning the ``Call`` record forward and backward work from; the broadcast rule (``image_of``); N images through one native function
+(``run_images``); where a topology comes from (``topology_of``); the order of ``sum_images``.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+import functools
+from collections import namedtuple
+from typing import Callable, Optional, Sequence
+
+import torch
+
+from .diff_gaussian_rasterization import _C as _rast_c
+
+MAX_FACES = (1 << 24) - 1          # the triangle ID travels in a float
+MAX_RESOLUTION = 8192
+
+_P, _I, _L, _Z, _F = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
+SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_raster.h declares them (every pointer is a c_void_p)
+    "tgs_mesh_workspace_bytes": (_Z, [_I, _I, _I]),
+    "tgs_mesh_rasterize": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _Z]),
+    "tgs_mesh_interpolate": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P]),
+    "tgs_mesh_topology_workspace_bytes": (_Z, [_I]),
+    "tgs_mesh_topology": (_I, [_P, _I, _I, _P, _P, _P, _Z]),
+    "tgs_mesh_antialias_workspace_bytes": (_Z, [_I, _I]),
+    "tgs_mesh_antialias": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _Z]),
+    "tgs_mesh_grad_workspace_bytes": (_Z, [_I, _I, _L]),
+    "tgs_mesh_interpolate_backward": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P, _P, _P, _P, _Z]),
+    "tgs_mesh_rasterize_backward": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _Z]),
+    "tgs_mesh_antialias_backward": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _F, _P, _Z]),
+}
+
+
+def declare(lib: C.CDLL) -> C.CDLL:
+    """applies ``SIGNATURES`` to a handle of the native library -> the handle"""
+    for name, (restype, argtypes) in SIGNATURES.items():
+        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
+    return lib
+
+
+_lib = declare(_rast_c._lib)                                                    # once: the three modules work on this handle
+# torch.cuda.current_stream(dev).cuda_stream builds a Stream object per call (1.9 us of a 17 us call); torch has the number itself, under a private name
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (
+    lambda index: torch.cuda.current_stream(index).cuda_stream)                # (the public way, should the private name go)
+
+
+# A checked call: N images of H x W pixels, V vertices, C channels, F faces, on dev; per_image: attr / pos has a row per image (its gradient is stacked, not summed)
+Call = namedtuple("Call", "N H W V C F dev per_image", defaults=(False,))
+_NO_GUARD = contextlib.nullcontext()
+
+
+def _refuse_grad(name: str, t: torch.Tensor) -> None:
+    if t.requires_grad:
+        raise RuntimeError(f"youreditableavatar_amd.mesh_raster is forward only: `{name}` requires a gradient and none would flow (pass {name}.detach() if that is intended)")
+
+
+def _need_device(**tensors) -> torch.device:
+    """checked last, behind everything that can be said about the arguments without a device -> the first tensor's device"""
+    for name, t in tensors.items():
+        if not t.is_cuda:
+            raise RuntimeError(f"youreditableavatar_amd.mesh_raster has no CPU path: {name} must be on a HIP device")
+    devs = {t.device for t in tensors.values()}
+    if len(devs) != 1:
+        raise RuntimeError("all tensors must be on one device, got " + ", ".join(f"{n} on {t.device}" for n, t in tensors.items()))
+    return next(iter(tensors.values())).device
+
+
+def _check_tri(tri: torch.Tensor) -> None:
+    if not isinstance(tri, torch.Tensor):
+        raise RuntimeError("tri must be a tensor")
+    if tri.dtype != torch.int32 or tri.dim() != 2 or tri.shape[1] != 3:
+        raise RuntimeError(f"expected int32 tri of shape [F,3], got {tri.dtype} {tuple(tri.shape)}")
+    if tri.shape[0] > MAX_FACES:
+        raise RuntimeError(f"tri has {tri.shape[0]} faces; at most 2^24 - 1 = {MAX_FACES} (the triangle ID is carried in a float)")
+
+
+def _check_rast(rast: torch.Tensor):
+    if rast.dtype != torch.float32 or rast.dim() != 4 or rast.shape[-1] != 4:
+        raise RuntimeError(f"expected float32 rast of shape [N,H,W,4], got {rast.dtype} {tuple(rast.shape)}")
+    return (int(x) for x in rast.shape[:3])
+
+
+def rasterize(pos: torch.Tensor, tri: torch.Tensor, resolution: Sequence[int], validate: bool) -> Call:
+    if not isinstance(pos, torch.Tensor):
+        raise RuntimeError("pos must be a tensor")
+    if pos.dtype != torch.float32 or pos.dim() not in (2, 3) or pos.shape[-1] != 4:
+        raise RuntimeError(f"expected float32 pos of shape [N,V,4] or [V,4], got {pos.dtype} {tuple(pos.shape)}")
+    _check_tri(tri)
+    _refuse_grad("pos", pos)
+    H, W = (int(resolution[0]), int(resolution[1])) if len(resolution) == 2 else (0, 0)
+    if not (0 < H <= MAX_RESOLUTION and 0 < W <= MAX_RESOLUTION):
+        raise RuntimeError(f"resolution must be (H, W) with 1 <= H, W <= {MAX_RESOLUTION}, got {tuple(resolution)}")
+    N, V, F = int(pos.shape[0]) if pos.dim() == 3 else 1, int(pos.shape[-2]), int(tri.shape[0])
+    if validate and F:
+        lo, hi = (int(x) for x in torch.aminmax(tri))
+        if lo < 0 or hi >= V:
+            raise ValueError(f"tri holds vertex indices in [{lo}, {hi}]; pos has {V} vertices")
+    return Call(N, H, W, V, 4, F, _need_device(pos=pos, tri=tri), True)
+
+
+def interpolate(attr: torch.Tensor, rast: torch.Tensor, tri: torch.Tensor) -> Call:
+    if not isinstance(attr, torch.Tensor) or not isinstance(rast, torch.Tensor):
+        raise RuntimeError("attr and rast must be tensors")
+    N, H, W = _check_rast(rast)
+    if attr.dtype != torch.float32 or attr.dim() not in (2, 3) or attr.shape[-1] < 1 or (attr.dim() == 3 and attr.shape[0] not in (1, N)):
+        raise RuntimeError(f"expected float32 attr of shape [{N},V,C], [1,V,C] or [V,C] with C >= 1, got {attr.dtype} {tuple(attr.shape)}")
+    _check_tri(tri)
+    _refuse_grad("attr", attr)
+    _refuse_grad("rast", rast)
+    _need_device(attr=attr, rast=rast, tri=tri)
+    return Call(N, H, W, int(attr.shape[-2]), int(attr.shape[-1]), int(tri.shape[0]), rast.device, attr.dim() == 3 and attr.shape[0] == N and N != 1)
+
+
+def antialias(color: torch.Tensor, rast: torch.Tensor, pos: torch.Tensor, tri: torch.Tensor, topology_hash: Optional[torch.Tensor]) -> Call:
+    if not isinstance(color, torch.Tensor) or not isinstance(rast, torch.Tensor) or not isinstance(pos, torch.Tensor):
+        raise RuntimeError("color, rast and pos must be tensors")
+    N, H, W = _check_rast(rast)
+    if color.dtype != torch.float32 or color.dim() != 4 or tuple(color.shape[:3]) != (N, H, W) or color.shape[-1] < 1:
+        raise RuntimeError(f"expected float32 color of shape [{N},{H},{W},C] with C >= 1, got {color.dtype} {tuple(color.shape)}")
+    if pos.dtype != torch.float32 or pos.dim() not in (2, 3) or pos.shape[-1] != 4 or (pos.dim() == 3 and pos.shape[0] not in (1, N)):
+        raise RuntimeError(f"expected float32 pos of shape [{N},V,4], [1,V,4] or [V,4], got {pos.dtype} {tuple(pos.shape)}")
+    _check_tri(tri)
+    if N * H * W and not (H <= MAX_RESOLUTION and W <= MAX_RESOLUTION):
+        raise RuntimeError(f"rast must have 1 <= H, W <= {MAX_RESOLUTION}, got {tuple(rast.shape)}")
+    F = int(tri.shape[0])
+    if topology_hash is not None:
+        if not isinstance(topology_hash, torch.Tensor) or topology_hash.dtype != torch.int32 or tuple(topology_hash.shape) != (F, 3):
+            got = f"{topology_hash.dtype} {tuple(topology_hash.shape)}" if isinstance(topology_hash, torch.Tensor) else type(topology_hash).__name__
+            raise RuntimeError(f"expected the int32 [{F},3] topology of antialias_construct_topology_hash(tri) as topology_hash, got {got}")
+    for name, t in (("color", color), ("rast", rast), ("pos", pos)):
+        _refuse_grad(name, t)
+    dev = _need_device(color=color, rast=rast, pos=pos, tri=tri)
+    if topology_hash is not None and topology_hash.device != dev:
+        raise RuntimeError(f"topology_hash is on {topology_hash.device}, tri on {dev}: the topology is built on tri's device")
+    return Call(N, H, W, int(pos.shape[-2]), int(color.shape[-1]), F, dev, pos.dim() == 3 and pos.shape[0] == N and N != 1)
+
+
+def topology(tri: torch.Tensor, num_vertices: Optional[int]) -> Call:
+    _check_tri(tri)
+    V = (1 << 31) - 1 if num_vertices is None else int(num_vertices)        # only tri is known: every non-negative index names a vertex
+    if V < 0:
+        raise RuntimeError(f"num_vertices must be >= 0, got {num_vertices}")
+    return Call(1, 0, 0, V, 0, int(tri.shape[0]), _need_device(tri=tri))
+
+
+def image_of(t: torch.Tensor, n: int, N: int) -> torch.Tensor:
+    """image n's part of an input that is given once ([V,C], [1,V,C]) or per image ([N,V,C])"""
+    return t if t.dim() == 2 else t[n if t.shape[0] == N else 0]
+
+
+def run_images(fn: Callable, call: Call, workspace: Optional[Callable[[Call], int]], shared: torch.Tensor, args: Callable[[int, int], tuple]) -> None:
+    """``call.N`` images through one native function: ``fn(stream, *args(n, p)[, workspace, bytes])`` for n = 0 .. N-1 on ``call.dev``'s current stream, under
+    its device guard.  p is the address of image n's contiguous part of ``shared``, the input given once or per image; ``workspace(call)`` gives the bytes of
+    scratch the calls share.  r < 0 raises the library's error."""
+    with torch.cuda.device(call.dev) if torch.cuda.current_device() != call.dev.index else _NO_GUARD:      # (the guard costs more than the test)
+        tail = ()
+        if workspace is not None:
+            nbytes = int(workspace(call))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=call.dev)
+            tail = (ws.data_ptr(), nbytes)
+        st = _raw_stream(call.dev.index)
+        for n in range(call.N):
+            part = image_of(shared, n, call.N).contiguous()                     # (alive over the call)
+            r = fn(st, *args(n, part.data_ptr()), *tail)
+            if r < 0:
+                raise _rast_c._err(r)
+
+
+def grad_workspace_bytes(call: Call) -> int:
+    nbytes = int(_lib.tgs_mesh_grad_workspace_bytes(call.V, call.C, call.H * call.W))
+    if nbytes == 0:
+        raise RuntimeError(f"no gradient workspace for V = {call.V}, C = {call.C}, {call.H * call.W} pixels")
+    return nbytes
+
+
+def build_topology(tri: torch.Tensor, V: int, F: int, dev) -> torch.Tensor:
+    """tri checked (by ``topology`` or by ``antialias``) -> int32 [F,3]"""
+    topo = torch.empty((F, 3), dtype=torch.int32, device=dev)
+    if F:
+        run_images(_lib.tgs_mesh_topology, Call(1, 0, 0, V, 0, F, dev), lambda c: _lib.tgs_mesh_topology_workspace_bytes(F), tri, lambda n, p: (V, F, p, topo.data_ptr()))
+    return topo
+
+
+def topology_of(call: Call, tri: torch.Tensor, topology_hash: Optional[torch.Tensor]) -> torch.Tensor:
+    """the topology a checked ``antialias`` call works with: the one given, else built here, else (no faces or no vertices: a copy) an empty table"""
+    if topology_hash is not None:
+        return topology_hash.contiguous()
+    if call.F and call.V:
+        return build_topology(tri, call.V, call.F, call.dev)
+    return torch.empty((call.F, 3), dtype=torch.int32, device=call.dev)
+
+
+def sum_images(per_image, like: torch.Tensor) -> torch.Tensor:
+    """the images' gradients of a shared input, added in ascending image order -> ``like``'s shape"""
+    return functools.reduce(torch.add, per_image).reshape(like.shape)          # ((g0 + g1) + g2) + ...
+
+
+def input_grad(call: Call, per_image, like: torch.Tensor) -> torch.Tensor:
+    """the gradient of ``attr`` / ``pos`` from its N per-image parts: zeros without pixels, stacked where it has a row per image, else summed"""
+    return torch.zeros_like(like) if not call.N * call.H * call.W else torch.stack(per_image) if call.per_image else sum_images(per_image, like)

@@ -280,16 +280,12 @@ __global__ __launch_bounds__(256) void k_mesh_interpolate(int V, int F, int C, c
     const int c = (int)(e - p * C);
     const float4 r = rast[p];
     float res = 0.f;
-    if (r.w >= 1.0f && r.w <= (float)F) {
-        const size_t t = (size_t)((int)r.w - 1);
-        const int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
-        if ((unsigned)i0 < (unsigned)V && (unsigned)i1 < (unsigned)V && (unsigned)i2 < (unsigned)V)
-        {
-            // in double, rounded once: where u + v is close to 1 the float subtraction's rounding, times a large a2, would exceed the sum of
-            // the three products' own roundings (the kernel moves 16 + 4 C bytes per pixel: the arithmetic is free)
-            const double u = (double)r.x, v = (double)r.y;
-            res = (float)(u * (double)attr[(size_t)i0 * C + c] + v * (double)attr[(size_t)i1 * C + c] + (1.0 - u - v) * (double)attr[(size_t)i2 * C + c]);
-        }
+    int idx[3];
+    if (mesh_pixel_triangle(r.w, F, V, tri, idx) >= 0) {
+        // in double, rounded once: where u + v is close to 1 the float subtraction's rounding, times a large a2, would exceed the sum of
+        // the three products' own roundings (the kernel moves 16 + 4 C bytes per pixel: the arithmetic is free)
+        const double u = (double)r.x, v = (double)r.y;
+        res = (float)(u * (double)attr[(size_t)idx[0] * C + c] + v * (double)attr[(size_t)idx[1] * C + c] + (1.0 - u - v) * (double)attr[(size_t)idx[2] * C + c]);
     }
     out[e] = res;
 }
@@ -302,7 +298,7 @@ extern "C" {
 size_t tgs_mesh_workspace_bytes(int F, int width, int height)
 {
     tgs::MeshWork w;
-    if (F < 0 || width <= 0 || height <= 0 || width > tgs::MESH_MAX_DIM || height > tgs::MESH_MAX_DIM) return 0;
+    if (F < 0 || !tgs::mesh_dims_ok(width, height)) return 0;
     return tgs::mesh_carve(w, nullptr, (size_t)F, (size_t)width * (size_t)height);
 }
 
@@ -310,8 +306,7 @@ int tgs_mesh_rasterize(void* stream, int V, int F, const float* pos, const int32
 {
     using namespace tgs;
     hipStream_t st = (hipStream_t)stream;
-    if (V < 0 || F < 0 || width <= 0 || height <= 0 || width > MESH_MAX_DIM || height > MESH_MAX_DIM || F > MESH_MAX_FACES || !rast || !workspace ||
-        (F > 0 && (!tri || (V > 0 && !pos))))
+    if (V < 0 || !mesh_faces_ok(F) || !mesh_dims_ok(width, height) || !rast || !workspace || (F > 0 && (!tri || (V > 0 && !pos))))
         return set_error(TGS_ERR_INVALID, "tgs_mesh_rasterize: V >= 0, 0 <= F < 2^24, 1 <= width, height <= 8192 and non-NULL pos / tri / rast / workspace required");
     MeshWork w;
     const size_t N = (size_t)width * (size_t)height;
@@ -334,7 +329,7 @@ int tgs_mesh_interpolate(void* stream, int V, int F, int C, const float* attr, c
     if (n_pixels == 0) return TGS_OK;
     if (V < 0 || F < 0 || C < 1 || n_pixels < 0 || !rast || !out || (F > 0 && V > 0 && (!attr || !tri)))
         return set_error(TGS_ERR_INVALID, "tgs_mesh_interpolate: V, F >= 0, C >= 1, n_pixels >= 0 and non-NULL attr / tri / rast / out required");
-    if (n_pixels > 0x7fffffffll * 256 / C) return set_error(TGS_ERR_INVALID, "tgs_mesh_interpolate: n_pixels * C too large for one launch");
+    if (n_pixels > MESH_MAX_ELEMS / C) return set_error(TGS_ERR_INVALID, "tgs_mesh_interpolate: n_pixels * C too large for one launch");
     const long long n_elems = (long long)n_pixels * C;
     // (F == 0 or V == 0: no ID names a triangle, the kernel writes zeros and reads neither attr nor tri)
     hipLaunchKernelGGL(k_mesh_interpolate, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, st, V, V > 0 ? F : 0, C, attr, tri, n_elems, (const float4*)rast, out);

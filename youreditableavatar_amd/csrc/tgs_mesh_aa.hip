@@ -124,30 +124,14 @@ __global__ __launch_bounds__(256) void k_topo_resolve(int V, int F, const int* _
 // The whole decision of one pair is aa_pair_full (tgs_mesh_aa_pair.hpp: the backward of tgs_mesh_grad.hip replays it); the forward keeps its
 // record: +|a| the second pixel receives |a| (color[first] - color[second]), -|a| the first receives |a| (color[second] - color[first]),
 // 0 nothing.
-__device__ __forceinline__ float aa_pair(int V, int F, const float4* __restrict__ pos, const int* __restrict__ tri, const int* __restrict__ topo,
-                                         int W, int H, int i, int j, int di, int dj, float2 r1, float2 r2)
-{
-    return aa_pair_full(V, F, pos, tri, topo, W, H, i, j, di, dj, r1, r2).rec;
-}
-
 __global__ __launch_bounds__(256) void k_aa_pairs(int V, int F, const float4* __restrict__ pos, const int* __restrict__ tri, const int* __restrict__ topo,
                                                   int W, int H, const float4* __restrict__ rast, float* __restrict__ rec_h, float* __restrict__ rec_v)
 {
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= (size_t)W * H) return;
-    const int j = (int)(p / (size_t)W), i = (int)(p - (size_t)j * W);
-    const float4 r = rast[p];
-    const float2 me = make_float2(r.z, r.w);
-    float h = 0.f, v = 0.f;
-    if (i + 1 < W) {
-        const float4 q = rast[p + 1];
-        h = aa_pair(V, F, pos, tri, topo, W, H, i, j, 1, 0, me, make_float2(q.z, q.w));
-    }
-    if (j + 1 < H) {
-        const float4 q = rast[p + W];
-        v = aa_pair(V, F, pos, tri, topo, W, H, i, j, 0, 1, me, make_float2(q.z, q.w));
-    }
-    rec_h[p] = h; rec_v[p] = v;
+    AaPair pr[2] = {aa_no_pair(), aa_no_pair()};
+    aa_pixel_pairs(V, F, pos, tri, topo, W, H, rast, p, pr);
+    rec_h[p] = pr[0].rec; rec_v[p] = pr[1].rec;
 }
 
 // out = (((color + left) + right) + below) + above, every contribution |a| (color[other] - color[self]) rounded on its own
@@ -185,7 +169,7 @@ extern "C" {
 size_t tgs_mesh_topology_workspace_bytes(int F)
 {
     tgs::TopoWork w;
-    if (F < 0 || F > tgs::MESH_MAX_FACES) return 0;
+    if (!tgs::mesh_faces_ok(F)) return 0;
     return tgs::topo_carve(w, nullptr, tgs::topo_capacity((size_t)F));
 }
 
@@ -193,7 +177,7 @@ int tgs_mesh_topology(void* stream, int V, int F, const int32_t* tri, int32_t* t
 {
     using namespace tgs;
     hipStream_t st = (hipStream_t)stream;
-    if (V < 0 || F < 0 || F > MESH_MAX_FACES || !workspace || (F > 0 && (!tri || !topo)))
+    if (V < 0 || !mesh_faces_ok(F) || !workspace || (F > 0 && (!tri || !topo)))
         return set_error(TGS_ERR_INVALID, "tgs_mesh_topology: V >= 0, 0 <= F < 2^24 and non-NULL tri / topo / workspace required");
     TopoWork w;
     const size_t cap = topo_capacity((size_t)F);
@@ -210,7 +194,7 @@ int tgs_mesh_topology(void* stream, int V, int F, const int32_t* tri, int32_t* t
 size_t tgs_mesh_antialias_workspace_bytes(int width, int height)
 {
     tgs::AaWork w;
-    if (width <= 0 || height <= 0 || width > tgs::MESH_MAX_DIM || height > tgs::MESH_MAX_DIM) return 0;
+    if (!tgs::mesh_dims_ok(width, height)) return 0;
     return tgs::aa_carve(w, nullptr, (size_t)width * (size_t)height);
 }
 
@@ -219,13 +203,13 @@ int tgs_mesh_antialias(void* stream, int V, int F, int C, const float* pos, cons
 {
     using namespace tgs;
     hipStream_t st = (hipStream_t)stream;
-    if (V < 0 || F < 0 || F > MESH_MAX_FACES || C < 1 || width <= 0 || height <= 0 || width > MESH_MAX_DIM || height > MESH_MAX_DIM || !rast || !color || !out ||
-        !workspace || (F > 0 && V > 0 && (!pos || !tri || !topo)))
+    if (V < 0 || !mesh_faces_ok(F) || C < 1 || !mesh_dims_ok(width, height) || !rast || !color || !out || !workspace ||
+        (F > 0 && V > 0 && (!pos || !tri || !topo)))
         return set_error(TGS_ERR_INVALID, "tgs_mesh_antialias: V >= 0, 0 <= F < 2^24, C >= 1, 1 <= width, height <= 8192 and non-NULL pos / tri / topo / rast / color / "
                                           "out / workspace required");
     if (out == color) return set_error(TGS_ERR_INVALID, "tgs_mesh_antialias: out may not alias color (every pixel reads its neighbours' colours)");
     const size_t N = (size_t)width * (size_t)height;
-    if (N > (size_t)0x7fffffff * 256 / (size_t)C) return set_error(TGS_ERR_INVALID, "tgs_mesh_antialias: width * height * C too large for one launch");
+    if ((long long)N > MESH_MAX_ELEMS / C) return set_error(TGS_ERR_INVALID, "tgs_mesh_antialias: width * height * C too large for one launch");
     AaWork w;
     if (aa_carve(w, (char*)workspace, N) > workspace_bytes)
         return set_error(TGS_ERR_INVALID, "tgs_mesh_antialias: workspace smaller than tgs_mesh_antialias_workspace_bytes(width, height)");

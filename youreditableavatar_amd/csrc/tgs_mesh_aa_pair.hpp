@@ -1,6 +1,7 @@
 // tgs_mesh_aa_pair.hpp -- the whole decision of one antialias pair, shared by the forward (tgs_mesh_aa.hip) and the backward
 // (tgs_mesh_grad.hip): which triangle, which exit edge, silhouette or not, which pixel receives.  It is written once so that the backward
 // differentiates exactly the pairs the forward blended: every integer decision is the forward's, on the rasterizer's snapped coordinates.
+// aa_pixel_pairs is the per-pixel prologue of both: the pairs a pixel has with its right and its upper neighbour.
 #pragma once
 #include "tgs_mesh_snap.hpp"
 
@@ -25,13 +26,16 @@ __device__ __forceinline__ AaVertex aa_vertex(const float4* __restrict__ pos, in
 // (Px, Py) the centre of the pixel that shows the triangle and (ux, uy) the step to the other one, in snapped units, first: that pixel is the
 // pair's first one.
 struct AaPair { float rec; int va, vb, Px, Py, ux, uy; bool first; };
+__device__ __forceinline__ AaPair aa_no_pair() { return {0.f, -1, -1, 0, 0, 0, 0, false}; }
 
 // (i, j) is the pair's first pixel, (i + di, j + dj) its second, (di, dj) = (1, 0) or (0, 1); r1, r2 are (z/w, ID) of the two.
 __device__ __forceinline__ AaPair aa_pair_full(int V, int F, const float4* __restrict__ pos, const int* __restrict__ tri, const int* __restrict__ topo,
                                                int W, int H, int i, int j, int di, int dj, float2 r1, float2 r2)
 {
 #pragma clang fp contract(off)
-    AaPair res = {0.f, -1, -1, 0, 0, 0, 0, false};
+    AaPair res = aa_no_pair();
+    // The antialias rule's own decode, NOT mesh_pixel_triangle: an ID that is not an integer or lies outside [1, F] is truncated (aa_id), not
+    // rejected, as the header's antialias rule states -- for F + 0.5 antialias still sees triangle F where interpolate sees nothing.
     const int id1 = aa_id(r1.y), id2 = aa_id(r2.y);
     if (id1 == id2) return res;
     // T: the only one with an ID, else the smaller z/w, else (equal or unordered) the lower ID
@@ -83,6 +87,17 @@ __device__ __forceinline__ AaPair aa_pair_full(int V, int F, const float4* __res
     res.vb = kexit == 0 ? idx[1] : kexit == 1 ? idx[2] : idx[0];
     res.Px = Px; res.Py = Py; res.ux = ux; res.uy = uy; res.first = first;
     return res;
+}
+
+// The two pairs that pixel p = (i, j) of the W x H image is the first pixel of: pr[0] with its right neighbour, pr[1] with the one above it
+// (pr holds aa_no_pair() on entry and keeps it at the image's edge).  One lane per pixel, in the forward's pair kernel and in the backward's.
+__device__ __forceinline__ void aa_pixel_pairs(int V, int F, const float4* pos, const int* tri, const int* topo, int W, int H, const float4* rast, size_t p, AaPair pr[2])
+{
+    const int j = (int)(p / (size_t)W), i = (int)(p - (size_t)j * W);
+    const auto zw_id = [](float4 r) { return make_float2(r.z, r.w); };
+    const float2 me = zw_id(rast[p]);
+    if (i + 1 < W) pr[0] = aa_pair_full(V, F, pos, tri, topo, W, H, i, j, 1, 0, me, zw_id(rast[p + 1]));
+    if (j + 1 < H) pr[1] = aa_pair_full(V, F, pos, tri, topo, W, H, i, j, 0, 1, me, zw_id(rast[p + W]));
 }
 
 }  // namespace tgs

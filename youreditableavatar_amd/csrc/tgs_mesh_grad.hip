@@ -125,15 +125,12 @@ __global__ __launch_bounds__(256) void k_interp_bwd(int V, int F, int C, const f
 {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    int t = -1, i0 = 0, i1 = 0, i2 = 0;
+    int t = -1, idx[3] = {0, 0, 0};
     double u = 0.0, v = 0.0;
     if (p < n_pixels) {
         const float4 r = rast[p];
-        if (r.w >= 1.0f && r.w <= (float)F) {
-            const size_t tt = (size_t)((int)r.w - 1);
-            i0 = tri[3 * tt]; i1 = tri[3 * tt + 1]; i2 = tri[3 * tt + 2];
-            if ((unsigned)i0 < (unsigned)V && (unsigned)i1 < (unsigned)V && (unsigned)i2 < (unsigned)V) { t = (int)tt; u = (double)r.x; v = (double)r.y; }
-        }
+        t = mesh_pixel_triangle(r.w, F, V, tri, idx);
+        if (t >= 0) { u = (double)r.x; v = (double)r.y; }
     }
     double scale = 0.0;
     const bool add = ATTR && grad_scale(*bound, scale);                           // (uniform)
@@ -144,18 +141,18 @@ __global__ __launch_bounds__(256) void k_interp_bwd(int V, int F, int C, const f
     for (int c = 0; c < C; c++) {
         const double gc = t >= 0 ? (double)g[p * C + c] : 0.0;
         if (RAST && t >= 0) {
-            const double a2 = (double)attr[(size_t)i2 * C + c];
-            du += gc * ((double)attr[(size_t)i0 * C + c] - a2);
-            dv += gc * ((double)attr[(size_t)i1 * C + c] - a2);
+            const double a2 = (double)attr[(size_t)idx[2] * C + c];
+            du += gc * ((double)attr[(size_t)idx[0] * C + c] - a2);
+            dv += gc * ((double)attr[(size_t)idx[1] * C + c] - a2);
         }
         if (add) {
             const long long s0 = run_sum(t >= 0 ? grad_fixed(u * gc, scale) : 0ll, lane, runs);
             const long long s1 = run_sum(t >= 0 ? grad_fixed(v * gc, scale) : 0ll, lane, runs);
             const long long s2 = run_sum(t >= 0 ? grad_fixed(w2 * gc, scale) : 0ll, lane, runs);
             if (runs.head && t >= 0) {
-                grad_add(acc + (size_t)i0 * C + c, s0);
-                grad_add(acc + (size_t)i1 * C + c, s1);
-                grad_add(acc + (size_t)i2 * C + c, s2);
+                grad_add(acc + (size_t)idx[0] * C + c, s0);
+                grad_add(acc + (size_t)idx[1] * C + c, s1);
+                grad_add(acc + (size_t)idx[2] * C + c, s2);
             }
         }
     }
@@ -219,20 +216,16 @@ __global__ __launch_bounds__(256) void k_rast_bwd(int V, int F, const float4* __
     int t = -1, idx[3] = {0, 0, 0};
     double d[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (p < (size_t)W * H) {
-        const float4 r = rast[p];
-        if (r.w >= 1.0f && r.w <= (float)F) {
-            const size_t tt = (size_t)((int)r.w - 1);
-            idx[0] = tri[3 * tt]; idx[1] = tri[3 * tt + 1]; idx[2] = tri[3 * tt + 2];
-            if ((unsigned)idx[0] < (unsigned)V && (unsigned)idx[1] < (unsigned)V && (unsigned)idx[2] < (unsigned)V) {
-                const float4 q[3] = {pos[idx[0]], pos[idx[1]], pos[idx[2]]};
-                float sx, sy;
-                int X, Y;
-                if (mesh_snap(q[0], W, H, sx, sy, X, Y) && mesh_snap(q[1], W, H, sx, sy, X, Y) && mesh_snap(q[2], W, H, sx, sy, X, Y)) {
-                    const int j = (int)(p / (size_t)W), i = (int)(p - (size_t)j * W);
-                    const float4 gp = g[p];
-                    t = (int)tt;
-                    rast_uv_grad(q, W, H, i, j, (double)gp.x, (double)gp.y, d);
-                }
+        const int tt = mesh_pixel_triangle(rast[p].w, F, V, tri, idx);
+        if (tt >= 0) {
+            const float4 q[3] = {pos[idx[0]], pos[idx[1]], pos[idx[2]]};
+            float sx, sy;
+            int X, Y;
+            if (mesh_snap(q[0], W, H, sx, sy, X, Y) && mesh_snap(q[1], W, H, sx, sy, X, Y) && mesh_snap(q[2], W, H, sx, sy, X, Y)) {
+                const int j = (int)(p / (size_t)W), i = (int)(p - (size_t)j * W);
+                const float4 gp = g[p];
+                t = tt;
+                rast_uv_grad(q, W, H, i, j, (double)gp.x, (double)gp.y, d);
             }
         }
     }
@@ -293,20 +286,10 @@ __global__ __launch_bounds__(256) void k_aa_bwd(int V, int F, int C, const float
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const bool live = p < (size_t)W * H;
-    AaPair pr[2] = {{0.f, -1, -1, 0, 0, 0, 0, false}, {0.f, -1, -1, 0, 0, 0, 0, false}};
+    AaPair pr[2] = {aa_no_pair(), aa_no_pair()};
     double d[2][6] = {{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
     if (live) {
-        const int j = (int)(p / (size_t)W), i = (int)(p - (size_t)j * W);
-        const float4 r = rast[p];
-        const float2 me = make_float2(r.z, r.w);
-        if (i + 1 < W) {
-            const float4 q = rast[p + 1];
-            pr[0] = aa_pair_full(V, F, pos, tri, topo, W, H, i, j, 1, 0, me, make_float2(q.z, q.w));
-        }
-        if (j + 1 < H) {
-            const float4 q = rast[p + W];
-            pr[1] = aa_pair_full(V, F, pos, tri, topo, W, H, i, j, 0, 1, me, make_float2(q.z, q.w));
-        }
+        aa_pixel_pairs(V, F, pos, tri, topo, W, H, rast, p, pr);
         if (MODE < 2) { rec_h[p] = pr[0].rec; rec_v[p] = pr[1].rec; }
         if (MODE > 0) {
             if (pr[0].rec != 0.f) aa_pair_grad(pr[0], pos, C, W, H, p, p + 1, color, g, boost, d[0]);
@@ -356,7 +339,16 @@ __global__ __launch_bounds__(256) void k_aa_bwd_color(int C, int W, int H, long 
     dcolor[e] = res;
 }
 
-constexpr long long GRAD_MAX_ELEMS = 0x7fffffffll * 256;                         // one launch, one lane per element
+// The scatter protocol of one gradient out[n] (the head of this file has the reasons): zero the bound and n accumulators, the caller's measuring
+// launch (w.bound <- max |contribution|), its accumulating launch (w.acc), k_grad_convert into out.  false: a memset was refused (hip_status says why).
+template <class Measure, class Accumulate>
+inline bool grad_scatter(hipStream_t st, const GradWork& w, size_t n, float* out, Measure measure, Accumulate accumulate)
+{
+    if (hipMemsetAsync(w.bound, 0, 64 * sizeof(uint32_t), st) != hipSuccess || hipMemsetAsync(w.acc, 0, n * sizeof(unsigned long long), st) != hipSuccess) return false;
+    measure(); accumulate();
+    hipLaunchKernelGGL(k_grad_convert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n, w.acc, w.bound, out);
+    return true;
+}
 
 }  // namespace tgs
 
@@ -366,7 +358,7 @@ extern "C" {
 size_t tgs_mesh_grad_workspace_bytes(int V, int C, int64_t n_pixels)
 {
     tgs::GradWork w;
-    if (V < 0 || C < 1 || n_pixels < 0 || n_pixels > (int64_t)tgs::MESH_MAX_DIM * tgs::MESH_MAX_DIM) return 0;
+    if (V < 0 || C < 1 || !tgs::mesh_pixels_ok(n_pixels)) return 0;
     return tgs::grad_carve(w, nullptr, (size_t)V, (size_t)C, (size_t)n_pixels);
 }
 
@@ -375,11 +367,11 @@ int tgs_mesh_interpolate_backward(void* stream, int V, int F, int C, const float
 {
     using namespace tgs;
     hipStream_t st = (hipStream_t)stream;
-    if (V < 0 || F < 0 || F > MESH_MAX_FACES || C < 1 || n_pixels < 0 || n_pixels > (int64_t)MESH_MAX_DIM * MESH_MAX_DIM || !workspace ||
-        (n_pixels > 0 && (!rast || !dL_dout)) || (F > 0 && V > 0 && n_pixels > 0 && (!attr || !tri)))
+    if (V < 0 || !mesh_faces_ok(F) || C < 1 || !mesh_pixels_ok(n_pixels) || !workspace || (n_pixels > 0 && (!rast || !dL_dout)) ||
+        (F > 0 && V > 0 && n_pixels > 0 && (!attr || !tri)))
         return set_error(TGS_ERR_INVALID, "tgs_mesh_interpolate_backward: V >= 0, 0 <= F < 2^24, C >= 1, 0 <= n_pixels <= 8192^2 and non-NULL attr / tri / rast / "
                                           "dL_dout / workspace required");
-    if (n_pixels > GRAD_MAX_ELEMS / C) return set_error(TGS_ERR_INVALID, "tgs_mesh_interpolate_backward: n_pixels * C too large for one launch");
+    if (n_pixels > MESH_MAX_ELEMS / C) return set_error(TGS_ERR_INVALID, "tgs_mesh_interpolate_backward: n_pixels * C too large for one launch");
     GradWork w;
     if (grad_carve(w, (char*)workspace, (size_t)V, (size_t)C, (size_t)n_pixels) > workspace_bytes)
         return set_error(TGS_ERR_INVALID, "tgs_mesh_interpolate_backward: workspace smaller than tgs_mesh_grad_workspace_bytes(V, C, n_pixels)");
@@ -391,17 +383,14 @@ int tgs_mesh_interpolate_backward(void* stream, int V, int F, int C, const float
     if (empty || (!dL_dattr && !dL_drast)) return TGS_OK;
     const long long n_elems = (long long)n_pixels * C;
     const dim3 blk(256), pgrid((unsigned)((n_pixels + 255) / 256));
-    if (dL_dattr) {
-        if (hipMemsetAsync(w.bound, 0, 64 * sizeof(uint32_t), st) != hipSuccess || hipMemsetAsync(w.acc, 0, n_attr * sizeof(unsigned long long), st) != hipSuccess)
-            return hip_status("tgs_mesh_interpolate_backward");
-        hipLaunchKernelGGL(k_grad_max_abs, dim3((unsigned)((n_elems + 255) / 256)), blk, 0, st, n_elems, dL_dout, w.bound);
-    }
-    const float4* r4 = (const float4*)rast;
-    if (dL_dattr && dL_drast) hipLaunchKernelGGL((k_interp_bwd<true, true>), pgrid, blk, 0, st, V, F, C, attr, tri, (long long)n_pixels, r4, dL_dout, (float4*)dL_drast, w.acc, w.bound);
-    else if (dL_dattr)        hipLaunchKernelGGL((k_interp_bwd<true, false>), pgrid, blk, 0, st, V, F, C, attr, tri, (long long)n_pixels, r4, dL_dout, (float4*)nullptr, w.acc, w.bound);
-    else                      hipLaunchKernelGGL((k_interp_bwd<false, true>), pgrid, blk, 0, st, V, F, C, attr, tri, (long long)n_pixels, r4, dL_dout, (float4*)dL_drast, w.acc, w.bound);
-    if (dL_dattr)
-        hipLaunchKernelGGL(k_grad_convert, dim3((unsigned)((n_attr + 255) / 256)), blk, 0, st, (long long)n_attr, w.acc, w.bound, dL_dattr);
+    const auto pixels = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, pgrid, blk, 0, st, V, F, C, attr, tri, (long long)n_pixels, (const float4*)rast, dL_dout, (float4*)dL_drast, w.acc, w.bound);
+    };
+    if (!dL_dattr) pixels(k_interp_bwd<false, true>);
+    else if (!grad_scatter(st, w, n_attr, dL_dattr,                               // (the weights lie in [0, 1]: the upstream's largest |g| is the bound)
+                           [&] { hipLaunchKernelGGL(k_grad_max_abs, dim3((unsigned)((n_elems + 255) / 256)), blk, 0, st, n_elems, dL_dout, w.bound); },
+                           [&] { if (dL_drast) pixels(k_interp_bwd<true, true>); else pixels(k_interp_bwd<true, false>); }))
+        return hip_status("tgs_mesh_interpolate_backward");
     return hip_status("tgs_mesh_interpolate_backward");
 }
 
@@ -410,8 +399,7 @@ int tgs_mesh_rasterize_backward(void* stream, int V, int F, const float* pos, co
 {
     using namespace tgs;
     hipStream_t st = (hipStream_t)stream;
-    if (V < 0 || F < 0 || F > MESH_MAX_FACES || width <= 0 || height <= 0 || width > MESH_MAX_DIM || height > MESH_MAX_DIM || !rast || !dL_drast || !workspace ||
-        (V > 0 && !dL_dpos) || (F > 0 && V > 0 && (!pos || !tri)))
+    if (V < 0 || !mesh_faces_ok(F) || !mesh_dims_ok(width, height) || !rast || !dL_drast || !workspace || (V > 0 && !dL_dpos) || (F > 0 && V > 0 && (!pos || !tri)))
         return set_error(TGS_ERR_INVALID, "tgs_mesh_rasterize_backward: V >= 0, 0 <= F < 2^24, 1 <= width, height <= 8192 and non-NULL pos / tri / rast / dL_drast / "
                                           "dL_dpos / workspace required");
     GradWork w;
@@ -424,12 +412,10 @@ int tgs_mesh_rasterize_backward(void* stream, int V, int F, const float* pos, co
         if (hipMemsetAsync(dL_dpos, 0, n_pos * sizeof(float), st) != hipSuccess) return hip_status("tgs_mesh_rasterize_backward");
         return TGS_OK;
     }
-    if (hipMemsetAsync(w.bound, 0, 64 * sizeof(uint32_t), st) != hipSuccess || hipMemsetAsync(w.acc, 0, n_pos * sizeof(unsigned long long), st) != hipSuccess)
-        return hip_status("tgs_mesh_rasterize_backward");
     const dim3 blk(256), pgrid((unsigned)((N + 255) / 256));
-    hipLaunchKernelGGL(k_rast_bwd<true>, pgrid, blk, 0, st, V, F, (const float4*)pos, tri, width, height, (const float4*)rast, (const float4*)dL_drast, w.acc, w.bound);
-    hipLaunchKernelGGL(k_rast_bwd<false>, pgrid, blk, 0, st, V, F, (const float4*)pos, tri, width, height, (const float4*)rast, (const float4*)dL_drast, w.acc, w.bound);
-    hipLaunchKernelGGL(k_grad_convert, dim3((unsigned)((n_pos + 255) / 256)), blk, 0, st, (long long)n_pos, w.acc, w.bound, dL_dpos);
+    const float4 *p4 = (const float4*)pos, *r4 = (const float4*)rast, *g4 = (const float4*)dL_drast;
+    const auto pixels = [&](auto kernel) { hipLaunchKernelGGL(kernel, pgrid, blk, 0, st, V, F, p4, tri, width, height, r4, g4, w.acc, w.bound); };
+    if (!grad_scatter(st, w, n_pos, dL_dpos, [&] { pixels(k_rast_bwd<true>); }, [&] { pixels(k_rast_bwd<false>); })) return hip_status("tgs_mesh_rasterize_backward");
     return hip_status("tgs_mesh_rasterize_backward");
 }
 
@@ -439,14 +425,14 @@ int tgs_mesh_antialias_backward(void* stream, int V, int F, int C, const float* 
 {
     using namespace tgs;
     hipStream_t st = (hipStream_t)stream;
-    if (V < 0 || F < 0 || F > MESH_MAX_FACES || C < 1 || width <= 0 || height <= 0 || width > MESH_MAX_DIM || height > MESH_MAX_DIM || !rast || !color || !dL_dout ||
-        !workspace || (F > 0 && V > 0 && (!pos || !tri || !topo)))
+    if (V < 0 || !mesh_faces_ok(F) || C < 1 || !mesh_dims_ok(width, height) || !rast || !color || !dL_dout || !workspace ||
+        (F > 0 && V > 0 && (!pos || !tri || !topo)))
         return set_error(TGS_ERR_INVALID, "tgs_mesh_antialias_backward: V >= 0, 0 <= F < 2^24, C >= 1, 1 <= width, height <= 8192 and non-NULL pos / tri / topo / rast / "
                                           "color / dL_dout / workspace required");
     if (dL_dcolor && dL_dcolor == dL_dout)
         return set_error(TGS_ERR_INVALID, "tgs_mesh_antialias_backward: dL_dcolor may not alias dL_dout (every pixel reads its neighbours' upstream rows)");
     const size_t N = (size_t)width * (size_t)height;
-    if ((long long)N > GRAD_MAX_ELEMS / C) return set_error(TGS_ERR_INVALID, "tgs_mesh_antialias_backward: width * height * C too large for one launch");
+    if ((long long)N > MESH_MAX_ELEMS / C) return set_error(TGS_ERR_INVALID, "tgs_mesh_antialias_backward: width * height * C too large for one launch");
     GradWork w;
     if (grad_carve(w, (char*)workspace, (size_t)V, (size_t)C, N) > workspace_bytes)
         return set_error(TGS_ERR_INVALID, "tgs_mesh_antialias_backward: workspace smaller than tgs_mesh_grad_workspace_bytes(V, C, width * height)");
@@ -459,17 +445,15 @@ int tgs_mesh_antialias_backward(void* stream, int V, int F, int C, const float* 
         return TGS_OK;
     }
     if (!dL_dcolor && !dL_dpos) return TGS_OK;
-    const dim3 blk(256), pgrid((unsigned)((N + 255) / 256));
-    const float4 *p4 = (const float4*)pos, *r4 = (const float4*)rast;
-    const double boost = (double)pos_gradient_boost;
+    const dim3 blk(256);
+    const auto pixels = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((N + 255) / 256)), blk, 0, st, V, F, C, (const float4*)pos, tri, topo, width, height, (const float4*)rast, color,
+                           dL_dout, (double)pos_gradient_boost, w.rec_h, w.rec_v, w.acc, w.bound);
+    };
     if (dL_dpos) {
-        if (hipMemsetAsync(w.bound, 0, 64 * sizeof(uint32_t), st) != hipSuccess || hipMemsetAsync(w.acc, 0, n_pos * sizeof(unsigned long long), st) != hipSuccess)
-            return hip_status("tgs_mesh_antialias_backward");
-        hipLaunchKernelGGL(k_aa_bwd<1>, pgrid, blk, 0, st, V, F, C, p4, tri, topo, width, height, r4, color, dL_dout, boost, w.rec_h, w.rec_v, w.acc, w.bound);
-        hipLaunchKernelGGL(k_aa_bwd<2>, pgrid, blk, 0, st, V, F, C, p4, tri, topo, width, height, r4, color, dL_dout, boost, w.rec_h, w.rec_v, w.acc, w.bound);
-        hipLaunchKernelGGL(k_grad_convert, dim3((unsigned)((n_pos + 255) / 256)), blk, 0, st, (long long)n_pos, w.acc, w.bound, dL_dpos);
+        if (!grad_scatter(st, w, n_pos, dL_dpos, [&] { pixels(k_aa_bwd<1>); }, [&] { pixels(k_aa_bwd<2>); })) return hip_status("tgs_mesh_antialias_backward");
     } else
-        hipLaunchKernelGGL(k_aa_bwd<0>, pgrid, blk, 0, st, V, F, C, p4, tri, topo, width, height, r4, color, dL_dout, boost, w.rec_h, w.rec_v, w.acc, w.bound);
+        pixels(k_aa_bwd<0>);                                                      // the records alone, for dL_dcolor
     if (dL_dcolor)
         hipLaunchKernelGGL(k_aa_bwd_color, dim3((unsigned)((n_elems + 255) / 256)), blk, 0, st, C, width, height, n_elems, dL_dout, w.rec_h, w.rec_v, dL_dcolor);
     return hip_status("tgs_mesh_antialias_backward");
