@@ -608,6 +608,61 @@ int tgs_mesh_antialias_backward(void* stream, int V, int F, int C, const float* 
                                 const float* rast, const float* color, const float* dL_dout, float* dL_dcolor, float* dL_dpos,
                                 float pos_gradient_boost, void* workspace, size_t workspace_bytes);
 
+/* ---- marching tetrahedra ----
+ * The step in front of the mesh rasterizer in the geometry stage: MarchingTetrahedraHelper._forward (tetgs_spatial/models/isosurface.py :112-184,
+ * called from forward, _isosurface and _isosurface_subdiv) and the call shape of the two marching_tetrahedra calls of models/geometry/base.py
+ * (:350, :465).  pos[N,3] fp32, sdf[N] fp32, tet[F,4] int32 or int64 (tet_is_int64 = 0 / 1: both are read as they are, no conversion pass).
+ * The rules:
+ *   inside       occ = sdf > 0: a NaN counts as outside and an exact zero counts as outside.
+ *   valid_tets   [F] one byte each: 1 where one to three of the tetrahedron's corners are inside.  The case code is sum_k occ_k 2^k.
+ *   interp_v     [M,2] int64: the distinct crossing edges of the valid tetrahedra -- exactly one endpoint inside -- each stored as
+ *                (min index, max index), in ascending lexicographic order of that pair.  An edge whose two indices are equal is never a
+ *                crossing edge.  Duplicated tetrahedra are legal: their edges are found once.
+ *   verts        [M,3] fp32: for edge (a, b) D = sdf[a] + (-sdf[b]), w_a = (-sdf[b]) / D, w_b = sdf[a] / D, v = pos[a] w_a + pos[b] w_b, every
+ *                operation rounded to fp32 on its own (no contraction).  The endpoints have opposite sign or are zero, so D is a sum of
+ *                magnitudes and nothing cancels.  A NaN sdf on a crossing edge gives a NaN vertex.
+ *   faces        [T,3] int64 rows of verts, T = n_one + 2 n_two: the one-triangle tetrahedra first, in ascending tetrahedron index, then the
+ *                two-triangle tetrahedra in ascending index with their two triangles adjacent.  The corner order is the 16-case table's over
+ *                the edge numbering (0,1) (0,2) (0,3) (1,2) (1,3) (2,3).
+ *   face_to_tet_idx  [T] int64, the same order.
+ * Fixed order: every output position comes from a prefix sum or from a sorted run; the hash only dedupes (integer CAS on the 64-bit
+ * (min, max) key; no output reads a slot number), the edges are ranked by a count per min vertex, one scan over N, and a sort of each
+ * vertex's few edges by their max index.  No float atomics anywhere: two runs give the same bits.
+ * The signs are packed once per call into a bitmap of N / 8 bytes, which the classify pass gathers its four bits from.
+ * Phases and read-backs: the sizes depend on the data, so the ABI is phased and the caller reads counts[4] (int64, device) back twice.
+ *   1. tgs_marching_tets_classify writes valid_tets and counts[0] = n_one, counts[1] = n_two, counts[2] = the index flag.  First read-back:
+ *      these three.  counts[2] != 0: an index outside [0, N) was met -- the caller treats it as TGS_ERR_INVALID; the kernels never read through
+ *      such an index (the tetrahedron is left out), so nothing faults.  n_one + n_two = 0: every output is empty and no further call is needed.
+ *   2. tgs_marching_tets_edges dedupes the 3 n_one + 4 n_two crossing edges in `table` -- sized from what phase 1 counted,
+ *      tgs_marching_tets_table_bytes(3 n_one + 4 n_two), never from the 4 F worst case -- and writes counts[3] = M.  Second read-back: M.
+ *   3. tgs_marching_tets_emit writes verts, interp_v, faces, face_to_tet_idx into arrays of exactly M and T rows.
+ * The three calls share `workspace` (tgs_marching_tets_workspace_bytes(N, F) bytes; 0 for sizes that are refused) and `table`, unchanged by
+ * the caller in between; n_one, n_two and M are passed back as they were read.  The calls allocate nothing and synchronise nothing.
+ * tgs_marching_tets_emit uses up what tgs_marching_tets_edges left in the workspace (the runs' starts become cursors): one emit per edges call.
+ * N, F < 2^31; tet is 16-byte aligned (a row is loaded as one or two 16-byte vectors).  F == 0: classify clears counts and launches nothing.
+ * One lane sorts a vertex's run: the work is quadratic in the number of crossing edges that share their min vertex (a dozen at the most on a
+ * grid of tetrahedra; a mesh that gives one vertex 10^5 crossing edges is served, slowly).  The backward's max-end lists likewise.
+ * Backward: dL_dverts[M,3] -> dL_dpos[N,3], dL_dsdf[N] (NULL for one that is not wanted).  With D = sdf[a] - sdf[b] and v the vertex:
+ *   dv/dpos[a] = -sdf[b] / D, dv/dpos[b] = sdf[a] / D, dv/dsdf[a] = (pos[b] - v) / D, dv/dsdf[b] = (v - pos[a]) / D.
+ * It is a gather per grid row, no scatter and no float atomics on gradient memory: a row's edges as the min end are a contiguous run of
+ * interp_v; its edges as the max end come from offsets of their own (a count per max vertex, a scan, a fill, each list sorted by edge
+ * number).  A row adds its min-end edges in ascending order, then its max-end edges in ascending order, in double from the fp32 inputs, and
+ * is rounded to fp32 once: the error term is that one rounding, 2^-24 of the element, on top of the double sum's.  Values are stored, not
+ * accumulated; rows that no crossing edge touches are exact zeros; two runs give the same bits.
+ * workspace: tgs_marching_tets_backward_workspace_bytes(N, M) bytes. */
+size_t tgs_marching_tets_workspace_bytes(int N, int F);
+size_t tgs_marching_tets_table_bytes(int64_t n_crossing);
+int tgs_marching_tets_classify(void* stream, int N, int F, const float* sdf, const void* tet, int tet_is_int64, uint8_t* valid_tets, int64_t* counts,
+                               void* workspace, size_t workspace_bytes);
+int tgs_marching_tets_edges(void* stream, int N, int F, const void* tet, int tet_is_int64, int64_t n_one, int64_t n_two, int64_t* counts,
+                            void* workspace, size_t workspace_bytes, void* table, size_t table_bytes);
+int tgs_marching_tets_emit(void* stream, int N, int F, const float* pos, const float* sdf, const void* tet, int tet_is_int64, int64_t n_one, int64_t n_two,
+                           int64_t M, float* verts, int64_t* interp_v, int64_t* faces, int64_t* face_to_tet_idx,
+                           void* workspace, size_t workspace_bytes, void* table, size_t table_bytes);
+size_t tgs_marching_tets_backward_workspace_bytes(int N, int64_t M);
+int tgs_marching_tets_backward(void* stream, int N, int64_t M, const float* pos, const float* sdf, const int64_t* interp_v, const float* dL_dverts,
+                               float* dL_dpos, float* dL_dsdf, void* workspace, size_t workspace_bytes);
+
 /* ---- Batched backward (multi-view steps) ----
  * Rasterizer::backward runs its per-Gaussian half (computeCov2DCUDA + preprocessCUDA of backward.cu) once per view; with
  * in-place accumulation that is 192 B of SH read plus 192 B of dL_dsh read AND written per Gaussian per view.  A batch
