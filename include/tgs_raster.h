@@ -663,6 +663,72 @@ size_t tgs_marching_tets_backward_workspace_bytes(int N, int64_t M);
 int tgs_marching_tets_backward(void* stream, int N, int64_t M, const float* pos, const float* sdf, const int64_t* interp_v, const float* dL_dverts,
                                float* dL_dpos, float* dL_dsdf, void* workspace, size_t workspace_bytes);
 
+/* ---- mesh geometry ----
+ * What the geometry stage computes on a fresh mesh between marching tetrahedra and the mesh rasterizer: compute_normal / compute_vertex_normal
+ * (tetgs_spatial/models/renderers/nvdiff_rasterize_utils.py :12-35, :37-70), Mesh._compute_vertex_normal, Mesh._compute_edges,
+ * Mesh.normal_consistency and Mesh.laplacian (models/mesh.py :136-162, :261-273, :275-280, :282-315).  v_pos[V,3] fp32, faces[F,3] int32 or int64
+ * (faces_is_int64 = 0 / 1: both are read as they are, no conversion pass).
+ * The topology is built once per mesh and read by every later call:
+ *   incidence    inc[3 F] uint32: the entries 3 * face + corner, grouped by the corner's vertex (a CSR layout); each vertex's run is in
+ *                ascending order of 3 * face + corner.
+ *   edges        [E,2] int64: the distinct (min index, max index) pairs of the 3 F face sides (0,1) (1,2) (2,0), in ascending lexicographic
+ *                order.  A pair (i, i), which a degenerate face produces, is kept, as the reference keeps it.  Edge e's number is its row.
+ *   max_list     [E] uint32: the edge numbers grouped by the edge's max vertex, each vertex's list ascending.  A vertex's edges as the min end
+ *                are a contiguous run of `edges`.
+ *   offsets      inc_end, edge_end, max_end [V + 1] uint32 hold the ENDS of the runs: vertex v's run is [v ? end[v - 1] : 0, end[v]).
+ * Fixed order: every output position comes from a prefix sum or from a sorted run; the hash only dedupes (integer CAS on the 64-bit
+ * (min, max) key; no output reads a slot number).  One lane sorts a vertex's run: quadratic in the valence (4 to 9 on a marching-tetrahedra
+ * mesh; an apex of 10^5 faces is served, slowly).
+ * Phases and the read-back: E depends on the data, so the topology is two calls around one read-back of counts[4] (int64, device).
+ *   1. tgs_meshgeom_topology_count counts a vertex's corners, dedupes the 3 F sides in `table` -- sized from 3 F, known before the call:
+ *      tgs_meshgeom_table_bytes(F) -- and scans: counts[0] = E, counts[1] = the index flag, counts[2] = the incidence entries.  The read-back:
+ *      E and the flag.  counts[1] != 0: an index outside [0, V) was met -- the caller treats it as TGS_ERR_INVALID; the kernels never read
+ *      through such an index (the face is left out), so nothing faults.  table == NULL: incidence only (E = 0, edge_end / max_end unused).
+ *   2. tgs_meshgeom_topology_fill writes inc, edges[E,2] and max_list[E]; the offsets' starts become cursors and end as the runs' ends: one
+ *      fill per count call.  Later calls read nothing back.
+ * The rules of the values:
+ *   normals      v_nrm[V,3]: per vertex the face normals cross(v1 - v0, v2 - v0) of its incidence run (always along the last axis), evaluated
+ *                and added in double in run order.  The row is (0, 0, 1) unless the squared length of the sum is > 1e-20 -- a non-finite sum
+ *                fails that comparison and gets the default too -- else the sum divided by its length; rounded to fp32 once.  After the
+ *                reference's `where`, its two normalizations (F.normalize, safe_normalize) are the same function.
+ *   normals, backward  three gathers: per vertex the upstream through the normalization, g_s = (g - n (n . g)) / |s|, an exact zero for a
+ *                default row; per face G = the g_s of its three corners added; per vertex, over its incidence run, with e1 = v1 - v0,
+ *                e2 = v2 - v0: corner 1 receives e2 x G, corner 2 receives G x e1, corner 0 minus both, added in double in run order and
+ *                rounded once.  Plain arithmetic with no skip-if-zero shortcut: 0 * NaN is a NaN, as in the framework's backward.  Rows
+ *                that no face touches are exact zeros.
+ *   consistency  out[1] = mean over the edges of 1 - cos(n_a, n_b), cos as the framework's cosine similarity evaluates it: each row divided by
+ *                max(|row|, 1e-8), then the dot product.  Per-workgroup partial sums in double (a fixed shuffle tree), then one workgroup adds
+ *                them in a fixed order.  Backward: a gather per vertex over its min-end run, then its max-end list:
+ *                d cos / d x = (y^ - cos [|x| >= 1e-8] x / |x|) / max(|x|, 1e-8), times -dL_dout / E.
+ *   laplacian    out[1] = mean over the V rows of |sum over the row's distinct neighbours o != v of (v_pos[v] - v_pos[o])|: the uniform
+ *                Laplacian of the distinct adjacency.  A pair (i, i) adds -1 and +1 to the diagonal in the reference's sparse construction:
+ *                nothing.  The forward stores the unit rows r / |r| in double (unit_rows[V,3], NULL if no gradient is wanted; a zero row
+ *                gets the zero subgradient), and the backward is the same gather over them -- the operator is symmetric -- times dL_dout / V.
+ * No float atomics anywhere, and no atomics at all on gradient memory: two runs give the same bits, forward and backward.  Values are stored,
+ * not accumulated.  dL_dout is read on the device.  A NULL gradient output: nothing is launched.
+ * workspace: tgs_meshgeom_workspace_bytes(V, F) bytes for the topology and the two losses (any F with 3 F >= E), and
+ * tgs_meshgeom_normals_backward_workspace_bytes(V, F) for the normals' backward; 0 for sizes that are refused.  V, F < 2^31 and
+ * F <= (2^32 - 1) / 3: incidence entries and edge numbers are 32-bit.  The calls allocate nothing and synchronise nothing.
+ * The prefix is tgs_meshgeom_, in one word: tgs_mesh_* is the mesh rasterizer's family of eleven, which its signature table is checked against. */
+size_t tgs_meshgeom_workspace_bytes(int V, int F);
+size_t tgs_meshgeom_table_bytes(int F);
+size_t tgs_meshgeom_normals_backward_workspace_bytes(int V, int F);
+int tgs_meshgeom_topology_count(void* stream, int V, int F, const void* faces, int faces_is_int64, uint32_t* inc_end, uint32_t* edge_end, uint32_t* max_end,
+                                 int64_t* counts, void* table, size_t table_bytes, void* workspace, size_t workspace_bytes);
+int tgs_meshgeom_topology_fill(void* stream, int V, int F, const void* faces, int faces_is_int64, int64_t E, uint32_t* inc_end, uint32_t* inc, uint32_t* edge_end,
+                                uint32_t* max_end, int64_t* edges, uint32_t* max_list, const void* table, size_t table_bytes);
+int tgs_meshgeom_normals(void* stream, int V, int F, const float* v_pos, const void* faces, int faces_is_int64, const uint32_t* inc_end, const uint32_t* inc,
+                          float* v_nrm);
+int tgs_meshgeom_normals_backward(void* stream, int V, int F, const float* v_pos, const void* faces, int faces_is_int64, const uint32_t* inc_end, const uint32_t* inc,
+                                   const float* dL_dnrm, float* dL_dpos, void* workspace, size_t workspace_bytes);
+int tgs_meshgeom_consistency(void* stream, int V, int64_t E, const float* v_nrm, const int64_t* edges, float* out, void* workspace, size_t workspace_bytes);
+int tgs_meshgeom_consistency_backward(void* stream, int V, int64_t E, const float* v_nrm, const int64_t* edges, const uint32_t* edge_end, const uint32_t* max_end,
+                                       const uint32_t* max_list, const float* dL_dout, float* dL_dnrm);
+int tgs_meshgeom_laplacian(void* stream, int V, int64_t E, const float* v_pos, const int64_t* edges, const uint32_t* edge_end, const uint32_t* max_end,
+                            const uint32_t* max_list, double* unit_rows, float* out, void* workspace, size_t workspace_bytes);
+int tgs_meshgeom_laplacian_backward(void* stream, int V, int64_t E, const int64_t* edges, const uint32_t* edge_end, const uint32_t* max_end, const uint32_t* max_list,
+                                     const double* unit_rows, const float* dL_dout, float* dL_dpos);
+
 /* ---- Batched backward (multi-view steps) ----
  * Rasterizer::backward runs its per-Gaussian half (computeCov2DCUDA + preprocessCUDA of backward.cu) once per view; with
  * in-place accumulation that is 192 B of SH read plus 192 B of dL_dsh read AND written per Gaussian per view.  A batch
