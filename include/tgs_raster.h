@@ -729,6 +729,81 @@ int tgs_meshgeom_laplacian(void* stream, int V, int64_t E, const float* v_pos, c
 int tgs_meshgeom_laplacian_backward(void* stream, int V, int64_t E, const int64_t* edges, const uint32_t* edge_end, const uint32_t* max_end, const uint32_t* max_list,
                                      const double* unit_rows, const float* dL_dout, float* dL_dpos);
 
+/* ---- hash-grid field ----
+ * The head of the geometry stage's chain, the field that produces sdf on every vertex of the tetrahedral grid: the multiresolution hash-grid
+ * encoding (a tcnn.Encoding of otype HashGrid in the reference, tetgs_spatial/models/networks.py :55-95, with the ProgressiveBandHashGrid mask)
+ * and the bias-free VanillaMLP behind it (:151-188), as models/geometry/implicit_sdf.py :26-41 configures them and forward_sdf / forward_field
+ * call them.  3 input dimensions, 2 features per level, linear interpolation, fp32 throughout; x[N,3], params[n_params], enc[N, 2 n_levels].
+ * The level table is computed ONCE, on the host (youreditableavatar_amd.hashgrid.level_table), and never recomputed on the device.  For level l,
+ * in float32 arithmetic: scale = exp2(l * log2(per_level_scale)) * base_resolution - 1, resolution = ceil(scale) + 1;
+ * size = min(round_up(resolution^3, 8), 2^log2_hashmap_size) entries; offset = the running sum of the sizes; dense = resolution^3 <= size.
+ * It travels to the kernels in the kernel argument, as at most 16 records of tgs_hashgrid_level_t: there is no device allocation for it and no
+ * read-back.  `levels` is a HOST pointer to n_levels records; a record that contradicts the rules above (offset not the running sum, size not a
+ * multiple of 8 or above 2^log2_hashmap_size, dense with resolution^3 > size, scale outside [0, 2^20)) is refused.
+ * Parameter layout: level-major, then entry, then feature: params[(offset + index) * 2 + f], n_params = 2 * the sum of the sizes.  This is the
+ * published layout of tiny-cuda-nn's grid encoding; it has not been compared against tiny-cuda-nn itself, which the project cannot run.
+ * The encoding of a point x, per level:
+ *   cell         pos = x * scale + 0.5, cell = floor(pos), frac = pos - cell, evaluated in double from the fp32 x and the fp32 scale: the product
+ *                is exact, so the cell decision is the rule's own and not an artefact of rounding.
+ *   corners      cell + {0,1}^3, each coordinate taken as uint32 (a negative cell wraps).
+ *   index        a dense level: cx + cy * res + cz * res^2; a hashed level: cx * 1 ^ cy * 2654435761 ^ cz * 805459861; both in uint32 arithmetic.
+ *                The index is then ALWAYS taken % size, so no coordinate, inside [0, 1] or not, can address outside the level.  x = 1.0 reaches
+ *                the corner coordinate res, which aliases into the next row of a dense level (cx = res is cx = 0 of row cy + 1): that is the rule.
+ *   value        columns 2 l and 2 l + 1 are the trilinear sum of the eight corners' rows, weights prod_d (frac_d or 1 - frac_d), formed in double
+ *                and rounded to fp32 once.
+ *   mask         levels at or above active_levels are skipped and their columns are exact zeros (ProgressiveBandHashGrid's mask); their
+ *                parameter gradients are exact zeros.
+ *   NaN row      a point with a non-finite coordinate, or one of magnitude above 1024, gives a row of NaN in every column (and in every output
+ *                of the field); in the backward it contributes nothing to any parameter or weight gradient, and its row of dL_dx is NaN.
+ * tgs_hashgrid_encode_backward: dL_denc[N, 2 n_levels] -> dL_dparams[n_params] and, with a non-NULL pointer, dL_dx[N,3].  dL_dx is the
+ * first-order derivative of the trilinear weights (scale * sum over the corners of +-row * the other two weights; cell held fixed), one lane
+ * per point in double, rounded once: a gather, no scatter.
+ * tgs_hashgrid_field, the fused path, per point: the optional box map x' = (x - bbox_min) / (bbox_max - bbox_min), every operation rounded
+ * to fp32 on its own (scale_tensor of contract_to_unisphere with unbounded = False; bbox is a HOST pointer to min[3], max[3], or NULL); the
+ * encoding of x', held in registers; h = relu(W1 enc) with W1[hidden, 2 n_levels]; out[N, n_out] = W2 h + bias with W2[n_out, hidden] and the
+ * scalar bias (sdf_bias).  hidden in {16, 32, 64}, 1 <= n_out <= 4, one hidden layer, no layer biases.  The products are fp32 FMAs in ascending
+ * column order.  Nothing of size N x 2 n_levels or N x hidden is written to memory.
+ * tgs_hashgrid_field_backward recomputes enc and h per point from x, params and W1 and writes dL_dparams, dL_dW1[hidden, 2 n_levels] and
+ * dL_dW2[n_out, hidden] (NULL for one that is not wanted).  relu passes the gradient where its input is > 0.  There is no dL_dx on the fused path.
+ * Gradients, no float atomics: dL_dparams is accumulated in fixed point exactly as in "mesh rasterizer: gradients" above (one shared header):
+ *   bound        a device-side B >= max |contribution| that is never read back.  Encode path: B = max |dL_denc|, because the weights lie in
+ *                [0, 1].  Fused path: dL_denc exists only inside the kernel, and the bound is the ANALYTIC upper bound
+ *                B = max |dL_dout| * max_j sum_k sum_o |W1[k,j]| |W2[o,k]|, from a tiny kernel, in double and rounded up to fp32.
+ *   accumulate   with 2^(e-1) <= B < 2^e a contribution c becomes llrint(c 2^(34 - e)); a point contributes at most 8 per level, so N <= 2^25
+ *                points stay within the 2^28 contributions the 63 bits allow.  The lanes of a wave are pre-reduced in integers over runs of
+ *                lanes in one cell (a sorted or a piled point set), one no-return 64-bit integer atomic per run and element;
+ *   convert      one pass converts the accumulators to fp32, one rounding.  Resolution: n 2^(e-35) <= n B 2^-34 for n contributions.
+ * Elements that no point reaches are exact zeros.  A non-finite bound makes that gradient all NaN.  dL_dW1 and dL_dW2 are per-workgroup partial
+ * sums in double (a persistent grid of at most 1024 workgroups, each adding its points in a fixed order), stored to the workspace and added in
+ * ascending workgroup order by a second small kernel, rounded once.  Two runs give the same bits for every output, forward and backward.
+ * Gradients are stored, not accumulated.
+ * Argument limits; everything outside is refused with TGS_ERR_INVALID and a message before any device call: n_input_dims == 3,
+ * n_features == 2, 1 <= n_levels <= 16, 3 <= log2_hashmap_size <= 24, 0 <= active_levels <= n_levels, 0 <= N <= 2^25 per call.  N == 0: nothing
+ * is launched and the gradients are zeros.
+ * workspace: tgs_hashgrid_workspace_bytes(n_params, hidden, n_out) bytes, hidden = n_out = 0 for the encode path: 8 bytes per parameter, the
+ * 1024 slabs of 64 * 32 + 4 * 64 doubles on the fused path, a small constant; 0 for arguments that are refused.  The calls allocate nothing
+ * and synchronise nothing. */
+typedef struct {
+    float scale;            /* exp2(l log2(per_level_scale)) base_resolution - 1, in float32 */
+    uint32_t resolution;    /* ceil(scale) + 1 */
+    uint32_t size;          /* entries of the level */
+    uint32_t offset;        /* entries in front of the level */
+    uint32_t dense;         /* 1: resolution^3 <= size, indexed without the hash */
+} tgs_hashgrid_level_t;
+size_t tgs_hashgrid_workspace_bytes(int64_t n_params, int hidden, int n_out);
+int tgs_hashgrid_encode(void* stream, int64_t N, int n_input_dims, const float* x, const float* params, const tgs_hashgrid_level_t* levels, int n_levels,
+                        int n_features, int log2_hashmap_size, int active_levels, float* enc);
+int tgs_hashgrid_encode_backward(void* stream, int64_t N, int n_input_dims, const float* x, const float* params, const tgs_hashgrid_level_t* levels,
+                                 int n_levels, int n_features, int log2_hashmap_size, int active_levels, const float* dL_denc, float* dL_dparams,
+                                 float* dL_dx, void* workspace, size_t workspace_bytes);
+int tgs_hashgrid_field(void* stream, int64_t N, int n_input_dims, const float* x, const float* params, const tgs_hashgrid_level_t* levels, int n_levels,
+                       int n_features, int log2_hashmap_size, int active_levels, const float* bbox, const float* W1, const float* W2, int hidden, int n_out,
+                       float bias, float* out);
+int tgs_hashgrid_field_backward(void* stream, int64_t N, int n_input_dims, const float* x, const float* params, const tgs_hashgrid_level_t* levels,
+                                int n_levels, int n_features, int log2_hashmap_size, int active_levels, const float* bbox, const float* W1, const float* W2,
+                                int hidden, int n_out, const float* dL_dout, float* dL_dparams, float* dL_dW1, float* dL_dW2, void* workspace,
+                                size_t workspace_bytes);
+
 /* ---- Batched backward (multi-view steps) ----
  * Rasterizer::backward runs its per-Gaussian half (computeCov2DCUDA + preprocessCUDA of backward.cu) once per view; with
  * in-place accumulation that is 192 B of SH read plus 192 B of dL_dsh read AND written per Gaussian per view.  A batch
