@@ -804,6 +804,61 @@ int tgs_hashgrid_field_backward(void* stream, int64_t N, int n_input_dims, const
                                 int hidden, int n_out, const float* dL_dout, float* dL_dparams, float* dL_dW1, float* dL_dW2, void* workspace,
                                 size_t workspace_bytes);
 
+/* ---- tetrahedral grids ----
+ * The grid's own topology passes between the field and marching tetrahedra in the geometry stage's step: MarchingTetrahedraHelper.compact_tets
+ * and .batch_subdivide_volume (tetgs_spatial/models/isosurface.py :264-345), which _isosurface_subdiv and _part_isosurface of
+ * models/geometry/base.py run every step, and the selection-and-remap that mark_part_tets (:208-261) runs twice.  pos[N,3] fp32, sdf[N] fp32,
+ * tet[F,4] int32 or int64 (tet_is_int64 = 0 / 1: both are read as they are, no conversion pass).  Everything is integer topology plus bit
+ * copies and exact halvings: the outputs are pinned element for element and bit for bit, there are no tolerances.
+ * compact -- the rules:
+ *   selection    a tetrahedron is kept iff fabsf((((s0 + s1) + s2) + s3) * 0.25f) <= threshold, s_k = sdf[tet[f,k]], evaluated in float32, left to
+ *                right, every operation rounded on its own (no contraction); threshold is a float32.  That is what a mean over four float32, an
+ *                abs and a <= compute on the CPU.  A NaN mean is dropped.  With a non-NULL keep[F] (one byte each) the tetrahedron is kept iff
+ *                its byte is non-zero, and sdf is not read.
+ *   indices      new_tet_idx_to_old[F'] holds the kept tetrahedra's indices, ascending.  unique_vtx[N'] holds the kept tetrahedra's distinct
+ *                vertex indices, ascending.  new_tets[f', k] is the rank of tet[old, k] in unique_vtx.  int64, or int32 with out_is_int64 = 0.
+ *   gathers      new_pos[N',3], new_sdf[N'] and new_mask[N'] are the rows of pos, sdf and mask at unique_vtx, as bit copies.  mask_type names
+ *                the mask's element: 0 int32, 1 int64, 2 float32, 3 one byte.  A NULL input is not gathered.
+ *   membership   with a non-NULL member_workspace -- the workspace another select call with the same N and F left behind -- member[N'] (int32) is
+ *                1 where that call kept the vertex too: membership by index, read from the two bitmaps.
+ * compact -- fixed order: a kept vertex is a bit in a bitmap of N bits (atomicOr on 64-bit words), its rank is the scanned popcount of the
+ * words before it plus the popcount of the bits below it; a kept tetrahedron's row is a workgroup scan on top of the scanned workgroup counts.
+ * compact -- phases and the read-back: tgs_tet_compact_select writes counts[0] = F', counts[1] = N', counts[2] = the index flag (counts[4],
+ * int64, device).  The one read-back: these three.  counts[2] != 0: an index outside [0, N) was met -- the caller treats it as TGS_ERR_INVALID;
+ * the kernels never read through such an index (the tetrahedron is left out), so nothing faults.  F' = 0: every output is empty and no further
+ * call is needed.  tgs_tet_compact_emit writes the outputs into arrays of exactly F' and N' rows.
+ * subdivide -- the rules:
+ *   edges        the six edges of a row (a, b, c, d) are ab, ac, ad, bc, bd, cd.  edges[E,2] int64 holds the distinct (min index, max index) pairs
+ *                of all rows in ascending lexicographic order.  An edge (v, v) of a row with a repeated vertex is an edge like any other; a
+ *                tetrahedron listed twice adds nothing.
+ *   new_v        [B, N + E, 3] fp32: the rows of pos, then per edge (pos[e0] + pos[e1]) * 0.5f: the sum rounded to fp32, then the exact halving.
+ *                A non-finite input propagates.  B batch elements share the topology; pos is [B,N,3].
+ *   new_mask     [B, N + E] fp32: the mask's values as floats, then 1.0 where the two end points' mask values sum to 2, else 0.0.
+ *   new_tets     [8 F, 4] int64: midpoint indices are N + the edge's row in `edges`; sub-tetrahedron k of parent f is row k F + f, with the corners
+ *                k = 0 (a, ab, ac, ad), 1 (b, bc, ab, bd), 2 (c, ac, bc, cd), 3 (d, ad, cd, bd), 4 (ab, ac, ad, bd), 5 (ab, ac, bd, bc),
+ *                6 (cd, ac, bd, ad), 7 (cd, ac, bc, bd).  sub_to_parent[k F + f] = f.
+ * subdivide -- fixed order, no hash table: every one of the 6 F edges goes into its min vertex's run (a count per min vertex, one scan over N,
+ * a fill through cursors), one lane sorts its vertex's run by the max index and drops the repeats in place, and a scan over the distinct
+ * counts ranks the edges; a binary search in the min vertex's run finds an edge's row.  24 bytes of workspace per tetrahedron.  One lane
+ * sorts a vertex's run: its work is the number of edge slots that share their min vertex (about 36 inside a grid of tetrahedra) times the
+ * distinct edges among them (7 there).  A tetrahedron issues one integer atomic per corner that is the min end of an edge, three at the most.
+ * subdivide -- phases and the read-back: tgs_tet_subdivide_edges writes counts[0] = E, counts[1] = the index flag.  The one read-back: these
+ * two.  tgs_tet_subdivide_emit writes the outputs; N + E < 2^31 or it is refused.
+ * The calls of a pair share `workspace` (tgs_tet_compact_workspace_bytes(N, F), tgs_tet_subdivide_workspace_bytes(N, F); 0 for sizes that are
+ * refused), unchanged by the caller in between.  The calls allocate nothing and synchronise nothing.  N, F < 2^31, and F <= (2^31 - 1) / 8 for
+ * the subdivision, whose new_tets has 8 F rows; tet is 16-byte aligned.  F == 0: the first call of a pair clears counts and launches nothing.
+ * No float atomics anywhere: two runs give the same bits. */
+size_t tgs_tet_compact_workspace_bytes(int N, int F);
+int tgs_tet_compact_select(void* stream, int N, int F, const float* sdf, const void* tet, int tet_is_int64, const uint8_t* keep, float threshold, int64_t* counts,
+                           void* workspace, size_t workspace_bytes);
+int tgs_tet_compact_emit(void* stream, int N, int F, const void* tet, int tet_is_int64, int64_t n_tets, int64_t n_verts, const float* pos, const float* sdf,
+                         const void* mask, int mask_type, const void* member_workspace, int out_is_int64, void* new_tets, void* new_tet_idx_to_old,
+                         void* unique_vtx, float* new_pos, float* new_sdf, void* new_mask, int32_t* member, void* workspace, size_t workspace_bytes);
+size_t tgs_tet_subdivide_workspace_bytes(int N, int F);
+int tgs_tet_subdivide_edges(void* stream, int N, int F, const void* tet, int tet_is_int64, int64_t* counts, void* workspace, size_t workspace_bytes);
+int tgs_tet_subdivide_emit(void* stream, int N, int F, int B, int64_t E, const float* pos, const void* tet, int tet_is_int64, const void* mask, int mask_type,
+                           float* new_v, int64_t* new_tets, float* new_mask, int64_t* sub_to_parent, int64_t* edges, void* workspace, size_t workspace_bytes);
+
 /* ---- Batched backward (multi-view steps) ----
  * Rasterizer::backward runs its per-Gaussian half (computeCov2DCUDA + preprocessCUDA of backward.cu) once per view; with
  * in-place accumulation that is 192 B of SH read plus 192 B of dL_dsh read AND written per Gaussian per view.  A batch

@@ -23,13 +23,10 @@
 //
 // The case table is written as the tetrahedron's corner pairs: a triangle corner is the crossing of the edge between local corners i and j, one
 // byte 0xij, three bytes per triangle, the first triangle in the high half.  tests/golden/ref_mt_fixture.npz (cases16) pins it.
-#include "tgs_device.hpp"
+#include "tgs_tet_common.hpp"                                           // the scans, the row load, the run sort and search
 
 namespace tgs {
 
-constexpr int MT_BLOCK = 256;
-constexpr int MT_SCAN_ITEMS = 8;
-constexpr int MT_SCAN_TILE = MT_BLOCK * MT_SCAN_ITEMS;                  // elements one workgroup scans
 constexpr unsigned long long MT_EMPTY = ~0ull;                          // no key: min <= max < 2^31 never gives all ones
 constexpr long long MT_MAX_CROSSING = 1ll << 33;                        // 4 F with F < 2^31
 
@@ -63,13 +60,6 @@ struct MtWork {
     uint32_t* run;                        // [N + 1] crossing edges per min vertex; scanned: run[v] is where v's edges start; after k_mt_fill where they end
     uint32_t* scan;                       // scratch of the scans
 };
-__host__ __device__ inline size_t mt_scan_scratch(size_t n)
-{
-    size_t s = 0;
-    while (n > (size_t)MT_SCAN_TILE) { n = (n + MT_SCAN_TILE - 1) / MT_SCAN_TILE; s += (n + 63) & ~(size_t)63; }
-    return s + 64;
-}
-__host__ __device__ inline size_t mt_blocks(size_t F) { return (F + MT_BLOCK - 1) / MT_BLOCK; }
 __host__ __device__ inline size_t mt_carve(MtWork& w, char* base, size_t N, size_t F)
 {
     char* p = base;
@@ -105,47 +95,6 @@ __device__ __forceinline__ unsigned long long mt_hash(unsigned long long k)     
     return k ^ (k >> 31);
 }
 
-// exclusive scan over the workgroup's 256 lanes; total: the workgroup's sum.  lds: 4 words.
-__device__ __forceinline__ uint32_t mt_block_escan(uint32_t v, uint32_t& total, uint32_t* lds)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t inc = wave_iscan_u32(v, lane);
-    if (lane == 63) lds[wv] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < MT_BLOCK / 64; k++) { const uint32_t s = lds[k]; base += k < wv ? s : 0u; total += s; }
-    __syncthreads();
-    return base + inc - v;
-}
-
-// ---- exclusive scan of uint32 in place: workgroup sums, their scan (recursively), then every workgroup on its own tile ----
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_scan_sums(const uint32_t* __restrict__ data, size_t n, uint32_t* __restrict__ sums)
-{
-    __shared__ uint32_t lds[4];
-    const size_t first = (size_t)blockIdx.x * MT_SCAN_TILE + (size_t)threadIdx.x * MT_SCAN_ITEMS;
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < MT_SCAN_ITEMS; k++) s += first + k < n ? data[first + k] : 0u;
-    uint32_t total;
-    mt_block_escan(s, total, lds);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_scan_tile(uint32_t* __restrict__ data, size_t n, const uint32_t* __restrict__ sums, long long* __restrict__ total_out)
-{
-    __shared__ uint32_t lds[4];
-    const size_t first = (size_t)blockIdx.x * MT_SCAN_TILE + (size_t)threadIdx.x * MT_SCAN_ITEMS;
-    uint32_t v[MT_SCAN_ITEMS], s = 0;
-#pragma unroll
-    for (int k = 0; k < MT_SCAN_ITEMS; k++) { v[k] = first + k < n ? data[first + k] : 0u; s += v[k]; }
-    uint32_t total;
-    uint32_t at = mt_block_escan(s, total, lds) + (sums ? sums[blockIdx.x] : 0u);
-#pragma unroll
-    for (int k = 0; k < MT_SCAN_ITEMS; k++) { if (first + k < n) data[first + k] = at; at += v[k]; }
-    if (total_out && threadIdx.x == 0) *total_out = (long long)total;    // (only the one-workgroup launch at the top is given total_out)
-}
-
 // ---- forward ----
 __global__ __launch_bounds__(MT_BLOCK) void k_mt_signs(int N, const float* __restrict__ sdf, unsigned long long* __restrict__ bits)
 {
@@ -158,23 +107,6 @@ __device__ __forceinline__ uint32_t mt_bit(const unsigned long long* __restrict_
 {
     return (uint32_t)(bits[v >> 6] >> (v & 63)) & 1u;
 }
-template <typename Idx>
-__device__ __forceinline__ void mt_load_tet(const Idx* __restrict__ tet, size_t f, long long t[4])
-{
-    if constexpr (sizeof(Idx) == 4) {
-        const int4 r = reinterpret_cast<const int4*>(tet)[f];
-        t[0] = r.x; t[1] = r.y; t[2] = r.z; t[3] = r.w;
-    } else {
-        const longlong2 r0 = reinterpret_cast<const longlong2*>(tet)[2 * f], r1 = reinterpret_cast<const longlong2*>(tet)[2 * f + 1];
-        t[0] = r0.x; t[1] = r0.y; t[2] = r1.x; t[3] = r1.y;
-    }
-}
-__device__ __forceinline__ bool mt_in_range(const long long t[4], int N)
-{
-    return (unsigned long long)t[0] < (unsigned long long)N && (unsigned long long)t[1] < (unsigned long long)N &&
-           (unsigned long long)t[2] < (unsigned long long)N && (unsigned long long)t[3] < (unsigned long long)N;
-}
-
 template <typename Idx>
 __global__ __launch_bounds__(MT_BLOCK) void k_mt_classify(int N, int F, const Idx* __restrict__ tet, const unsigned long long* __restrict__ bits,
                                                           uint8_t* __restrict__ code, uint8_t* __restrict__ valid, uint32_t* __restrict__ blk_one,
@@ -251,12 +183,7 @@ __global__ __launch_bounds__(MT_BLOCK) void k_mt_sort_runs(int N, long long M, c
     const long long lo = v ? run[v - 1] : 0;
     long long hi = run[v];
     if (hi > M) hi = M;
-    for (long long i = lo + 1; i < hi; i++) {
-        const long long b = interp_v[2 * i + 1];
-        long long j = i;
-        for (; j > lo && interp_v[2 * (j - 1) + 1] > b; j--) interp_v[2 * j + 1] = interp_v[2 * (j - 1) + 1];
-        interp_v[2 * j + 1] = b;
-    }
+    mt_sort_run(interp_v + 1, 2, lo, hi);
 }
 
 // v = pos[a] w_a + pos[b] w_b with w_a = (-sdf[b]) / D, w_b = sdf[a] / D, D = sdf[a] + (-sdf[b]); every operation rounded on its own
@@ -280,13 +207,7 @@ __device__ __forceinline__ long long mt_find(int N, long long M, const uint32_t*
 {
     long long lo = a ? run[a - 1] : 0, hi = run[a];
     if (hi > M) hi = M;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        const long long have = interp_v[2 * mid + 1];
-        if (have == b) return mid;
-        if (have < b) lo = mid + 1; else hi = mid;
-    }
-    return -1;
+    return mt_search_run(interp_v + 1, 2, lo, hi, b);
 }
 
 template <typename Idx>
@@ -384,22 +305,6 @@ __global__ __launch_bounds__(MT_BLOCK) void k_mt_grad(int N, long long M, const 
     if (d_pos) { d_pos[3 * v] = (float)acc.p[0]; d_pos[3 * v + 1] = (float)acc.p[1]; d_pos[3 * v + 2] = (float)acc.p[2]; }
     if (d_sdf) d_sdf[v] = (float)acc.s;
 }
-
-// exclusive scan of data[0 .. n) in place on `st`; the sum goes to *total_out (device) if given
-static void mt_scan(hipStream_t st, uint32_t* data, size_t n, uint32_t* scratch, long long* total_out)
-{
-    if (n <= (size_t)MT_SCAN_TILE) {
-        hipLaunchKernelGGL(k_mt_scan_tile, dim3(1), dim3(MT_BLOCK), 0, st, data, n, (const uint32_t*)nullptr, total_out);
-        return;
-    }
-    const size_t nb = (n + MT_SCAN_TILE - 1) / MT_SCAN_TILE;
-    hipLaunchKernelGGL(k_mt_scan_sums, dim3((unsigned)nb), dim3(MT_BLOCK), 0, st, (const uint32_t*)data, n, scratch);
-    mt_scan(st, scratch, nb, scratch + ((nb + 63) & ~(size_t)63), total_out);
-    hipLaunchKernelGGL(k_mt_scan_tile, dim3((unsigned)nb), dim3(MT_BLOCK), 0, st, data, n, (const uint32_t*)scratch, (long long*)nullptr);
-}
-
-static inline dim3 mt_grid(size_t n) { return dim3((unsigned)((n + MT_BLOCK - 1) / MT_BLOCK)); }
-static inline bool mt_aligned(const void* tet) { return ((uintptr_t)tet & 15u) == 0; }              // rows are loaded as 16-byte vectors
 
 }  // namespace tgs
 
