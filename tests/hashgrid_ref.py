@@ -20,10 +20,23 @@ CONFIGS = {
     "tiny": dict(otype="HashGrid", n_levels=4, n_features_per_level=2, log2_hashmap_size=6, base_resolution=2, per_level_scale=2.0),
     "odd": dict(otype="Grid", type="Hash", n_levels=5, n_features_per_level=2, log2_hashmap_size=8, base_resolution=3, per_level_scale=1.5),
 }
+_WIDE = dict(otype="HashGrid", n_levels=16, n_features_per_level=2, log2_hashmap_size=7, base_resolution=2, per_level_scale=1.3)
+_SINGLE = dict(otype="HashGrid", n_levels=1, n_features_per_level=2, log2_hashmap_size=5, base_resolution=3, per_level_scale=2.0)
+CONFIGS.update(wide=_WIDE, wide_thin=_WIDE, single=_SINGLE, single_wide=_SINGLE)      # the launch cases' grids: every table is below 16 KB
 MLP = {"default": (64, 1), "tiny": (16, 3), "odd": (32, 4)}           # hidden width and outputs of the fused field in each config's cases
+MLP.update(wide=(64, 4), wide_thin=(16, 1), single=(16, 2), single_wide=(64, 4))     # the full LDS layout; most chunks skipped; C = 2 and D = 2
 BBOX = ((-1.0, -0.5, -2.0), (1.0, 1.5, 1.0))                           # the box the fused cases map their points from
 POINT_SETS = ("uniform", "lattice", "pile", "one", "outside")
 CASES = [("default", "uniform"), ("default", "pile")] + [(c, s) for c in ("tiny", "odd") for s in POINT_SETS]   # (the default table is 49 MB)
+# The launch cases (tests/test_gpu_hashgrid_launch.py): the shapes at which the kernels take the branches that CASES leaves alone.
+LAUNCH_SETS = ("many", "runs", "far")
+MANY = 1024 * 256 + 2 * 256 + 77                                       # above HG_MAX_SLABS * HG_BLOCK: workgroups 0, 1, 2 take two tiles, the last a partial one
+RUN_LENGTHS = (1, 2, 3, 5, 31, 33, 63, 64, 65, 127, 130, 200, 300)
+RUN_REPEATS = 3
+NAN_RUN, ZERO_RUN = 70, 13                                             # the run with a NaN row inside, and the run in cell (0,0,0) with one in its middle
+FAR_NEAR, FAR_N = 256, 2048
+LAUNCH_CASES = [("tiny", "many")] + [(c, s) for c in ("wide", "wide_thin", "single", "single_wide") for s in ("uniform", "runs")] + \
+    [(c, "runs") for c in ("tiny", "odd")] + [(c, "far") for c in ("tiny", "odd", "wide")]
 KINK_FACTOR = 64.0 * 2.0 ** -24
 KINK_CAP = 0.01
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_hashgrid_fixture.npz")   # tests/make_ref_hashgrid_fixture.py
@@ -55,7 +68,7 @@ def _seed(*names):
 
 
 def points(config_name, set_name):
-    """-> [N,3] float32 in the grid's domain (the unit cube and a little around it)"""
+    """-> [N,3] float32 in the grid's domain (the unit cube and a little around it; ``far``: up to |x| = 1024).  POINT_SETS and LAUNCH_SETS."""
     rng = np.random.default_rng(_seed(config_name, set_name))
     levels = level_table(CONFIGS[config_name])
     if set_name == "uniform":
@@ -70,9 +83,40 @@ def points(config_name, set_name):
         return np.repeat(rng.uniform(0.0, 1.0, (1, 3)).astype(np.float32), 4096, axis=0)
     if set_name == "one":
         return rng.uniform(0.0, 1.0, (1, 3)).astype(np.float32)
+    if set_name == "many":
+        return rng.uniform(0.0, 1.0, (MANY, 3)).astype(np.float32)
+    if set_name == "runs":
+        return _runs(rng, levels[-1].scale)
+    if set_name == "far":
+        x = np.concatenate([rng.uniform(-3.0, 4.0, (FAR_NEAR, 3)), rng.uniform(-MAX_COORD, MAX_COORD, (FAR_N - FAR_NEAR - 3, 3)), np.zeros((3, 3))]).astype(np.float32)
+        x[-3] = (MAX_COORD, -MAX_COORD, MAX_COORD)                       # valid: the rule admits |x| <= 1024
+        x[-2] = (0.25, np.nextafter(np.float32(MAX_COORD), np.float32(np.inf)), 0.75)
+        x[-1] = (0.5, 0.5, -np.inf)
+        return x
     x = rng.uniform(-0.5, 1.5, (17, 3)).astype(np.float32)              # outside
     x[5] = (np.nan, 0.5, 0.5)
     return x
+
+
+def _runs(rng, scale):
+    """consecutive rows in runs of prescribed lengths, each run jittered inside one cell of the finest level (cell k: pos = x scale + 0.5 in [k, k + 1),
+    so the centre is x = k / scale, +- 0.2 cell).  RUN_LENGTHS in RUN_REPEATS orders; between them a run of NAN_RUN rows with a NaN row inside, and a
+    run of ZERO_RUN rows with every coordinate in [0, 0.5 / scale) -- cell (0,0,0) at every level -- with a NaN row in its middle."""
+    def run(n):
+        k = rng.integers(1, max(int(np.floor(scale)), 1) + 1, 3).astype(np.float64)
+        return (k + rng.uniform(-0.2, 0.2, (n, 3))) / scale
+    parts = []
+    for rep in range(RUN_REPEATS):
+        parts += [run(int(n)) for n in rng.permutation(RUN_LENGTHS)]
+        if rep == 0:
+            holed = run(NAN_RUN)
+            holed[NAN_RUN // 3] = (np.nan, 0.5, 0.5)
+            parts.append(holed)
+        if rep == 1:
+            zero = rng.uniform(0.0, 0.499 / scale, (ZERO_RUN, 3))
+            zero[ZERO_RUN // 2] = (0.5, np.nan, 0.5)
+            parts.append(zero)
+    return np.concatenate(parts).astype(np.float32)
 
 
 def table(config_name):
@@ -93,6 +137,12 @@ def upstream(kind, shape, *names):
     if kind == "one_row":
         keep = int(rng.integers(0, shape[0]))
         g[np.arange(shape[0]) != keep] = 0.0
+    if kind == "binades":                                               # one row 2^40 above the rest: what the bound leaves of the small rows
+        keep = int(rng.integers(0, shape[0]))
+        g *= np.float32(2.0 ** -20)
+        g[keep] *= np.float32(2.0 ** 40)
+    if kind == "denormal":                                              # max |g| = 2^-130: the bound is a denormal
+        g = (g.astype(np.float64) / np.abs(g).max() * 2.0 ** -130).astype(np.float32)
     return g
 
 
@@ -257,3 +307,53 @@ def case(config_name, set_name, kind="random", active=None):
     for a in (x, xb, P, W1, W2, g_enc, g_out):
         a.setflags(write=False)
     return out
+
+
+def run_lengths(cell, valid, wave=None):
+    """the lengths of the runs of consecutive valid rows in one cell ([N,3] int64), an invalid row breaking a run; with ``wave``, a run also ends
+    where a wave of that many rows does -> a list of ints"""
+    cell, valid = np.asarray(cell), np.asarray(valid)
+    out, n = [], 0
+    for r in range(len(cell)):
+        joins = n > 0 and valid[r] and (cell[r] == cell[r - 1]).all() and (wave is None or r % wave)
+        if joins:
+            n += 1
+            continue
+        if n:
+            out.append(n)
+        n = 1 if valid[r] else 0
+    return out + ([n] if n else [])
+
+
+def term_sums(x, valid, params, g, levels, active=None):
+    """The sums of the magnitudes of the terms of the encode path's three results, in float64, for the round-once bars: ``enc`` [N, 2 n_levels] =
+    sum_i w_i |row_i|; ``d_x`` [N,3] = sum_l scale_l sum_i (|g_0| |row_i0| + |g_1| |row_i1|) (the corner's two other weights); ``d_params`` =
+    per element the sum of w |g| over the contributions that reach it.  ``x`` [N,3] float32, ``valid`` [N] bool: the other rows hold zeros and
+    reach no element."""
+    valid = torch.tensor(np.asarray(valid))
+    x = torch.where(valid[:, None], torch.tensor(np.asarray(x)).double(), torch.full((1, 3), 0.5, dtype=torch.float64))
+    rows, g = torch.tensor(np.asarray(params)).double().abs().view(-1, 2), torch.tensor(np.asarray(g)).double().abs() * valid[:, None]
+    m_enc, m_x, m_p = torch.zeros_like(g), torch.zeros_like(x), torch.zeros_like(rows)
+    for l, lv in enumerate(levels[:len(levels) if active is None else active]):
+        pos = x * lv.scale + 0.5
+        cell = torch.floor(pos).to(torch.int64)
+        f = pos - cell.double()
+        at = lv.offset + corner_indices(cell, lv)
+        side = [[(f[:, d] if (i >> d) & 1 else 1.0 - f[:, d]) for d in range(3)] for i in range(8)]
+        w = torch.stack([a * b * c for a, b, c in side], dim=1) * valid[:, None]                      # [N,8]
+        v = rows[at]                                                                                    # [N,8,2]
+        gl = g[:, 2 * l:2 * l + 2]
+        m_enc[:, 2 * l:2 * l + 2] = (w[..., None] * v).sum(dim=1)
+        s = (v * gl[:, None, :]).sum(dim=2)                                                             # [N,8]
+        for d in range(3):
+            others = torch.stack([side[i][(d + 1) % 3] * side[i][(d + 2) % 3] for i in range(8)], dim=1)
+            m_x[:, d] += lv.scale * (s * others).sum(dim=1)
+        m_p.index_add_(0, at.reshape(-1), (w[..., None] * gl[:, None, :]).reshape(-1, 2))
+    return dict(enc=m_enc.numpy(), d_x=m_x.numpy(), d_params=m_p.reshape(-1).numpy())
+
+
+@functools.lru_cache(maxsize=None)
+def magnitudes(config_name, set_name, kind="random", active=None):
+    """``term_sums`` of a case's encode path, computed once"""
+    c = case(config_name, set_name, kind, active)
+    return term_sums(c["x"], c["valid"], c["params"], c["g_enc"], c["levels"], active)

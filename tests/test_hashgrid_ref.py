@@ -1,5 +1,9 @@
 """CPU: the restatement of the hash-grid field's rules (tests/hashgrid_ref.py) against the figures of the reference's default config, against a slow
-per-point loop, at x = 1.0, under the kink cap, and under float64 gradcheck; and youreditableavatar_amd.hashgrid.level_table against the same figures."""
+per-point loop, at x = 1.0, under the kink cap, and under float64 gradcheck; and youreditableavatar_amd.hashgrid.level_table against the same figures.
+Below them, the conditions on the launch cases (R.LAUNCH_CASES) that tests/test_gpu_hashgrid_launch.py relies on: the tile count of ``many`` against the
+kernel's own constants, the run lengths of ``runs`` on every level, the rows of ``far``, the kink cap, the slow loop and the level tables."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -101,3 +105,103 @@ def test_the_cases_are_what_the_issue_lists():
     assert c["enc"]["n"] >= 4096
     g = R.upstream("one_row", (9, 4), "x")
     assert (np.abs(g).sum(axis=1) > 0).sum() == 1
+
+
+# ---- the launch cases (tests/test_gpu_hashgrid_launch.py) ------------------------------------------------------------------------------
+WIDE_RESOLUTIONS = [2, 3, 4, 5, 6, 8, 10, 13, 17, 22, 28, 36, 47, 61, 79, 103]
+LAUNCH_CONFIGS = ("wide", "wide_thin", "single", "single_wide")
+RUNS_CONFIGS = sorted({c for c, s in R.LAUNCH_CASES if s == "runs"})
+
+
+def _kernel_constant(name):
+    import re
+    import youreditableavatar_amd
+    src = open(os.path.join(os.path.dirname(youreditableavatar_amd.__file__), "csrc", "tgs_hashgrid.hip")).read()
+    (value,) = re.findall(r"constexpr int " + name + r" = (\d+);", src)
+    return int(value)
+
+
+def test_the_launch_level_tables():
+    wide, thin, single, single_wide = (_tables(n) for n in LAUNCH_CONFIGS)
+    assert wide == thin and single == single_wide
+    assert [v.resolution for v in wide] == WIDE_RESOLUTIONS
+    assert [v.size for v in wide] == [8, 32, 64] + [128] * 13 and [v.dense for v in wide] == [True] * 4 + [False] * 12
+    assert abs(wide[15].scale - 101.37) < 0.01 and R.n_entries(wide) == 1768
+    assert [(v.scale, v.resolution, v.size, v.dense) for v in single] == [(2.0, 3, 32, True)]
+    assert all(8 * R.n_entries(R.level_table(R.CONFIGS[n])) < 16384 for n in LAUNCH_CONFIGS)                      # every table below 16 KB
+    assert [R.MLP[n] for n in LAUNCH_CONFIGS] == [(64, 4), (16, 1), (16, 2), (64, 4)]                            # H64 D4, H16 C32, C2 D2, C2 H64
+
+
+def test_the_launch_cases_are_what_the_issue_lists():
+    assert set(R.LAUNCH_CASES) == {("tiny", "many")} | {(c, s) for c in LAUNCH_CONFIGS for s in ("uniform", "runs")} | \
+        {("tiny", "runs"), ("odd", "runs"), ("tiny", "far"), ("odd", "far"), ("wide", "far")}
+    assert len(set(R.LAUNCH_CASES)) == len(R.LAUNCH_CASES) and R.LAUNCH_SETS == ("many", "runs", "far")
+    # many: more tiles than the fused backward has workgroups, the last tile partial and taken on a second trip
+    block, slabs = _kernel_constant("HG_BLOCK"), _kernel_constant("HG_MAX_SLABS")
+    many = R.points("tiny", "many")
+    assert len(many) == R.MANY == 262733 and len(many) > slabs * block and len(many) % block != 0 and len(many) % 256 != 0
+    assert -(-len(many) // block) - slabs == 3                                                                   # workgroups 0, 1 and 2 take two tiles
+    assert many.min() >= 0.0 and many.max() <= 1.0
+    # far
+    far = R.points("wide", "far")
+    assert len(far) == 2048 and np.abs(far[:256]).max() <= 4.0 and far[:256].min() < 0.0 and far[:256].max() > 1.0
+    assert np.abs(far[256:-3]).max() <= 1024.0 and (far[256:-3] < -512.0).any() and (far[256:-3] > 512.0).any()
+    assert far[-3].tolist() == [1024.0, -1024.0, 1024.0] and far[-2, 1] == np.nextafter(np.float32(1024.0), np.float32(np.inf)) and far[-1, 2] == -np.inf
+    valid = R.valid_rows(torch.tensor(far)).numpy()
+    assert valid[:-2].all() and not valid[-2:].any()
+    # the upstreams of the dynamic-range test
+    g = R.upstream("binades", (50, 4), "x")
+    big = np.abs(g).max(axis=1)
+    assert (big > 1.0).sum() == 1 and np.sort(big)[-2] <= 2.0 ** -20 and big.max() <= 2.0 ** 20
+    assert np.abs(R.upstream("denormal", (50, 4), "x")).max() == 2.0 ** -130
+
+
+@pytest.mark.parametrize("config_name", RUNS_CONFIGS)
+def test_the_runs_set_has_runs_of_every_kind(config_name):
+    x = R.points(config_name, "runs")
+    levels = R.level_table(R.CONFIGS[config_name])
+    valid = R.valid_rows(torch.tensor(x)).numpy()
+    assert 3000 <= len(x) <= 4000 and set((1, 2, 3, 5, 31, 33, 63, 64, 65, 127, 130, 200, 300)) <= set(R.RUN_LENGTHS)
+    nan_rows = np.flatnonzero(~valid)
+    assert len(nan_rows) == 2 and valid[nan_rows - 1].all() and valid[nan_rows + 1].all()                        # valid neighbours on both sides
+    zero_run = np.flatnonzero((x >= 0).all(axis=1) & (x < 0.5 / levels[-1].scale).all(axis=1))
+    assert len(zero_run) >= 10 and (np.diff(zero_run) <= 2).all() and zero_run[0] < nan_rows[1] < zero_run[-1]   # consecutive but for its NaN row
+    for l, lv in enumerate(levels):
+        cell = np.floor(np.where(valid[:, None], x, 0.5).astype(np.float64) * lv.scale + 0.5).astype(np.int64)
+        lengths, in_wave = R.run_lengths(cell, valid), R.run_lengths(cell, valid, 64)
+        print(f"{config_name}/runs level {l}: {len(set(lengths))} distinct run lengths up to {max(lengths)}, {len(set(in_wave))} inside the waves")
+        assert len(set(lengths)) >= 10 and max(lengths) > 64
+        assert len(set(in_wave)) >= 10 and max(in_wave) == 64 and min(in_wave) == 1                               # what WaveRuns.end takes: mixed lengths
+        assert not cell[zero_run].any()                                                                           # the cell-zero run, at every level
+    r = nan_rows[0]                                                                                               # the NaN row strictly inside a run of >= 65
+    finest = np.floor(x.astype(np.float64) * levels[-1].scale + 0.5)
+    same = np.flatnonzero((finest == finest[r - 1]).all(axis=1))
+    assert len(same) >= 65 - 1 and same.min() < r < same.max()
+
+
+@pytest.mark.parametrize("config_name,set_name", R.LAUNCH_CASES)
+def test_the_kink_cap_of_the_launch_cases(config_name, set_name):
+    test_the_kink_cap(config_name, set_name)
+
+
+@pytest.mark.parametrize("config_name,set_name", R.LAUNCH_CASES)
+def test_the_magnitude_sums_dominate_the_results(config_name, set_name):
+    c, m = R.case(config_name, set_name), R.magnitudes(config_name, set_name)
+    v, ref = c["valid"], c["enc"]["ref64"]
+    for key, rows in (("enc", v), ("d_x", v), ("d_params", slice(None))):
+        assert np.isfinite(m[key]).all() and (np.abs(ref[key][rows]) <= m[key][rows] * (1.0 + 1e-12)).all(), key
+    assert not m["enc"][~v].any() and not m["d_x"][~v].any()
+
+
+@pytest.mark.parametrize("config_name", ["tiny", "wide"])
+@pytest.mark.parametrize("set_name", R.LAUNCH_SETS)
+def test_the_restatement_against_a_slow_loop_on_the_launch_sets(config_name, set_name):
+    levels, P = R.level_table(R.CONFIGS[config_name]), R.table(config_name)
+    x = R.points(config_name, set_name)
+    x = np.concatenate([x[:64], x[-3:]]) if set_name == "far" else x[:64]                                         # far's special rows too
+    fast, _ = R.encode(torch.tensor(x).double(), torch.tensor(P).double(), levels)
+    slow = R.encode_slow(x, P, levels)
+    assert np.array_equal(np.isnan(fast.numpy()), np.isnan(slow))
+    np.testing.assert_allclose(np.nan_to_num(fast.numpy()), np.nan_to_num(slow), rtol=0, atol=1e-14)
+    if set_name == "far":
+        assert np.isfinite(slow[-3]).all() and np.isnan(slow[-2:]).all() and slow[-3].any()
