@@ -1,6 +1,6 @@
 """CPU: the tetrahedral grid's passes at the C ABI and in youreditableavatar_amd.tet_grid (no device needed): the header declares and the
 cross-compiled library exports the entry points, the header states the rules, the signature table matches the header, the shared pieces live in
-one header, the workspace sizes are sane, bad arguments are refused before any device call, and the module refuses what it cannot serve."""
+their headers, the workspace sizes are sane, bad arguments are refused before any device call, and the module refuses what it cannot serve."""
 import ctypes
 import os
 import re
@@ -61,17 +61,45 @@ def test_header_declares_and_library_exports_the_entry_points():
 
 
 def test_the_shared_pieces_have_one_copy():
-    """the scans, the row load, the run sort and the binary search: tgs_tet_common.hpp, included by both kernel files"""
-    common = open(os.path.join(CSRC, "tgs_tet_common.hpp")).read()
-    for source in ("tgs_marching_tets.hip", "tgs_tet_grid.hip"):
-        text = open(os.path.join(CSRC, source)).read()
-        assert '#include "tgs_tet_common.hpp"' in text, source
-        for once in ("void k_mt_scan_sums", "void k_mt_scan_tile", "uint32_t mt_block_escan(", "void mt_load_tet(", "void mt_sort_run(", "long long mt_sort_unique_run(", "long long mt_search_run(", "void mt_scan("):
-            assert once in common and once not in text, (source, once)
-        assert ("mt_sort_run(" in text or "mt_sort_unique_run(" in text) and "mt_search_run(" in text and "mt_scan(" in text, source
-        assert "atomicCAS" not in text or source == "tgs_marching_tets.hip"  # the subdivision has no hash table
+    """the scans, the run bounds, the run sort and the binary search: tgs_runs.hpp; the edge set, its fill and its sort: tgs_edge_set.hpp; the row
+    load: tgs_tet_common.hpp.  Each definition stands once, in its header, and in none of the four kernel files of the geometry stage"""
+    read = lambda name: open(os.path.join(CSRC, name)).read()
+    shared = {
+        "tgs_runs.hpp": ("size_t run_scan_scratch(", "size_t run_blocks(", "dim3 run_grid(", "uint32_t run_block_escan(", "void k_run_scan_sums(", "void k_run_scan_tile(",
+                         "void run_scan(", "size_t run_start(", "Run run_bounds(", "void run_sort(", "long long run_sort_unique(", "long long run_search("),
+        "tgs_edge_set.hpp": ("EDGE_EMPTY = ", "unsigned long long edge_key(", "unsigned long long edge_hash(", "0xbf58476d1ce4e5b9ull", "size_t edge_insert(", "size_t edge_find(",
+                             "void k_edge_fill(", "void k_edge_sort("),
+        "tgs_tet_common.hpp": ("void mt_load_tet(", "bool mt_in_range(", "bool mt_aligned("),
+    }
+    kernel_files = {name: read(name) for name in ("tgs_marching_tets.hip", "tgs_tet_grid.hip", "tgs_mesh_geom.hip", "tgs_mesh_aa.hip")}
+    for header, definitions in shared.items():
+        text = read(header)
+        assert text.count("__global__") == text.count("static __global__"), header    # a kernel in a header is static: one copy per translation unit, no relocatable device code
+        for once in definitions:
+            assert text.count(once) == 1, (header, once)
+            for other, code in {**{h: read(h) for h in set(shared) - {header}}, **kernel_files}.items():
+                assert once not in code, (other, once)
+    assert '#include "tgs_runs.hpp"' in read("tgs_tet_common.hpp") and '#include "tgs_runs.hpp"' in read("tgs_edge_set.hpp")
+    includes = {"tgs_marching_tets.hip": ("tgs_tet_common.hpp", "tgs_edge_set.hpp"), "tgs_tet_grid.hip": ("tgs_tet_common.hpp",), "tgs_mesh_geom.hip": ("tgs_edge_set.hpp",),
+                "tgs_mesh_aa.hip": ("tgs_edge_set.hpp",)}
+    for source, text in kernel_files.items():
+        for header in includes[source]:
+            assert f'#include "{header}"' in text, (source, header)
+        assert "atomicCAS" not in text, source                               # the probe loop is the edge set's
+        for old in ("mt_scan", "mg_scan", "_block_escan(uint32_t", "mt_sort_run", "mt_sort_unique_run", "mt_search_run", "mg_run(", "mg_hash", "mt_hash", "topo_hash", "k_mg_edge_fill",
+                    "k_mg_edge_sort", "k_mt_fill", "k_mt_sort_runs", "MT_EMPTY", "MG_EMPTY", "TOPO_EMPTY", "end[v - 1]", "run[v - 1]", "run[a - 1]", "run_b[v - 1]"):
+            assert old not in text, (source, old)
         for float_atomic in ("atomicAdd(float", "unsafeAtomicAdd", "atomicAdd_system"):
             assert float_atomic not in text, (source, float_atomic)
+    assert "atomicCAS" in read("tgs_edge_set.hpp")
+    for source in ("tgs_marching_tets.hip", "tgs_mesh_geom.hip"):
+        text = kernel_files[source]
+        assert "edge_insert(" in text and "k_edge_fill," in text and "k_edge_sort," in text and "run_scan(" in text and "run_bounds(" in text and "run_sort(" in text, source
+    aa, grid = kernel_files["tgs_mesh_aa.hip"], kernel_files["tgs_tet_grid.hip"]
+    assert "edge_insert(" in aa and "edge_find(" in aa and "edge_key(" in aa
+    assert "run_search(" in kernel_files["tgs_marching_tets.hip"]
+    assert "run_sort_unique(" in grid and "run_search(" in grid and "run_scan(" in grid and "run_bounds(" in grid and "run_start(" in grid
+    assert "tgs_edge_set.hpp" not in grid and "edge_insert" not in grid and "edge_find" not in grid                # the subdivision has no hash table
 
 
 def test_workspace_sizes():

@@ -1,26 +1,24 @@
 """The host layer under ``mesh_raster``, ``mesh_raster_aa`` and ``mesh_raster_grad`` (private: those three are what callers import).
 
-Written once here: the ctypes signatures of the eleven ``tgs_mesh_*`` entry points (``SIGNATURES``, ``declare``); the argument checks of the four calls
+The pieces every geometry module shares (``declare``, the guard, the raw stream, the device check) are ``_host``'s.  Written once here: the ctypes signatures of the eleven ``tgs_mesh_*`` entry points (``SIGNATURES``, ``declare``); the argument checks of the four calls
 (``rasterize``, ``interpolate``, ``antialias``, ``topology``: types, shapes and dtypes, then ``tri``, the gradient refusal, resolution or extent, the device
 last), each returning the ``Call`` record forward and backward work from; the broadcast rule (``image_of``); N images through one native function
 (``run_images``); where a topology comes from (``topology_of``); the order of ``sum_images``.
 """
 from __future__ import annotations
 
-import contextlib
-import ctypes as C
 import functools
 from collections import namedtuple
 from typing import Callable, Optional, Sequence
 
 import torch
 
-from .diff_gaussian_rasterization import _C as _rast_c
+from . import _host
+from ._host import _F, _I, _L, _P, _Z, NO_GUARD as _NO_GUARD, need_device as _need_device, ok as _ok, raw_stream as _raw_stream
 
 MAX_FACES = (1 << 24) - 1          # the triangle ID travels in a float
 MAX_RESOLUTION = 8192
 
-_P, _I, _L, _Z, _F = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
 SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_raster.h declares them (every pointer is a c_void_p)
     "tgs_mesh_workspace_bytes": (_Z, [_I, _I, _I]),
     "tgs_mesh_rasterize": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _Z]),
@@ -36,38 +34,21 @@ SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_r
 }
 
 
-def declare(lib: C.CDLL) -> C.CDLL:
+def declare(lib):
     """applies ``SIGNATURES`` to a handle of the native library -> the handle"""
-    for name, (restype, argtypes) in SIGNATURES.items():
-        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
-    return lib
+    return _host.declare(lib, SIGNATURES)
 
 
-_lib = declare(_rast_c._lib)                                                    # once: the three modules work on this handle
-# torch.cuda.current_stream(dev).cuda_stream builds a Stream object per call (1.9 us of a 17 us call); torch has the number itself, under a private name
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (
-    lambda index: torch.cuda.current_stream(index).cuda_stream)                # (the public way, should the private name go)
+_lib = declare(_host.lib)                                                       # once: the three modules work on this handle
 
 
 # A checked call: N images of H x W pixels, V vertices, C channels, F faces, on dev; per_image: attr / pos has a row per image (its gradient is stacked, not summed)
 Call = namedtuple("Call", "N H W V C F dev per_image", defaults=(False,))
-_NO_GUARD = contextlib.nullcontext()
 
 
 def _refuse_grad(name: str, t: torch.Tensor) -> None:
     if t.requires_grad:
         raise RuntimeError(f"youreditableavatar_amd.mesh_raster is forward only: `{name}` requires a gradient and none would flow (pass {name}.detach() if that is intended)")
-
-
-def _need_device(**tensors) -> torch.device:
-    """checked last, behind everything that can be said about the arguments without a device -> the first tensor's device"""
-    for name, t in tensors.items():
-        if not t.is_cuda:
-            raise RuntimeError(f"youreditableavatar_amd.mesh_raster has no CPU path: {name} must be on a HIP device")
-    devs = {t.device for t in tensors.values()}
-    if len(devs) != 1:
-        raise RuntimeError("all tensors must be on one device, got " + ", ".join(f"{n} on {t.device}" for n, t in tensors.items()))
-    return next(iter(tensors.values())).device
 
 
 def _check_tri(tri: torch.Tensor) -> None:
@@ -100,7 +81,7 @@ def rasterize(pos: torch.Tensor, tri: torch.Tensor, resolution: Sequence[int], v
         lo, hi = (int(x) for x in torch.aminmax(tri))
         if lo < 0 or hi >= V:
             raise ValueError(f"tri holds vertex indices in [{lo}, {hi}]; pos has {V} vertices")
-    return Call(N, H, W, V, 4, F, _need_device(pos=pos, tri=tri), True)
+    return Call(N, H, W, V, 4, F, _need_device("mesh_raster", pos=pos, tri=tri), True)
 
 
 def interpolate(attr: torch.Tensor, rast: torch.Tensor, tri: torch.Tensor) -> Call:
@@ -112,7 +93,7 @@ def interpolate(attr: torch.Tensor, rast: torch.Tensor, tri: torch.Tensor) -> Ca
     _check_tri(tri)
     _refuse_grad("attr", attr)
     _refuse_grad("rast", rast)
-    _need_device(attr=attr, rast=rast, tri=tri)
+    _need_device("mesh_raster", attr=attr, rast=rast, tri=tri)
     return Call(N, H, W, int(attr.shape[-2]), int(attr.shape[-1]), int(tri.shape[0]), rast.device, attr.dim() == 3 and attr.shape[0] == N and N != 1)
 
 
@@ -134,7 +115,7 @@ def antialias(color: torch.Tensor, rast: torch.Tensor, pos: torch.Tensor, tri: t
             raise RuntimeError(f"expected the int32 [{F},3] topology of antialias_construct_topology_hash(tri) as topology_hash, got {got}")
     for name, t in (("color", color), ("rast", rast), ("pos", pos)):
         _refuse_grad(name, t)
-    dev = _need_device(color=color, rast=rast, pos=pos, tri=tri)
+    dev = _need_device("mesh_raster", color=color, rast=rast, pos=pos, tri=tri)
     if topology_hash is not None and topology_hash.device != dev:
         raise RuntimeError(f"topology_hash is on {topology_hash.device}, tri on {dev}: the topology is built on tri's device")
     return Call(N, H, W, int(pos.shape[-2]), int(color.shape[-1]), F, dev, pos.dim() == 3 and pos.shape[0] == N and N != 1)
@@ -145,7 +126,7 @@ def topology(tri: torch.Tensor, num_vertices: Optional[int]) -> Call:
     V = (1 << 31) - 1 if num_vertices is None else int(num_vertices)        # only tri is known: every non-negative index names a vertex
     if V < 0:
         raise RuntimeError(f"num_vertices must be >= 0, got {num_vertices}")
-    return Call(1, 0, 0, V, 0, int(tri.shape[0]), _need_device(tri=tri))
+    return Call(1, 0, 0, V, 0, int(tri.shape[0]), _need_device("mesh_raster", tri=tri))
 
 
 def image_of(t: torch.Tensor, n: int, N: int) -> torch.Tensor:
@@ -168,7 +149,7 @@ def run_images(fn: Callable, call: Call, workspace: Optional[Callable[[Call], in
             part = image_of(shared, n, call.N).contiguous()                     # (alive over the call)
             r = fn(st, *args(n, part.data_ptr()), *tail)
             if r < 0:
-                raise _rast_c._err(r)
+                _ok(r)
 
 
 def grad_workspace_bytes(call: Call) -> int:

@@ -9,25 +9,25 @@
 //                                code into a byte per tetrahedron, valid_tets, and the workgroup's number of one- and two-triangle tetrahedra),
 //                                two scans over the workgroup counts -> counts[0] = n_one, counts[1] = n_two, counts[2] = the index flag.
 //   tgs_marching_tets_edges      the table is sized from n_one, n_two (3 n_one + 4 n_two crossing edges before dedupe).  k_mt_insert (the
-//                                crossing edges of every valid tetrahedron into an open-addressing table keyed by (min << 32 | max), integer CAS;
-//                                whoever claims a free slot adds one to the count of the edge's min vertex), one scan over N -> the run of every
-//                                vertex's edges, counts[3] = M.  The hash only dedupes: no output reads a slot number.
-//   tgs_marching_tets_emit       k_mt_fill (every key to its vertex's run, through a cursor), k_mt_sort_runs (one lane per vertex sorts its run by
-//                                the max index: now interp_v is in ascending (min, max) order whatever the cursors did), k_mt_verts (one lane per
-//                                edge), k_mt_faces (one lane per tetrahedron: the ranks among the one- and the two-triangle tetrahedra from a
-//                                workgroup scan on top of the scanned workgroup counts; every corner's edge is found by a binary search in its min
-//                                vertex's run).
+//                                crossing edges of every valid tetrahedron into the edge set of tgs_edge_set.hpp; whoever claims a free slot
+//                                adds one to the count of the edge's min vertex), one scan over N (tgs_runs.hpp) -> the run of every vertex's
+//                                edges, counts[3] = M.
+//   tgs_marching_tets_emit       k_edge_fill and k_edge_sort (tgs_edge_set.hpp: every key to its vertex's run, through a cursor, then one lane
+//                                per vertex sorts its run by the max index: now interp_v is in ascending (min, max) order whatever the cursors
+//                                did), k_mt_verts (one lane per edge), k_mt_faces (one lane per tetrahedron: the ranks among the one- and the
+//                                two-triangle tetrahedra from a workgroup scan on top of the scanned workgroup counts; every corner's edge is
+//                                found by a binary search in its min vertex's run).
 // tgs_marching_tets_backward is a gather per grid row: k_mt_grad_count (edges per min and per max vertex), two scans, k_mt_grad_fill (edge
 // numbers into the max side's runs), k_mt_grad (one lane per grid row: its run of interp_v as the min end, then its max-side list sorted by edge
 // number, added in double and rounded once).
 //
 // The case table is written as the tetrahedron's corner pairs: a triangle corner is the crossing of the edge between local corners i and j, one
 // byte 0xij, three bytes per triangle, the first triangle in the high half.  tests/golden/ref_mt_fixture.npz (cases16) pins it.
-#include "tgs_tet_common.hpp"                                           // the scans, the row load, the run sort and search
+#include "tgs_tet_common.hpp"                                           // the row load; with it tgs_runs.hpp: the scans, the run bounds, sort and search
+#include "tgs_edge_set.hpp"                                             // the edge set, its fill and its sort
 
 namespace tgs {
 
-constexpr unsigned long long MT_EMPTY = ~0ull;                          // no key: min <= max < 2^31 never gives all ones
 constexpr long long MT_MAX_CROSSING = 1ll << 33;                        // 4 F with F < 2^31
 
 #define MT_TRI(a, b, c) ((unsigned long long)(((a) << 16) | ((b) << 8) | (c)))
@@ -57,15 +57,15 @@ struct MtWork {
     uint8_t* code;                        // [F] the case code of a valid tetrahedron, 0 otherwise
     uint32_t* blk_one;                    // [ceil(F / 256) + 1] one-triangle tetrahedra per workgroup of k_mt_classify; scanned (exclusive)
     uint32_t* blk_two;                    // likewise, two-triangle
-    uint32_t* run;                        // [N + 1] crossing edges per min vertex; scanned: run[v] is where v's edges start; after k_mt_fill where they end
+    uint32_t* run;                        // [N + 1] crossing edges per min vertex; scanned: run[v] is where v's edges start; after k_edge_fill where they end
     uint32_t* scan;                       // scratch of the scans
 };
 __host__ __device__ inline size_t mt_carve(MtWork& w, char* base, size_t N, size_t F)
 {
     char* p = base;
-    const size_t big = N + 1 > mt_blocks(F) + 1 ? N + 1 : mt_blocks(F) + 1;
-    carve(p, w.bits, (N + 63) / 64 + 1); carve(p, w.code, F + 1); carve(p, w.blk_one, mt_blocks(F) + 1); carve(p, w.blk_two, mt_blocks(F) + 1);
-    carve(p, w.run, N + 1); carve(p, w.scan, mt_scan_scratch(big));
+    const size_t big = N + 1 > run_blocks(F) + 1 ? N + 1 : run_blocks(F) + 1;
+    carve(p, w.bits, (N + 63) / 64 + 1); carve(p, w.code, F + 1); carve(p, w.blk_one, run_blocks(F) + 1); carve(p, w.blk_two, run_blocks(F) + 1);
+    carve(p, w.run, N + 1); carve(p, w.scan, run_scan_scratch(big));
     return (size_t)(p - base) + 256;
 }
 __host__ __device__ inline size_t mt_table_capacity(long long n_crossing)
@@ -84,21 +84,14 @@ struct MtGradWork {
 __host__ __device__ inline size_t mt_grad_carve(MtGradWork& w, char* base, size_t N, size_t M)
 {
     char* p = base;
-    carve(p, w.run_a, N + 1); carve(p, w.run_b, N + 1); carve(p, w.list_b, M + 1); carve(p, w.scan, mt_scan_scratch(N + 1));
+    carve(p, w.run_a, N + 1); carve(p, w.run_b, N + 1); carve(p, w.list_b, M + 1); carve(p, w.scan, run_scan_scratch(N + 1));
     return (size_t)(p - base) + 256;
 }
 
-__device__ __forceinline__ unsigned long long mt_hash(unsigned long long k)       // (splitmix64's finaliser, as the mesh topology's table)
-{
-    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27; k *= 0x94d049bb133111ebull;
-    return k ^ (k >> 31);
-}
-
 // ---- forward ----
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_signs(int N, const float* __restrict__ sdf, unsigned long long* __restrict__ bits)
+__global__ __launch_bounds__(RUN_BLOCK) void k_mt_signs(int N, const float* __restrict__ sdf, unsigned long long* __restrict__ bits)
 {
-    const size_t v = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t v = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     const bool inside = v < (size_t)N && sdf[v] > 0.f;                  // NaN and 0 are outside
     const unsigned long long word = __ballot(inside);
     if ((threadIdx.x & 63) == 0 && v < (size_t)N) bits[v >> 6] = word;
@@ -108,12 +101,12 @@ __device__ __forceinline__ uint32_t mt_bit(const unsigned long long* __restrict_
     return (uint32_t)(bits[v >> 6] >> (v & 63)) & 1u;
 }
 template <typename Idx>
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_classify(int N, int F, const Idx* __restrict__ tet, const unsigned long long* __restrict__ bits,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mt_classify(int N, int F, const Idx* __restrict__ tet, const unsigned long long* __restrict__ bits,
                                                           uint8_t* __restrict__ code, uint8_t* __restrict__ valid, uint32_t* __restrict__ blk_one,
                                                           uint32_t* __restrict__ blk_two, long long* __restrict__ counts)
 {
     __shared__ uint32_t lds[4];
-    const size_t f = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t f = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     uint32_t c = 0;
     if (f < (size_t)F) {
         long long t[4];
@@ -130,15 +123,15 @@ __global__ __launch_bounds__(MT_BLOCK) void k_mt_classify(int N, int F, const Id
     const bool two = __popc(c) == 2;
     const uint32_t pack = c == 0 ? 0u : two ? 0x10000u : 1u;            // both counts in one scan: at most 256 each
     uint32_t total;
-    mt_block_escan(pack, total, lds);
+    run_block_escan(pack, total, lds);
     if (threadIdx.x == 0) { blk_one[blockIdx.x] = total & 0xffffu; blk_two[blockIdx.x] = total >> 16; }
 }
 
 template <typename Idx>
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_insert(int N, int F, const Idx* __restrict__ tet, const uint8_t* __restrict__ code, size_t cap,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mt_insert(int N, int F, const Idx* __restrict__ tet, const uint8_t* __restrict__ code, size_t cap,
                                                         unsigned long long* __restrict__ keys, uint32_t* __restrict__ run)
 {
-    const size_t f = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t f = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (f >= (size_t)F) return;
     const uint32_t c = code[f];
     if (c == 0) return;
@@ -151,47 +144,18 @@ __global__ __launch_bounds__(MT_BLOCK) void k_mt_insert(int N, int F, const Idx*
         for (int j = i + 1; j < 4; j++) {
             if ((((c >> i) ^ (c >> j)) & 1u) == 0) continue;             // both inside or both outside (an edge of equal indices is always that)
             const long long a = t[i] < t[j] ? t[i] : t[j], b = t[i] < t[j] ? t[j] : t[i];
-            const unsigned long long key = ((unsigned long long)a << 32) | (unsigned long long)b;
-            size_t slot = (size_t)mt_hash(key) & (cap - 1);
-            for (size_t probe = 0; probe < cap; probe++) {               // (the table is never full: it ends at the key or at a free slot)
-                const unsigned long long prev = atomicCAS(&keys[slot], MT_EMPTY, key);
-                if (prev == MT_EMPTY) { atomicAdd(&run[a], 1u); break; }
-                if (prev == key) break;
-                slot = (slot + 1) & (cap - 1);
-            }
+            bool claimed;
+            edge_insert(keys, cap, edge_key(a, b), claimed);
+            if (claimed) atomicAdd(&run[a], 1u);
         }
 }
 
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_fill(int N, long long M, size_t cap, const unsigned long long* __restrict__ keys, uint32_t* __restrict__ run,
-                                                      long long* __restrict__ interp_v)
-{
-    const size_t s = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
-    if (s >= cap) return;
-    const unsigned long long key = keys[s];
-    if (key == MT_EMPTY) return;
-    const long long a = (long long)(key >> 32), b = (long long)(key & 0xffffffffull);
-    if (a >= N) return;
-    const long long p = atomicAdd(&run[a], 1u);                         // the cursor: run[a] ends at the start of a + 1's run
-    if (p < M) { interp_v[2 * p] = a; interp_v[2 * p + 1] = b; }
-}
-
-// run[v] is now the END of v's run (the start of v + 1's); v's edges are sorted by their max index
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_sort_runs(int N, long long M, const uint32_t* __restrict__ run, long long* __restrict__ interp_v)
-{
-    const size_t v = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
-    if (v >= (size_t)N) return;
-    const long long lo = v ? run[v - 1] : 0;
-    long long hi = run[v];
-    if (hi > M) hi = M;
-    mt_sort_run(interp_v + 1, 2, lo, hi);
-}
-
 // v = pos[a] w_a + pos[b] w_b with w_a = (-sdf[b]) / D, w_b = sdf[a] / D, D = sdf[a] + (-sdf[b]); every operation rounded on its own
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_verts(int N, long long M, const float* __restrict__ pos, const float* __restrict__ sdf,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mt_verts(int N, long long M, const float* __restrict__ pos, const float* __restrict__ sdf,
                                                        const long long* __restrict__ interp_v, float* __restrict__ verts)
 {
 #pragma clang fp contract(off)
-    const long long e = (long long)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const long long e = (long long)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (e >= M) return;
     const long long a = interp_v[2 * e], b = interp_v[2 * e + 1];
     if ((unsigned long long)a >= (unsigned long long)N || (unsigned long long)b >= (unsigned long long)N) return;
@@ -205,24 +169,23 @@ __global__ __launch_bounds__(MT_BLOCK) void k_mt_verts(int N, long long M, const
 // the row of interp_v that holds (a, b), -1 if none (never, for a crossing edge of this call sequence)
 __device__ __forceinline__ long long mt_find(int N, long long M, const uint32_t* __restrict__ run, const long long* __restrict__ interp_v, long long a, long long b)
 {
-    long long lo = a ? run[a - 1] : 0, hi = run[a];
-    if (hi > M) hi = M;
-    return mt_search_run(interp_v + 1, 2, lo, hi, b);
+    const Run r = run_bounds(run, (size_t)a, (size_t)M);
+    return run_search(interp_v + 1, 2, (long long)r.lo, (long long)r.hi, b);
 }
 
 template <typename Idx>
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_faces(int N, int F, long long M, long long n_one, long long T, const Idx* __restrict__ tet,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mt_faces(int N, int F, long long M, long long n_one, long long T, const Idx* __restrict__ tet,
                                                        const uint8_t* __restrict__ code, const uint32_t* __restrict__ blk_one, const uint32_t* __restrict__ blk_two,
                                                        const uint32_t* __restrict__ run, const long long* __restrict__ interp_v,
                                                        long long* __restrict__ faces, long long* __restrict__ face_to_tet)
 {
     __shared__ uint32_t lds[4];
-    const size_t f = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t f = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     const uint32_t c = f < (size_t)F ? code[f] : 0u;
     const bool two = __popc(c) == 2;
     const uint32_t pack = c == 0 ? 0u : two ? 0x10000u : 1u;
     uint32_t total;
-    const uint32_t before = mt_block_escan(pack, total, lds);
+    const uint32_t before = run_block_escan(pack, total, lds);
     if (c == 0) return;
     long long t[4];
     mt_load_tet(tet, f, t);
@@ -245,18 +208,18 @@ __global__ __launch_bounds__(MT_BLOCK) void k_mt_faces(int N, int F, long long M
 }
 
 // ---- backward ----
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_grad_count(int N, long long M, const long long* __restrict__ interp_v, uint32_t* __restrict__ run_a, uint32_t* __restrict__ run_b)
+__global__ __launch_bounds__(RUN_BLOCK) void k_mt_grad_count(int N, long long M, const long long* __restrict__ interp_v, uint32_t* __restrict__ run_a, uint32_t* __restrict__ run_b)
 {
-    const long long e = (long long)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const long long e = (long long)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (e >= M) return;
     const long long a = interp_v[2 * e], b = interp_v[2 * e + 1];
     if ((unsigned long long)a >= (unsigned long long)N || (unsigned long long)b >= (unsigned long long)N) return;
     atomicAdd(&run_a[a], 1u);
     atomicAdd(&run_b[b], 1u);
 }
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_grad_fill(int N, long long M, const long long* __restrict__ interp_v, uint32_t* __restrict__ run_b, uint32_t* __restrict__ list_b)
+__global__ __launch_bounds__(RUN_BLOCK) void k_mt_grad_fill(int N, long long M, const long long* __restrict__ interp_v, uint32_t* __restrict__ run_b, uint32_t* __restrict__ list_b)
 {
-    const long long e = (long long)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const long long e = (long long)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (e >= M) return;
     const long long a = interp_v[2 * e], b = interp_v[2 * e + 1];
     if ((unsigned long long)a >= (unsigned long long)N || (unsigned long long)b >= (unsigned long long)N) return;
@@ -283,24 +246,19 @@ __device__ __forceinline__ void mt_grad_edge(int N, const float* __restrict__ po
     }
     acc.s += dot / D;
 }
-__global__ __launch_bounds__(MT_BLOCK) void k_mt_grad(int N, long long M, const float* __restrict__ pos, const float* __restrict__ sdf,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mt_grad(int N, long long M, const float* __restrict__ pos, const float* __restrict__ sdf,
                                                       const long long* __restrict__ interp_v, const float* __restrict__ g_verts, const uint32_t* __restrict__ run_a,
                                                       const uint32_t* __restrict__ run_b, uint32_t* __restrict__ list_b, float* __restrict__ d_pos, float* __restrict__ d_sdf)
 {
-    const size_t v = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t v = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (v >= (size_t)N) return;
     MtAcc acc = {{0.0, 0.0, 0.0}, 0.0};
     long long lo = run_a[v], hi = run_a[v + 1];
     if (hi > M) hi = M;
     for (long long e = lo; e < hi; e++) mt_grad_edge(N, pos, sdf, interp_v, g_verts, e, (long long)v, true, acc);
-    lo = v ? run_b[v - 1] : 0; hi = run_b[v];                            // (the fill's cursors: ends)
-    if (hi > M) hi = M;
-    for (long long i = lo + 1; i < hi; i++) {                            // ascending edge number, whatever the cursors did
-        const uint32_t x = list_b[i];
-        long long j = i;
-        for (; j > lo && list_b[j - 1] > x; j--) list_b[j] = list_b[j - 1];
-        list_b[j] = x;
-    }
+    const Run r = run_bounds(run_b, v, (size_t)M);                       // (the fill's cursors: ends)
+    lo = (long long)r.lo; hi = (long long)r.hi;
+    run_sort(list_b, 1, lo, hi);                                        // ascending edge number, whatever the cursors did
     for (long long i = lo; i < hi; i++) mt_grad_edge(N, pos, sdf, interp_v, g_verts, (long long)list_b[i], (long long)v, false, acc);
     if (d_pos) { d_pos[3 * v] = (float)acc.p[0]; d_pos[3 * v + 1] = (float)acc.p[1]; d_pos[3 * v + 2] = (float)acc.p[2]; }
     if (d_sdf) d_sdf[v] = (float)acc.s;
@@ -336,12 +294,12 @@ int tgs_marching_tets_classify(void* stream, int N, int F, const float* sdf, con
         return set_error(TGS_ERR_INVALID, "tgs_marching_tets_classify: workspace smaller than tgs_marching_tets_workspace_bytes(N, F)");
     if (hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), st) != hipSuccess) return hip_status("tgs_marching_tets_classify");
     if (F == 0) return TGS_OK;
-    if (N > 0) hipLaunchKernelGGL(k_mt_signs, mt_grid((size_t)N), dim3(MT_BLOCK), 0, st, N, sdf, w.bits);
+    if (N > 0) hipLaunchKernelGGL(k_mt_signs, run_grid((size_t)N), dim3(RUN_BLOCK), 0, st, N, sdf, w.bits);
     long long* cnt = (long long*)counts;
-    if (tet_is_int64) hipLaunchKernelGGL(k_mt_classify<long long>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (const long long*)tet, w.bits, w.code, valid_tets, w.blk_one, w.blk_two, cnt);
-    else              hipLaunchKernelGGL(k_mt_classify<int>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (const int*)tet, w.bits, w.code, valid_tets, w.blk_one, w.blk_two, cnt);
-    mt_scan(st, w.blk_one, mt_blocks((size_t)F), w.scan, cnt + 0);
-    mt_scan(st, w.blk_two, mt_blocks((size_t)F), w.scan, cnt + 1);
+    if (tet_is_int64) hipLaunchKernelGGL(k_mt_classify<long long>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (const long long*)tet, w.bits, w.code, valid_tets, w.blk_one, w.blk_two, cnt);
+    else              hipLaunchKernelGGL(k_mt_classify<int>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (const int*)tet, w.bits, w.code, valid_tets, w.blk_one, w.blk_two, cnt);
+    run_scan(st, w.blk_one, run_blocks((size_t)F), w.scan, cnt + 0);
+    run_scan(st, w.blk_two, run_blocks((size_t)F), w.scan, cnt + 1);
     return hip_status("tgs_marching_tets_classify");
 }
 
@@ -363,9 +321,9 @@ int tgs_marching_tets_edges(void* stream, int N, int F, const void* tet, int tet
     unsigned long long* keys = (unsigned long long*)(((uintptr_t)table + 255) & ~(uintptr_t)255);
     if (hipMemsetAsync(keys, 0xff, cap * sizeof(unsigned long long), st) != hipSuccess || hipMemsetAsync(w.run, 0, ((size_t)N + 1) * sizeof(uint32_t), st) != hipSuccess)
         return hip_status("tgs_marching_tets_edges");
-    if (tet_is_int64) hipLaunchKernelGGL(k_mt_insert<long long>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (const long long*)tet, w.code, cap, keys, w.run);
-    else              hipLaunchKernelGGL(k_mt_insert<int>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (const int*)tet, w.code, cap, keys, w.run);
-    mt_scan(st, w.run, (size_t)N + 1, w.scan, (long long*)counts + 3);
+    if (tet_is_int64) hipLaunchKernelGGL(k_mt_insert<long long>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (const long long*)tet, w.code, cap, keys, w.run);
+    else              hipLaunchKernelGGL(k_mt_insert<int>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (const int*)tet, w.code, cap, keys, w.run);
+    run_scan(st, w.run, (size_t)N + 1, w.scan, (long long*)counts + 3);
     return hip_status("tgs_marching_tets_edges");
 }
 
@@ -387,14 +345,14 @@ int tgs_marching_tets_emit(void* stream, int N, int F, const float* pos, const f
     const unsigned long long* keys = (const unsigned long long*)(((uintptr_t)table + 255) & ~(uintptr_t)255);
     const long long T = n_one + 2 * n_two;
     long long* iv = (long long*)interp_v;
-    hipLaunchKernelGGL(k_mt_fill, mt_grid(cap), dim3(MT_BLOCK), 0, st, N, (long long)M, cap, keys, w.run, iv);
-    hipLaunchKernelGGL(k_mt_sort_runs, mt_grid((size_t)N), dim3(MT_BLOCK), 0, st, N, (long long)M, (const uint32_t*)w.run, iv);
-    hipLaunchKernelGGL(k_mt_verts, mt_grid((size_t)M), dim3(MT_BLOCK), 0, st, N, (long long)M, pos, sdf, (const long long*)iv, verts);
+    hipLaunchKernelGGL(k_edge_fill, run_grid(cap), dim3(RUN_BLOCK), 0, st, N, (long long)M, cap, keys, w.run, iv);
+    hipLaunchKernelGGL(k_edge_sort, run_grid((size_t)N), dim3(RUN_BLOCK), 0, st, N, (long long)M, (const uint32_t*)w.run, iv);
+    hipLaunchKernelGGL(k_mt_verts, run_grid((size_t)M), dim3(RUN_BLOCK), 0, st, N, (long long)M, pos, sdf, (const long long*)iv, verts);
     if (tet_is_int64)
-        hipLaunchKernelGGL(k_mt_faces<long long>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (long long)M, (long long)n_one, T, (const long long*)tet, (const uint8_t*)w.code,
+        hipLaunchKernelGGL(k_mt_faces<long long>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (long long)M, (long long)n_one, T, (const long long*)tet, (const uint8_t*)w.code,
                            (const uint32_t*)w.blk_one, (const uint32_t*)w.blk_two, (const uint32_t*)w.run, (const long long*)iv, (long long*)faces, (long long*)face_to_tet_idx);
     else
-        hipLaunchKernelGGL(k_mt_faces<int>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (long long)M, (long long)n_one, T, (const int*)tet, (const uint8_t*)w.code,
+        hipLaunchKernelGGL(k_mt_faces<int>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (long long)M, (long long)n_one, T, (const int*)tet, (const uint8_t*)w.code,
                            (const uint32_t*)w.blk_one, (const uint32_t*)w.blk_two, (const uint32_t*)w.run, (const long long*)iv, (long long*)faces, (long long*)face_to_tet_idx);
     return hip_status("tgs_marching_tets_emit");
 }
@@ -425,11 +383,11 @@ int tgs_marching_tets_backward(void* stream, int N, int64_t M, const float* pos,
     if (hipMemsetAsync(w.run_a, 0, ((size_t)N + 1) * sizeof(uint32_t), st) != hipSuccess || hipMemsetAsync(w.run_b, 0, ((size_t)N + 1) * sizeof(uint32_t), st) != hipSuccess)
         return hip_status("tgs_marching_tets_backward");
     const long long* iv = (const long long*)interp_v;
-    hipLaunchKernelGGL(k_mt_grad_count, mt_grid((size_t)M), dim3(MT_BLOCK), 0, st, N, (long long)M, iv, w.run_a, w.run_b);
-    mt_scan(st, w.run_a, (size_t)N + 1, w.scan, (long long*)nullptr);
-    mt_scan(st, w.run_b, (size_t)N + 1, w.scan, (long long*)nullptr);
-    hipLaunchKernelGGL(k_mt_grad_fill, mt_grid((size_t)M), dim3(MT_BLOCK), 0, st, N, (long long)M, iv, w.run_b, w.list_b);
-    hipLaunchKernelGGL(k_mt_grad, mt_grid((size_t)N), dim3(MT_BLOCK), 0, st, N, (long long)M, pos, sdf, iv, dL_dverts, (const uint32_t*)w.run_a, (const uint32_t*)w.run_b,
+    hipLaunchKernelGGL(k_mt_grad_count, run_grid((size_t)M), dim3(RUN_BLOCK), 0, st, N, (long long)M, iv, w.run_a, w.run_b);
+    run_scan(st, w.run_a, (size_t)N + 1, w.scan, (long long*)nullptr);
+    run_scan(st, w.run_b, (size_t)N + 1, w.scan, (long long*)nullptr);
+    hipLaunchKernelGGL(k_mt_grad_fill, run_grid((size_t)M), dim3(RUN_BLOCK), 0, st, N, (long long)M, iv, w.run_b, w.list_b);
+    hipLaunchKernelGGL(k_mt_grad, run_grid((size_t)N), dim3(RUN_BLOCK), 0, st, N, (long long)M, pos, sdf, iv, dL_dverts, (const uint32_t*)w.run_a, (const uint32_t*)w.run_b,
                        w.list_b, dL_dpos, dL_dsdf);
     return hip_status("tgs_marching_tets_backward");
 }

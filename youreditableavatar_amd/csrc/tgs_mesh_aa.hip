@@ -15,15 +15,15 @@
 // `rast` are read coalesced and the right / upper neighbour's line is the lane's own or the one the wave above fetches (L1 / L2 hits); what a
 // pair costs is its divergent analysis -- three dependent indexed reads (tri row, three pos rows, one topo entry) -- which an LDS tile of IDs
 // would not shorten.
-// Launches of tgs_mesh_topology: k_topo_clear, k_topo_insert (every edge of every usable triangle into an open-addressing table keyed by its
-// unordered vertex pair: integer CAS for the key, add for the count, min / max of the edge number 3 t + k), k_topo_resolve (count 1: -1,
+// Launches of tgs_mesh_topology: k_topo_clear, k_topo_insert (every edge of every usable triangle into the edge set of tgs_edge_set.hpp, keyed by
+// its unordered vertex pair; on the key's slot: add for the count, min / max of the edge number 3 t + k), k_topo_resolve (count 1: -1,
 // count 2: the opposite vertex of the other edge, which is the min or the max, more: -2).  Count, min and max do not depend on the order the
 // lanes arrive in; the slot a key lands in does, but no output reads it.
 #include "tgs_mesh_aa_pair.hpp"
+#define TGS_EDGE_SET_TABLE_ONLY                                         // no runs here: count, min and max stay on the slot
+#include "tgs_edge_set.hpp"                                             // the key, the hash, the insert and the lookup
 
 namespace tgs {
-
-constexpr unsigned long long TOPO_EMPTY = ~0ull;       // no key: lo < hi < 2^31 never gives all ones
 
 struct TopoWork {
     unsigned long long* keys;             // [cap] (lo << 32 | hi) of the edge's vertex pair
@@ -44,12 +44,6 @@ __host__ __device__ inline size_t topo_carve(TopoWork& w, char* base, size_t cap
     return (size_t)(p - base) + 256;
 }
 
-__device__ __forceinline__ unsigned long long topo_hash(unsigned long long k)      // (splitmix64's finaliser)
-{
-    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27; k *= 0x94d049bb133111ebull;
-    return k ^ (k >> 31);
-}
 // usable as a neighbour: three different indices inside [0, V)
 __device__ __forceinline__ bool topo_usable(int V, const int* __restrict__ tri, int t, int idx[3])
 {
@@ -59,14 +53,14 @@ __device__ __forceinline__ bool topo_usable(int V, const int* __restrict__ tri, 
 }
 __device__ __forceinline__ unsigned long long topo_key(int a, int b)
 {
-    return ((unsigned long long)(uint32_t)min(a, b) << 32) | (uint32_t)max(a, b);
+    return edge_key((uint32_t)min(a, b), (uint32_t)max(a, b));
 }
 
 __global__ __launch_bounds__(256) void k_topo_clear(size_t cap, TopoWork w)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= cap) return;
-    w.keys[i] = TOPO_EMPTY; w.count[i] = 0u; w.emin[i] = 0xffffffffu; w.emax[i] = 0u;
+    w.keys[i] = EDGE_EMPTY; w.count[i] = 0u; w.emin[i] = 0xffffffffu; w.emax[i] = 0u;
 }
 
 __global__ __launch_bounds__(256) void k_topo_insert(int V, int F, const int* __restrict__ tri, size_t cap, TopoWork w)
@@ -77,17 +71,12 @@ __global__ __launch_bounds__(256) void k_topo_insert(int V, int F, const int* __
     int idx[3];
     if (!topo_usable(V, tri, t, idx)) return;
     const unsigned long long key = topo_key(idx[k], idx[(k + 1) % 3]);
-    size_t slot = (size_t)topo_hash(key) & (cap - 1);
-    for (size_t probe = 0; probe < cap; probe++) {                                // (the table is never full: it ends at the key or at a free slot)
-        const unsigned long long prev = atomicCAS(&w.keys[slot], TOPO_EMPTY, key);
-        if (prev == TOPO_EMPTY || prev == key) {
-            atomicAdd(&w.count[slot], 1u);
-            atomicMin(&w.emin[slot], (uint32_t)e);
-            atomicMax(&w.emax[slot], (uint32_t)e);
-            return;
-        }
-        slot = (slot + 1) & (cap - 1);
-    }
+    bool claimed;
+    const size_t slot = edge_insert(w.keys, cap, key, claimed);
+    if (slot == EDGE_ABSENT) return;                                              // (never: the table is never full)
+    atomicAdd(&w.count[slot], 1u);                                                // on the key's slot, whoever claimed it
+    atomicMin(&w.emin[slot], (uint32_t)e);
+    atomicMax(&w.emax[slot], (uint32_t)e);
 }
 
 __global__ __launch_bounds__(256) void k_topo_resolve(int V, int F, const int* __restrict__ tri, size_t cap, TopoWork w, int* __restrict__ topo)
@@ -99,22 +88,16 @@ __global__ __launch_bounds__(256) void k_topo_resolve(int V, int F, const int* _
     int res = TOPO_NONE;
     if (topo_usable(V, tri, t, idx)) {
         const unsigned long long key = topo_key(idx[k], idx[(k + 1) % 3]);
-        size_t slot = (size_t)topo_hash(key) & (cap - 1);
-        for (size_t probe = 0; probe < cap; probe++) {
-            const unsigned long long have = w.keys[slot];
-            if (have == key) {
-                const uint32_t n = w.count[slot];
-                if (n > 2u) res = TOPO_MANY;
-                else if (n == 2u) {
-                    const uint32_t lo = w.emin[slot], hi = w.emax[slot];
-                    const uint32_t other = lo == (uint32_t)e ? hi : lo;            // < 3 F: it was written by an edge of this launch
-                    const uint32_t ot = other / 3u, oe = other - 3u * ot;
-                    res = tri[3 * (size_t)ot + (oe + 2u) % 3u];
-                }
-                break;
+        const size_t slot = edge_find(w.keys, cap, key);
+        if (slot != EDGE_ABSENT) {                                                // (always: the edge was inserted by the launch before)
+            const uint32_t n = w.count[slot];
+            if (n > 2u) res = TOPO_MANY;
+            else if (n == 2u) {
+                const uint32_t lo = w.emin[slot], hi = w.emax[slot];
+                const uint32_t other = lo == (uint32_t)e ? hi : lo;                // < 3 F: it was written by an edge of this launch
+                const uint32_t ot = other / 3u, oe = other - 3u * ot;
+                res = tri[3 * (size_t)ot + (oe + 2u) % 3u];
             }
-            if (have == TOPO_EMPTY) break;                                        // (never: the edge was inserted by the launch before)
-            slot = (slot + 1) & (cap - 1);
         }
     }
     topo[e] = res;

@@ -6,35 +6,22 @@
 // full; tests/mesh_geom_ref.py restates them.
 //
 // The topology is built once per mesh, in two calls around one read-back (E and the index flag):
-//   tgs_meshgeom_topology_count  k_mg_count (one lane per face: the range check, one count per corner's vertex, the three sides into an
-//                                 open-addressing table keyed by (min << 32 | max), integer CAS; whoever claims a free slot adds one to the
-//                                 count of the side's min vertex and of its max vertex), three scans over V + 1 -> counts[0] = E.
+//   tgs_meshgeom_topology_count  k_mg_count (one lane per face: the range check, one count per corner's vertex, the three sides into the edge
+//                                 set of tgs_edge_set.hpp; whoever claims a free slot adds one to the count of the side's min vertex and of
+//                                 its max vertex), three scans over V + 1 (tgs_runs.hpp) -> counts[0] = E.
 //   tgs_meshgeom_topology_fill   k_mg_inc_fill (3 * face + corner into the vertex's run, through a cursor), k_mg_sort_u32 (one lane per vertex
-//                                 sorts its run), k_mg_edge_fill (every key to its min vertex's run), k_mg_edge_sort (by the max index: the
-//                                 edges are now in ascending (min, max) order whatever the cursors did), k_mg_max_fill (edge numbers by max
-//                                 vertex), k_mg_sort_u32 again.  The hash only dedupes: no output reads a slot number.
-// After the fill the three offset arrays hold the ENDS of the runs: vertex v's run is [v ? end[v - 1] : 0, end[v]).
+//                                 sorts its run), k_edge_fill and k_edge_sort (tgs_edge_set.hpp: the edges are now in ascending (min, max)
+//                                 order whatever the cursors did), k_mg_max_fill (edge numbers by max vertex), k_mg_sort_u32 again.
+// After the fill the three offset arrays hold the ENDS of the runs: vertex v's run is run_bounds(end, v, n) of tgs_runs.hpp.
 // Every later call is a gather: one lane per vertex over its run(s), or one lane per face / per edge; sums in double, in run order, rounded to
 // fp32 once.  The two losses reduce per workgroup in double (a fixed shuffle tree) and one workgroup adds the partial sums in a fixed order.
-#include "tgs_device.hpp"
+#include "tgs_edge_set.hpp"                                             // the edge set; with it tgs_runs.hpp: the scans, the run bounds and the run sort
 
 namespace tgs {
 
-constexpr int MG_BLOCK = 256;
-constexpr int MG_SCAN_ITEMS = 8;
-constexpr int MG_SCAN_TILE = MG_BLOCK * MG_SCAN_ITEMS;                  // elements one workgroup scans
-constexpr unsigned long long MG_EMPTY = ~0ull;                          // no key: min <= max < 2^31 never gives all ones
 constexpr long long MG_MAX_FACES = 1431655765ll;                        // 3 F < 2^32: incidence entries and edge numbers are 32-bit
 constexpr double MG_NORMAL_EPS = 1e-20;                                 // the reference's threshold on the squared length
 constexpr double MG_COSINE_EPS = 1e-8;                                  // torch.cosine_similarity's default eps
-
-__host__ __device__ inline size_t mg_scan_scratch(size_t n)
-{
-    size_t s = 0;
-    while (n > (size_t)MG_SCAN_TILE) { n = (n + MG_SCAN_TILE - 1) / MG_SCAN_TILE; s += (n + 63) & ~(size_t)63; }
-    return s + 64;
-}
-__host__ __device__ inline size_t mg_blocks(size_t n) { return (n + MG_BLOCK - 1) / MG_BLOCK; }
 
 struct MgWork {
     uint32_t* scan;                       // scratch of the scans over V + 1
@@ -44,7 +31,7 @@ __host__ __device__ inline size_t mg_carve(MgWork& w, char* base, size_t V, size
 {
     char* p = base;
     const size_t big = V > 3 * F ? V : 3 * F;
-    carve(p, w.scan, mg_scan_scratch(V + 1)); carve(p, w.partial, mg_blocks(big) + 1);
+    carve(p, w.scan, run_scan_scratch(V + 1)); carve(p, w.partial, run_blocks(big) + 1);
     return (size_t)(p - base) + 256;
 }
 struct MgGradWork {
@@ -64,54 +51,6 @@ __host__ __device__ inline size_t mg_table_capacity(size_t F)
     return cap;
 }
 
-__device__ __forceinline__ unsigned long long mg_hash(unsigned long long k)       // (splitmix64's finaliser)
-{
-    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27; k *= 0x94d049bb133111ebull;
-    return k ^ (k >> 31);
-}
-
-// exclusive scan over the workgroup's 256 lanes; total: the workgroup's sum.  lds: 4 words.
-__device__ __forceinline__ uint32_t mg_block_escan(uint32_t v, uint32_t& total, uint32_t* lds)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t inc = wave_iscan_u32(v, lane);
-    if (lane == 63) lds[wv] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < MG_BLOCK / 64; k++) { const uint32_t s = lds[k]; base += k < wv ? s : 0u; total += s; }
-    __syncthreads();
-    return base + inc - v;
-}
-
-// ---- exclusive scan of uint32 in place: workgroup sums, their scan (recursively), then every workgroup on its own tile ----
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_scan_sums(const uint32_t* __restrict__ data, size_t n, uint32_t* __restrict__ sums)
-{
-    __shared__ uint32_t lds[4];
-    const size_t first = (size_t)blockIdx.x * MG_SCAN_TILE + (size_t)threadIdx.x * MG_SCAN_ITEMS;
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < MG_SCAN_ITEMS; k++) s += first + k < n ? data[first + k] : 0u;
-    uint32_t total;
-    mg_block_escan(s, total, lds);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_scan_tile(uint32_t* __restrict__ data, size_t n, const uint32_t* __restrict__ sums, long long* __restrict__ total_out)
-{
-    __shared__ uint32_t lds[4];
-    const size_t first = (size_t)blockIdx.x * MG_SCAN_TILE + (size_t)threadIdx.x * MG_SCAN_ITEMS;
-    uint32_t v[MG_SCAN_ITEMS], s = 0;
-#pragma unroll
-    for (int k = 0; k < MG_SCAN_ITEMS; k++) { v[k] = first + k < n ? data[first + k] : 0u; s += v[k]; }
-    uint32_t total;
-    uint32_t at = mg_block_escan(s, total, lds) + (sums ? sums[blockIdx.x] : 0u);
-#pragma unroll
-    for (int k = 0; k < MG_SCAN_ITEMS; k++) { if (first + k < n) data[first + k] = at; at += v[k]; }
-    if (total_out && threadIdx.x == 0) *total_out = (long long)total;    // (only the one-workgroup launch at the top is given total_out)
-}
-
 // ---- the topology ----
 template <typename Idx>
 __device__ __forceinline__ bool mg_load_face(const Idx* __restrict__ faces, size_t f, int V, long long i[3])
@@ -121,10 +60,10 @@ __device__ __forceinline__ bool mg_load_face(const Idx* __restrict__ faces, size
 }
 
 template <typename Idx>
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_count(int V, int F, const Idx* __restrict__ faces, uint32_t* __restrict__ inc_end, uint32_t* __restrict__ edge_end,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_count(int V, int F, const Idx* __restrict__ faces, uint32_t* __restrict__ inc_end, uint32_t* __restrict__ edge_end,
                                                        uint32_t* __restrict__ max_end, size_t cap, unsigned long long* __restrict__ keys, long long* __restrict__ counts)
 {
-    const size_t f = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const size_t f = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (f >= (size_t)F) return;
     long long i[3];
     if (!mg_load_face(faces, f, V, i)) {
@@ -138,21 +77,16 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_count(int V, int F, const Idx* 
     for (int c = 0; c < 3; c++) {
         const long long x = i[c], y = i[c == 2 ? 0 : c + 1];
         const long long a = x < y ? x : y, b = x < y ? y : x;
-        const unsigned long long key = ((unsigned long long)a << 32) | (unsigned long long)b;
-        size_t slot = (size_t)mg_hash(key) & (cap - 1);
-        for (size_t probe = 0; probe < cap; probe++) {                   // (the table is never full: it ends at the key or at a free slot)
-            const unsigned long long prev = atomicCAS(&keys[slot], MG_EMPTY, key);
-            if (prev == MG_EMPTY) { atomicAdd(&edge_end[a], 1u); atomicAdd(&max_end[b], 1u); break; }
-            if (prev == key) break;
-            slot = (slot + 1) & (cap - 1);
-        }
+        bool claimed;
+        edge_insert(keys, cap, edge_key(a, b), claimed);
+        if (claimed) { atomicAdd(&edge_end[a], 1u); atomicAdd(&max_end[b], 1u); }
     }
 }
 
 template <typename Idx>
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_inc_fill(int V, int F, const Idx* __restrict__ faces, uint32_t* __restrict__ inc_end, uint32_t* __restrict__ inc)
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_inc_fill(int V, int F, const Idx* __restrict__ faces, uint32_t* __restrict__ inc_end, uint32_t* __restrict__ inc)
 {
-    const size_t f = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const size_t f = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (f >= (size_t)F) return;
     long long i[3];
     if (!mg_load_face(faces, f, V, i)) return;
@@ -164,52 +98,17 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_inc_fill(int V, int F, const Id
 }
 
 // end[v] is now the END of v's run (the start of v + 1's); one lane sorts a vertex's run ascending
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_sort_u32(int V, size_t n, const uint32_t* __restrict__ end, uint32_t* __restrict__ list)
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_sort_u32(int V, size_t n, const uint32_t* __restrict__ end, uint32_t* __restrict__ list)
 {
-    const size_t v = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const size_t v = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (v >= (size_t)V) return;
-    const size_t lo = v ? end[v - 1] : 0;
-    size_t hi = end[v];
-    if (hi > n) hi = n;
-    for (size_t i = lo + 1; i < hi; i++) {
-        const uint32_t x = list[i];
-        size_t j = i;
-        for (; j > lo && list[j - 1] > x; j--) list[j] = list[j - 1];
-        list[j] = x;
-    }
+    const Run run = run_bounds(end, v, n);
+    run_sort(list, 1, (long long)run.lo, (long long)run.hi);
 }
 
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_edge_fill(int V, long long E, size_t cap, const unsigned long long* __restrict__ keys, uint32_t* __restrict__ edge_end,
-                                                           long long* __restrict__ edges)
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_max_fill(int V, long long E, const long long* __restrict__ edges, uint32_t* __restrict__ max_end, uint32_t* __restrict__ max_list)
 {
-    const size_t s = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
-    if (s >= cap) return;
-    const unsigned long long key = keys[s];
-    if (key == MG_EMPTY) return;
-    const long long a = (long long)(key >> 32), b = (long long)(key & 0xffffffffull);
-    if (a >= V) return;
-    const long long p = atomicAdd(&edge_end[a], 1u);
-    if (p < E) { edges[2 * p] = a; edges[2 * p + 1] = b; }
-}
-
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_edge_sort(int V, long long E, const uint32_t* __restrict__ edge_end, long long* __restrict__ edges)
-{
-    const size_t v = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
-    if (v >= (size_t)V) return;
-    const long long lo = v ? edge_end[v - 1] : 0;
-    long long hi = edge_end[v];
-    if (hi > E) hi = E;
-    for (long long i = lo + 1; i < hi; i++) {
-        const long long b = edges[2 * i + 1];
-        long long j = i;
-        for (; j > lo && edges[2 * (j - 1) + 1] > b; j--) edges[2 * j + 1] = edges[2 * (j - 1) + 1];
-        edges[2 * j + 1] = b;
-    }
-}
-
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_max_fill(int V, long long E, const long long* __restrict__ edges, uint32_t* __restrict__ max_end, uint32_t* __restrict__ max_list)
-{
-    const long long e = (long long)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const long long e = (long long)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (e >= E) return;
     const long long b = edges[2 * e + 1];
     if ((unsigned long long)b >= (unsigned long long)V) return;
@@ -217,15 +116,6 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_max_fill(int V, long long E, co
     if (p < E) max_list[p] = (uint32_t)e;
 }
 
-// ---- the runs of a vertex, as the later calls read them ----
-struct MgRun { size_t lo, hi; };
-__device__ __forceinline__ MgRun mg_run(const uint32_t* __restrict__ end, size_t v, size_t n)
-{
-    MgRun r = {v ? (size_t)end[v - 1] : 0, (size_t)end[v]};
-    if (r.hi > n) r.hi = n;
-    if (r.lo > r.hi) r.lo = r.hi;
-    return r;
-}
 __device__ __forceinline__ void mg_row(const float* __restrict__ x, long long v, double r[3])
 {
     r[0] = x[3 * v]; r[1] = x[3 * v + 1]; r[2] = x[3 * v + 2];
@@ -242,7 +132,7 @@ __device__ __forceinline__ void mg_normal_sum(int V, int F, const float* __restr
                                               const uint32_t* __restrict__ inc, size_t v, double s[3])
 {
     s[0] = s[1] = s[2] = 0.0;
-    const MgRun run = mg_run(inc_end, v, 3 * (size_t)F);
+    const Run run = run_bounds(inc_end, v, 3 * (size_t)F);
     for (size_t k = run.lo; k < run.hi; k++) {
         const size_t f = inc[k] / 3u;
         long long i[3];
@@ -257,10 +147,10 @@ __device__ __forceinline__ void mg_normal_sum(int V, int F, const float* __restr
 }
 
 template <typename Idx>
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_normals(int V, int F, const float* __restrict__ v_pos, const Idx* __restrict__ faces, const uint32_t* __restrict__ inc_end,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_normals(int V, int F, const float* __restrict__ v_pos, const Idx* __restrict__ faces, const uint32_t* __restrict__ inc_end,
                                                          const uint32_t* __restrict__ inc, float* __restrict__ v_nrm)
 {
-    const size_t v = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const size_t v = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (v >= (size_t)V) return;
     double s[3];
     mg_normal_sum(V, F, v_pos, faces, inc_end, inc, v, s);
@@ -275,11 +165,11 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_normals(int V, int F, const flo
 
 // the upstream through the normalization n = s / |s|: g_sum = (g - n (n . g)) / |s|, an exact zero for a default row
 template <typename Idx>
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_normals_bwd_vertex(int V, int F, const float* __restrict__ v_pos, const Idx* __restrict__ faces,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_normals_bwd_vertex(int V, int F, const float* __restrict__ v_pos, const Idx* __restrict__ faces,
                                                                     const uint32_t* __restrict__ inc_end, const uint32_t* __restrict__ inc, const float* __restrict__ g_nrm,
                                                                     double* __restrict__ g_sum)
 {
-    const size_t v = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const size_t v = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (v >= (size_t)V) return;
     double s[3], out[3] = {0.0, 0.0, 0.0};
     mg_normal_sum(V, F, v_pos, faces, inc_end, inc, v, s);
@@ -297,9 +187,9 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_normals_bwd_vertex(int V, int F
 }
 
 template <typename Idx>
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_normals_bwd_face(int V, int F, const Idx* __restrict__ faces, const double* __restrict__ g_sum, double* __restrict__ g_face)
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_normals_bwd_face(int V, int F, const Idx* __restrict__ faces, const double* __restrict__ g_sum, double* __restrict__ g_face)
 {
-    const size_t f = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const size_t f = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (f >= (size_t)F) return;
     long long i[3];
     double g[3] = {0.0, 0.0, 0.0};
@@ -313,14 +203,14 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_normals_bwd_face(int V, int F, 
 // with e1 = v1 - v0, e2 = v2 - v0 and G the face's gradient: dL/de1 = e2 x G, dL/de2 = G x e1; corner 1 receives the first, corner 2 the
 // second, corner 0 minus both.  Plain arithmetic: 0 * NaN stays a NaN, as in the framework's backward.
 template <typename Idx>
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_normals_bwd_gather(int V, int F, const float* __restrict__ v_pos, const Idx* __restrict__ faces,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_normals_bwd_gather(int V, int F, const float* __restrict__ v_pos, const Idx* __restrict__ faces,
                                                                     const uint32_t* __restrict__ inc_end, const uint32_t* __restrict__ inc, const double* __restrict__ g_face,
                                                                     float* __restrict__ d_pos)
 {
-    const size_t v = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const size_t v = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (v >= (size_t)V) return;
     double acc[3] = {0.0, 0.0, 0.0};
-    const MgRun run = mg_run(inc_end, v, 3 * (size_t)F);
+    const Run run = run_bounds(inc_end, v, 3 * (size_t)F);
     for (size_t k = run.lo; k < run.hi; k++) {
         const uint32_t x = inc[k];
         const size_t f = x / 3u;
@@ -349,16 +239,16 @@ __device__ __forceinline__ double mg_block_sum(double x, double* lds)       // a
     double s = 0.0;
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int k = 0; k < MG_BLOCK / 64; k++) s += lds[k];
+        for (int k = 0; k < RUN_BLOCK / 64; k++) s += lds[k];
     }
     __syncthreads();
     return s;
 }
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_mean(size_t n_partial, const double* __restrict__ partial, double count, float* __restrict__ out)
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_mean(size_t n_partial, const double* __restrict__ partial, double count, float* __restrict__ out)
 {
     __shared__ double lds[4];
     double s = 0.0;
-    for (size_t k = threadIdx.x; k < n_partial; k += MG_BLOCK) s += partial[k];
+    for (size_t k = threadIdx.x; k < n_partial; k += RUN_BLOCK) s += partial[k];
     s = mg_block_sum(s, lds);
     if (threadIdx.x == 0) *out = (float)(s / count);
 }
@@ -374,10 +264,10 @@ __device__ __forceinline__ double mg_cosine(const double x[3], const double y[3]
     return (x[0] / cx) * yh[0] + (x[1] / cx) * yh[1] + (x[2] / cx) * yh[2];
 }
 
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_consistency(int V, long long E, const float* __restrict__ v_nrm, const long long* __restrict__ edges, double* __restrict__ partial)
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_consistency(int V, long long E, const float* __restrict__ v_nrm, const long long* __restrict__ edges, double* __restrict__ partial)
 {
     __shared__ double lds[4];
-    const long long e = (long long)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const long long e = (long long)blockIdx.x * RUN_BLOCK + threadIdx.x;
     double term = 0.0;
     if (e < E) {
         const long long a = edges[2 * e], b = edges[2 * e + 1];
@@ -401,20 +291,20 @@ __device__ __forceinline__ void mg_cosine_grad(const float* __restrict__ v_nrm, 
 #pragma unroll
     for (int d = 0; d < 3; d++) acc[d] += (yh[d] - (live ? c * (x[d] / nx) : 0.0)) / cx;
 }
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_consistency_bwd(int V, long long E, const float* __restrict__ v_nrm, const long long* __restrict__ edges,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_consistency_bwd(int V, long long E, const float* __restrict__ v_nrm, const long long* __restrict__ edges,
                                                                  const uint32_t* __restrict__ edge_end, const uint32_t* __restrict__ max_end, const uint32_t* __restrict__ max_list,
                                                                  const float* __restrict__ g_out, float* __restrict__ d_nrm)
 {
-    const size_t v = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const size_t v = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (v >= (size_t)V) return;
     double x[3], acc[3] = {0.0, 0.0, 0.0};
     mg_row(v_nrm, (long long)v, x);
-    MgRun run = mg_run(edge_end, v, (size_t)E);
+    Run run = run_bounds(edge_end, v, (size_t)E);
     for (size_t e = run.lo; e < run.hi; e++) {                            // v is the min end
         const long long b = edges[2 * e + 1];
         if (edges[2 * e] == (long long)v && (unsigned long long)b < (unsigned long long)V) mg_cosine_grad(v_nrm, x, b, acc);
     }
-    run = mg_run(max_end, v, (size_t)E);
+    run = run_bounds(max_end, v, (size_t)E);
     for (size_t k = run.lo; k < run.hi; k++) {                            // v is the max end, ascending edge number
         const size_t e = max_list[k];
         if (e >= (size_t)E) continue;
@@ -433,13 +323,13 @@ __device__ __forceinline__ void mg_laplace_row(int V, long long E, const T* __re
 {
     const double x0 = x[3 * v], x1 = x[3 * v + 1], x2 = x[3 * v + 2];
     r[0] = r[1] = r[2] = 0.0;
-    MgRun run = mg_run(edge_end, v, (size_t)E);
+    Run run = run_bounds(edge_end, v, (size_t)E);
     for (size_t e = run.lo; e < run.hi; e++) {
         const long long o = edges[2 * e + 1];
         if (edges[2 * e] != (long long)v || o == (long long)v || (unsigned long long)o >= (unsigned long long)V) continue;
         r[0] += x0 - (double)x[3 * o]; r[1] += x1 - (double)x[3 * o + 1]; r[2] += x2 - (double)x[3 * o + 2];
     }
-    run = mg_run(max_end, v, (size_t)E);
+    run = run_bounds(max_end, v, (size_t)E);
     for (size_t k = run.lo; k < run.hi; k++) {
         const size_t e = max_list[k];
         if (e >= (size_t)E) continue;
@@ -448,12 +338,12 @@ __device__ __forceinline__ void mg_laplace_row(int V, long long E, const T* __re
         r[0] += x0 - (double)x[3 * o]; r[1] += x1 - (double)x[3 * o + 1]; r[2] += x2 - (double)x[3 * o + 2];
     }
 }
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_laplacian(int V, long long E, const float* __restrict__ v_pos, const long long* __restrict__ edges,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_laplacian(int V, long long E, const float* __restrict__ v_pos, const long long* __restrict__ edges,
                                                            const uint32_t* __restrict__ edge_end, const uint32_t* __restrict__ max_end, const uint32_t* __restrict__ max_list,
                                                            double* __restrict__ unit_rows, double* __restrict__ partial)
 {
     __shared__ double lds[4];
-    const size_t v = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const size_t v = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     double norm = 0.0;
     if (v < (size_t)V) {
         double r[3];
@@ -467,11 +357,11 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_laplacian(int V, long long E, c
     norm = mg_block_sum(norm, lds);
     if (threadIdx.x == 0) partial[blockIdx.x] = norm;
 }
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_laplacian_bwd(int V, long long E, const long long* __restrict__ edges, const uint32_t* __restrict__ edge_end,
+__global__ __launch_bounds__(RUN_BLOCK) void k_mg_laplacian_bwd(int V, long long E, const long long* __restrict__ edges, const uint32_t* __restrict__ edge_end,
                                                                const uint32_t* __restrict__ max_end, const uint32_t* __restrict__ max_list, const double* __restrict__ unit_rows,
                                                                const float* __restrict__ g_out, float* __restrict__ d_pos)
 {
-    const size_t v = (size_t)blockIdx.x * MG_BLOCK + threadIdx.x;
+    const size_t v = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (v >= (size_t)V) return;
     double r[3];
     mg_laplace_row(V, E, unit_rows, edges, edge_end, max_end, max_list, v, r);     // the operator is symmetric
@@ -479,20 +369,6 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_laplacian_bwd(int V, long long 
     d_pos[3 * v] = (float)(w * r[0]); d_pos[3 * v + 1] = (float)(w * r[1]); d_pos[3 * v + 2] = (float)(w * r[2]);
 }
 
-// exclusive scan of data[0 .. n) in place on `st`; the sum goes to *total_out (device) if given
-static void mg_scan(hipStream_t st, uint32_t* data, size_t n, uint32_t* scratch, long long* total_out)
-{
-    if (n <= (size_t)MG_SCAN_TILE) {
-        hipLaunchKernelGGL(k_mg_scan_tile, dim3(1), dim3(MG_BLOCK), 0, st, data, n, (const uint32_t*)nullptr, total_out);
-        return;
-    }
-    const size_t nb = (n + MG_SCAN_TILE - 1) / MG_SCAN_TILE;
-    hipLaunchKernelGGL(k_mg_scan_sums, dim3((unsigned)nb), dim3(MG_BLOCK), 0, st, (const uint32_t*)data, n, scratch);
-    mg_scan(st, scratch, nb, scratch + ((nb + 63) & ~(size_t)63), total_out);
-    hipLaunchKernelGGL(k_mg_scan_tile, dim3((unsigned)nb), dim3(MG_BLOCK), 0, st, data, n, (const uint32_t*)scratch, (long long*)nullptr);
-}
-
-static inline dim3 mg_grid(size_t n) { return dim3((unsigned)mg_blocks(n)); }
 static inline bool mg_sizes_ok(int V, int F) { return V >= 0 && F >= 0 && (long long)F <= MG_MAX_FACES; }
 static inline bool mg_flag_ok(int is64) { return is64 == 0 || is64 == 1; }
 
@@ -542,12 +418,12 @@ int tgs_meshgeom_topology_count(void* stream, int V, int F, const void* faces, i
                   hipMemsetAsync(max_end, 0, row, st) != hipSuccess)))
         return hip_status("tgs_meshgeom_topology_count");
     long long* cnt = (long long*)counts;
-    if (faces_is_int64) hipLaunchKernelGGL(k_mg_count<long long>, mg_grid((size_t)F), dim3(MG_BLOCK), 0, st, V, F, (const long long*)faces, inc_end, edge_end, max_end, cap, keys, cnt);
-    else                hipLaunchKernelGGL(k_mg_count<int>, mg_grid((size_t)F), dim3(MG_BLOCK), 0, st, V, F, (const int*)faces, inc_end, edge_end, max_end, cap, keys, cnt);
-    mg_scan(st, inc_end, (size_t)V + 1, w.scan, cnt + 2);
+    if (faces_is_int64) hipLaunchKernelGGL(k_mg_count<long long>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, V, F, (const long long*)faces, inc_end, edge_end, max_end, cap, keys, cnt);
+    else                hipLaunchKernelGGL(k_mg_count<int>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, V, F, (const int*)faces, inc_end, edge_end, max_end, cap, keys, cnt);
+    run_scan(st, inc_end, (size_t)V + 1, w.scan, cnt + 2);
     if (keys) {
-        mg_scan(st, edge_end, (size_t)V + 1, w.scan, cnt + 0);
-        mg_scan(st, max_end, (size_t)V + 1, w.scan, (long long*)nullptr);
+        run_scan(st, edge_end, (size_t)V + 1, w.scan, cnt + 0);
+        run_scan(st, max_end, (size_t)V + 1, w.scan, (long long*)nullptr);
     }
     return hip_status("tgs_meshgeom_topology_count");
 }
@@ -564,16 +440,16 @@ int tgs_meshgeom_topology_fill(void* stream, int V, int F, const void* faces, in
     const size_t cap = mg_table_capacity((size_t)F);
     if (table && cap * sizeof(unsigned long long) + 256 > table_bytes)
         return set_error(TGS_ERR_INVALID, "tgs_meshgeom_topology_fill: table smaller than tgs_meshgeom_table_bytes(F)");
-    if (faces_is_int64) hipLaunchKernelGGL(k_mg_inc_fill<long long>, mg_grid((size_t)F), dim3(MG_BLOCK), 0, st, V, F, (const long long*)faces, inc_end, inc);
-    else                hipLaunchKernelGGL(k_mg_inc_fill<int>, mg_grid((size_t)F), dim3(MG_BLOCK), 0, st, V, F, (const int*)faces, inc_end, inc);
-    hipLaunchKernelGGL(k_mg_sort_u32, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, 3 * (size_t)F, (const uint32_t*)inc_end, inc);
+    if (faces_is_int64) hipLaunchKernelGGL(k_mg_inc_fill<long long>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, V, F, (const long long*)faces, inc_end, inc);
+    else                hipLaunchKernelGGL(k_mg_inc_fill<int>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, V, F, (const int*)faces, inc_end, inc);
+    hipLaunchKernelGGL(k_mg_sort_u32, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, 3 * (size_t)F, (const uint32_t*)inc_end, inc);
     if (table) {
         const unsigned long long* keys = (const unsigned long long*)(((uintptr_t)table + 255) & ~(uintptr_t)255);
         long long* ed = (long long*)edges;
-        hipLaunchKernelGGL(k_mg_edge_fill, mg_grid(cap), dim3(MG_BLOCK), 0, st, V, (long long)E, cap, keys, edge_end, ed);
-        hipLaunchKernelGGL(k_mg_edge_sort, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, (long long)E, (const uint32_t*)edge_end, ed);
-        hipLaunchKernelGGL(k_mg_max_fill, mg_grid((size_t)E), dim3(MG_BLOCK), 0, st, V, (long long)E, (const long long*)ed, max_end, max_list);
-        hipLaunchKernelGGL(k_mg_sort_u32, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, (size_t)E, (const uint32_t*)max_end, max_list);
+        hipLaunchKernelGGL(k_edge_fill, run_grid(cap), dim3(RUN_BLOCK), 0, st, V, (long long)E, cap, keys, edge_end, ed);
+        hipLaunchKernelGGL(k_edge_sort, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, (long long)E, (const uint32_t*)edge_end, ed);
+        hipLaunchKernelGGL(k_mg_max_fill, run_grid((size_t)E), dim3(RUN_BLOCK), 0, st, V, (long long)E, (const long long*)ed, max_end, max_list);
+        hipLaunchKernelGGL(k_mg_sort_u32, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, (size_t)E, (const uint32_t*)max_end, max_list);
     }
     return hip_status("tgs_meshgeom_topology_fill");
 }
@@ -585,8 +461,8 @@ int tgs_meshgeom_normals(void* stream, int V, int F, const float* v_pos, const v
     if (!mg_sizes_ok(V, F) || !mg_flag_ok(faces_is_int64) || (V > 0 && (!v_pos || !v_nrm || !inc_end)) || (V > 0 && F > 0 && (!faces || !inc)))
         return set_error(TGS_ERR_INVALID, "tgs_meshgeom_normals: V >= 0, 0 <= F <= (2^32 - 1) / 3, faces_is_int64 in {0, 1} and non-NULL v_pos / faces / inc_end / inc / v_nrm required");
     if (V == 0) return TGS_OK;
-    if (faces_is_int64) hipLaunchKernelGGL(k_mg_normals<long long>, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, F, v_pos, (const long long*)faces, inc_end, inc, v_nrm);
-    else                hipLaunchKernelGGL(k_mg_normals<int>, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, F, v_pos, (const int*)faces, inc_end, inc, v_nrm);
+    if (faces_is_int64) hipLaunchKernelGGL(k_mg_normals<long long>, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, F, v_pos, (const long long*)faces, inc_end, inc, v_nrm);
+    else                hipLaunchKernelGGL(k_mg_normals<int>, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, F, v_pos, (const int*)faces, inc_end, inc, v_nrm);
     return hip_status("tgs_meshgeom_normals");
 }
 
@@ -608,14 +484,14 @@ int tgs_meshgeom_normals_backward(void* stream, int V, int F, const float* v_pos
     }
     if (faces_is_int64) {
         const long long* fc = (const long long*)faces;
-        hipLaunchKernelGGL(k_mg_normals_bwd_vertex<long long>, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, F, v_pos, fc, inc_end, inc, dL_dnrm, w.g_sum);
-        hipLaunchKernelGGL(k_mg_normals_bwd_face<long long>, mg_grid((size_t)F), dim3(MG_BLOCK), 0, st, V, F, fc, (const double*)w.g_sum, w.g_face);
-        hipLaunchKernelGGL(k_mg_normals_bwd_gather<long long>, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, F, v_pos, fc, inc_end, inc, (const double*)w.g_face, dL_dpos);
+        hipLaunchKernelGGL(k_mg_normals_bwd_vertex<long long>, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, F, v_pos, fc, inc_end, inc, dL_dnrm, w.g_sum);
+        hipLaunchKernelGGL(k_mg_normals_bwd_face<long long>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, V, F, fc, (const double*)w.g_sum, w.g_face);
+        hipLaunchKernelGGL(k_mg_normals_bwd_gather<long long>, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, F, v_pos, fc, inc_end, inc, (const double*)w.g_face, dL_dpos);
     } else {
         const int* fc = (const int*)faces;
-        hipLaunchKernelGGL(k_mg_normals_bwd_vertex<int>, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, F, v_pos, fc, inc_end, inc, dL_dnrm, w.g_sum);
-        hipLaunchKernelGGL(k_mg_normals_bwd_face<int>, mg_grid((size_t)F), dim3(MG_BLOCK), 0, st, V, F, fc, (const double*)w.g_sum, w.g_face);
-        hipLaunchKernelGGL(k_mg_normals_bwd_gather<int>, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, F, v_pos, fc, inc_end, inc, (const double*)w.g_face, dL_dpos);
+        hipLaunchKernelGGL(k_mg_normals_bwd_vertex<int>, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, F, v_pos, fc, inc_end, inc, dL_dnrm, w.g_sum);
+        hipLaunchKernelGGL(k_mg_normals_bwd_face<int>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, V, F, fc, (const double*)w.g_sum, w.g_face);
+        hipLaunchKernelGGL(k_mg_normals_bwd_gather<int>, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, F, v_pos, fc, inc_end, inc, (const double*)w.g_face, dL_dpos);
     }
     return hip_status("tgs_meshgeom_normals_backward");
 }
@@ -629,8 +505,8 @@ int tgs_meshgeom_consistency(void* stream, int V, int64_t E, const float* v_nrm,
     MgWork w;
     if (mg_carve(w, (char*)workspace, (size_t)V, (size_t)((E + 2) / 3)) > workspace_bytes)
         return set_error(TGS_ERR_INVALID, "tgs_meshgeom_consistency: workspace smaller than tgs_meshgeom_workspace_bytes(V, ceil(E / 3))");
-    hipLaunchKernelGGL(k_mg_consistency, mg_grid((size_t)E), dim3(MG_BLOCK), 0, st, V, (long long)E, v_nrm, (const long long*)edges, w.partial);
-    hipLaunchKernelGGL(k_mg_mean, dim3(1), dim3(MG_BLOCK), 0, st, mg_blocks((size_t)E), (const double*)w.partial, (double)E, out);
+    hipLaunchKernelGGL(k_mg_consistency, run_grid((size_t)E), dim3(RUN_BLOCK), 0, st, V, (long long)E, v_nrm, (const long long*)edges, w.partial);
+    hipLaunchKernelGGL(k_mg_mean, dim3(1), dim3(RUN_BLOCK), 0, st, run_blocks((size_t)E), (const double*)w.partial, (double)E, out);
     return hip_status("tgs_meshgeom_consistency");
 }
 
@@ -642,7 +518,7 @@ int tgs_meshgeom_consistency_backward(void* stream, int V, int64_t E, const floa
     if (V <= 0 || E <= 0 || E > 3 * MG_MAX_FACES || !v_nrm || !edges || !edge_end || !max_end || !max_list || !dL_dout)
         return set_error(TGS_ERR_INVALID, "tgs_meshgeom_consistency_backward: V > 0, 0 < E < 2^32 and non-NULL v_nrm / edges / edge_end / max_end / max_list / dL_dout required");
     if (!dL_dnrm) return TGS_OK;
-    hipLaunchKernelGGL(k_mg_consistency_bwd, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, (long long)E, v_nrm, (const long long*)edges, edge_end, max_end, max_list, dL_dout, dL_dnrm);
+    hipLaunchKernelGGL(k_mg_consistency_bwd, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, (long long)E, v_nrm, (const long long*)edges, edge_end, max_end, max_list, dL_dout, dL_dnrm);
     return hip_status("tgs_meshgeom_consistency_backward");
 }
 
@@ -656,8 +532,8 @@ int tgs_meshgeom_laplacian(void* stream, int V, int64_t E, const float* v_pos, c
     MgWork w;
     if (mg_carve(w, (char*)workspace, (size_t)V, (size_t)((E + 2) / 3)) > workspace_bytes)
         return set_error(TGS_ERR_INVALID, "tgs_meshgeom_laplacian: workspace smaller than tgs_meshgeom_workspace_bytes(V, ceil(E / 3))");
-    hipLaunchKernelGGL(k_mg_laplacian, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, (long long)E, v_pos, (const long long*)edges, edge_end, max_end, max_list, unit_rows, w.partial);
-    hipLaunchKernelGGL(k_mg_mean, dim3(1), dim3(MG_BLOCK), 0, st, mg_blocks((size_t)V), (const double*)w.partial, (double)V, out);
+    hipLaunchKernelGGL(k_mg_laplacian, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, (long long)E, v_pos, (const long long*)edges, edge_end, max_end, max_list, unit_rows, w.partial);
+    hipLaunchKernelGGL(k_mg_mean, dim3(1), dim3(RUN_BLOCK), 0, st, run_blocks((size_t)V), (const double*)w.partial, (double)V, out);
     return hip_status("tgs_meshgeom_laplacian");
 }
 
@@ -669,7 +545,7 @@ int tgs_meshgeom_laplacian_backward(void* stream, int V, int64_t E, const int64_
     if (V <= 0 || E < 0 || E > 3 * MG_MAX_FACES || !edge_end || !max_end || !unit_rows || !dL_dout || (E > 0 && (!edges || !max_list)))
         return set_error(TGS_ERR_INVALID, "tgs_meshgeom_laplacian_backward: V > 0, 0 <= E < 2^32 and non-NULL edges / edge_end / max_end / max_list / unit_rows / dL_dout required");
     if (!dL_dpos) return TGS_OK;
-    hipLaunchKernelGGL(k_mg_laplacian_bwd, mg_grid((size_t)V), dim3(MG_BLOCK), 0, st, V, (long long)E, (const long long*)edges, edge_end, max_end, max_list, unit_rows, dL_dout, dL_dpos);
+    hipLaunchKernelGGL(k_mg_laplacian_bwd, run_grid((size_t)V), dim3(RUN_BLOCK), 0, st, V, (long long)E, (const long long*)edges, edge_end, max_end, max_list, unit_rows, dL_dout, dL_dpos);
     return hip_status("tgs_meshgeom_laplacian_backward");
 }
 }

@@ -15,11 +15,12 @@
 // the distinct counts ranks the edges.  24 bytes per tetrahedron of workspace where the open-addressing table of tgs_marching_tets.hip would
 // take 96 (6 F keys of 8 bytes at load <= 1/2), no CAS, no table to clear, and the size is known before the call; the price is runs about five
 // times as long for the one lane that sorts them (an interior edge of a grid is listed by four to six tetrahedra).
-//   tgs_tet_subdivide_edges  k_ts_count, scan, k_ts_fill, k_ts_sort_unique, scan.
+//   tgs_tet_subdivide_edges  k_ts_count, scan, k_ts_fill, k_ts_sort_unique, scan.  (The scans, the run bounds, the sort that drops repeats and the
+//                            binary search are tgs_runs.hpp's, as in tgs_marching_tets.hip and tgs_mesh_geom.hip.)
 //   tgs_tet_subdivide_emit   k_ts_edges (one lane per vertex writes its rows of `edges`), k_ts_verts (one lane per row of new_v and batch
 //                            element: a copy, or the midpoint (a + b) * 0.5f; the mask row), k_ts_tets (one lane per tetrahedron: six binary
 //                            searches, eight rows, eight parents).
-#include "tgs_tet_common.hpp"                                           // shared with tgs_marching_tets.hip
+#include "tgs_tet_common.hpp"                                           // the row load, shared with tgs_marching_tets.hip; with it tgs_runs.hpp
 
 namespace tgs {
 
@@ -36,9 +37,9 @@ __host__ __device__ inline size_t tg_words(size_t N) { return (N + 63) / 64; }
 __host__ __device__ inline size_t tg_compact_carve(TgCompactWork& w, char* base, size_t N, size_t F)
 {
     char* p = base;
-    const size_t big = tg_words(N) + 1 > mt_blocks(F) + 1 ? tg_words(N) + 1 : mt_blocks(F) + 1;
-    carve(p, w.bits, tg_words(N) + 1); carve(p, w.kept, F + 1); carve(p, w.blk, mt_blocks(F) + 1); carve(p, w.wpre, tg_words(N) + 1);
-    carve(p, w.scan, mt_scan_scratch(big));
+    const size_t big = tg_words(N) + 1 > run_blocks(F) + 1 ? tg_words(N) + 1 : run_blocks(F) + 1;
+    carve(p, w.bits, tg_words(N) + 1); carve(p, w.kept, F + 1); carve(p, w.blk, run_blocks(F) + 1); carve(p, w.wpre, tg_words(N) + 1);
+    carve(p, w.scan, run_scan_scratch(big));
     return (size_t)(p - base) + 256;
 }
 
@@ -51,7 +52,7 @@ struct TgSubdivWork {
 __host__ __device__ inline size_t tg_subdiv_carve(TgSubdivWork& w, char* base, size_t N, size_t F)
 {
     char* p = base;
-    carve(p, w.run, N + 1); carve(p, w.urun, N + 1); carve(p, w.list, 6 * F + 1); carve(p, w.scan, mt_scan_scratch(N + 1));
+    carve(p, w.run, N + 1); carve(p, w.urun, N + 1); carve(p, w.list, 6 * F + 1); carve(p, w.scan, run_scan_scratch(N + 1));
     return (size_t)(p - base) + 256;
 }
 
@@ -61,13 +62,13 @@ __host__ __device__ inline int tg_mask_bytes(int type) { return type == TG_MASK_
 
 // ---- compact ----
 template <typename Idx>
-__global__ __launch_bounds__(MT_BLOCK) void k_tg_select(int N, int F, const float* __restrict__ sdf, const Idx* __restrict__ tet, const uint8_t* __restrict__ keep,
+__global__ __launch_bounds__(RUN_BLOCK) void k_tg_select(int N, int F, const float* __restrict__ sdf, const Idx* __restrict__ tet, const uint8_t* __restrict__ keep,
                                                         float threshold, unsigned long long* __restrict__ bits, uint8_t* __restrict__ kept,
                                                         uint32_t* __restrict__ blk, long long* __restrict__ counts)
 {
 #pragma clang fp contract(off)
     __shared__ uint32_t lds[4];
-    const size_t f = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t f = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     uint32_t k = 0;
     if (f < (size_t)F) {
         long long t[4];
@@ -92,12 +93,12 @@ __global__ __launch_bounds__(MT_BLOCK) void k_tg_select(int N, int F, const floa
         kept[f] = (uint8_t)k;
     }
     uint32_t total;
-    mt_block_escan(k, total, lds);
+    run_block_escan(k, total, lds);
     if (threadIdx.x == 0) blk[blockIdx.x] = total;
 }
-__global__ __launch_bounds__(MT_BLOCK) void k_tg_popc(size_t words, const unsigned long long* __restrict__ bits, uint32_t* __restrict__ wpre)
+__global__ __launch_bounds__(RUN_BLOCK) void k_tg_popc(size_t words, const unsigned long long* __restrict__ bits, uint32_t* __restrict__ wpre)
 {
-    const size_t w = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t w = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (w < words) wpre[w] = (uint32_t)__popcll(bits[w]);
 }
 // the number of set bits below v: v's row among the kept vertices
@@ -107,15 +108,15 @@ __device__ __forceinline__ long long tg_rank(const unsigned long long* __restric
     return (long long)wpre[v >> 6] + __popcll(below);
 }
 template <typename Idx, typename Out>
-__global__ __launch_bounds__(MT_BLOCK) void k_tg_emit_tets(int N, int F, long long Fk, const Idx* __restrict__ tet, const uint8_t* __restrict__ kept,
+__global__ __launch_bounds__(RUN_BLOCK) void k_tg_emit_tets(int N, int F, long long Fk, const Idx* __restrict__ tet, const uint8_t* __restrict__ kept,
                                                            const uint32_t* __restrict__ blk, const unsigned long long* __restrict__ bits,
                                                            const uint32_t* __restrict__ wpre, Out* __restrict__ new_tets, Out* __restrict__ idx_to_old)
 {
     __shared__ uint32_t lds[4];
-    const size_t f = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t f = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     const uint32_t k = f < (size_t)F ? kept[f] : 0u;
     uint32_t total;
-    const long long row = (long long)blk[blockIdx.x] + mt_block_escan(k, total, lds);
+    const long long row = (long long)blk[blockIdx.x] + run_block_escan(k, total, lds);
     if (!k || row >= Fk) return;
     long long t[4];
     mt_load_tet(tet, f, t);
@@ -125,13 +126,13 @@ __global__ __launch_bounds__(MT_BLOCK) void k_tg_emit_tets(int N, int F, long lo
     idx_to_old[row] = (Out)f;
 }
 template <typename Out>
-__global__ __launch_bounds__(MT_BLOCK) void k_tg_emit_verts(int N, long long Nk, const unsigned long long* __restrict__ bits, const uint32_t* __restrict__ wpre,
+__global__ __launch_bounds__(RUN_BLOCK) void k_tg_emit_verts(int N, long long Nk, const unsigned long long* __restrict__ bits, const uint32_t* __restrict__ wpre,
                                                             const float* __restrict__ pos, const float* __restrict__ sdf, const void* __restrict__ mask,
                                                             int mask_bytes, const unsigned long long* __restrict__ member_bits, Out* __restrict__ unique_vtx,
                                                             float* __restrict__ new_pos, float* __restrict__ new_sdf, void* __restrict__ new_mask,
                                                             int* __restrict__ member)
 {
-    const long long v = (long long)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const long long v = (long long)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (v >= N || !((bits[v >> 6] >> (v & 63)) & 1ull)) return;
     const long long r = tg_rank(bits, wpre, v);
     if (r >= Nk) return;
@@ -153,9 +154,9 @@ __device__ __forceinline__ uint32_t ts_min_end(const long long t[4], int i, int 
     return (i != j && (t[i] < t[j] || (t[i] == t[j] && i < j))) ? 1u : 0u;
 }
 template <typename Idx>
-__global__ __launch_bounds__(MT_BLOCK) void k_ts_count(int N, int F, const Idx* __restrict__ tet, uint32_t* __restrict__ run, long long* __restrict__ counts)
+__global__ __launch_bounds__(RUN_BLOCK) void k_ts_count(int N, int F, const Idx* __restrict__ tet, uint32_t* __restrict__ run, long long* __restrict__ counts)
 {
-    const size_t f = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t f = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (f >= (size_t)F) return;
     long long t[4];
     mt_load_tet(tet, f, t);
@@ -169,9 +170,9 @@ __global__ __launch_bounds__(MT_BLOCK) void k_ts_count(int N, int F, const Idx* 
     }
 }
 template <typename Idx>
-__global__ __launch_bounds__(MT_BLOCK) void k_ts_fill(int N, int F, const Idx* __restrict__ tet, uint32_t* __restrict__ run, uint32_t* __restrict__ list)
+__global__ __launch_bounds__(RUN_BLOCK) void k_ts_fill(int N, int F, const Idx* __restrict__ tet, uint32_t* __restrict__ run, uint32_t* __restrict__ list)
 {
-    const size_t f = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t f = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (f >= (size_t)F) return;
     long long t[4];
     mt_load_tet(tet, f, t);
@@ -189,22 +190,20 @@ __global__ __launch_bounds__(MT_BLOCK) void k_ts_fill(int N, int F, const Idx* _
     }
 }
 // run[v] is now the END of v's run (the start of v + 1's); v's max indices are sorted and the repeats dropped, in place
-__global__ __launch_bounds__(MT_BLOCK) void k_ts_sort_unique(int N, int F, const uint32_t* __restrict__ run, uint32_t* __restrict__ list, uint32_t* __restrict__ urun)
+__global__ __launch_bounds__(RUN_BLOCK) void k_ts_sort_unique(int N, int F, const uint32_t* __restrict__ run, uint32_t* __restrict__ list, uint32_t* __restrict__ urun)
 {
-    const size_t v = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t v = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (v > (size_t)N) return;
     if (v == (size_t)N) { urun[v] = 0; return; }
-    const long long lo = v ? run[v - 1] : 0;
-    long long hi = run[v];
-    if (hi > 6ll * F) hi = 6ll * F;
-    urun[v] = (uint32_t)(mt_sort_unique_run(list, lo, hi) - lo);
+    const Run r = run_bounds(run, v, 6 * (size_t)F);
+    urun[v] = (uint32_t)(run_sort_unique(list, (long long)r.lo, (long long)r.hi) - (long long)r.lo);
 }
-__global__ __launch_bounds__(MT_BLOCK) void k_ts_edges(int N, long long E, const uint32_t* __restrict__ run, const uint32_t* __restrict__ urun,
+__global__ __launch_bounds__(RUN_BLOCK) void k_ts_edges(int N, long long E, const uint32_t* __restrict__ run, const uint32_t* __restrict__ urun,
                                                        const uint32_t* __restrict__ list, long long* __restrict__ edges)
 {
-    const size_t v = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t v = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (v >= (size_t)N) return;
-    const long long lo = v ? run[v - 1] : 0, first = urun[v];
+    const long long lo = (long long)run_start(run, v), first = urun[v];
     long long last = urun[v + 1];
     if (last > E) last = E;
     for (long long e = first; e < last; e++) { edges[2 * e] = (long long)v; edges[2 * e + 1] = (long long)list[lo + (e - first)]; }
@@ -225,11 +224,11 @@ __device__ __forceinline__ float tg_mask_value(const void* __restrict__ mask, in
          : type == TG_MASK_I32 ? (float)((const int*)mask)[v] : (float)((const uint8_t*)mask)[v];
 }
 // row r of batch element blockIdx.y: r < N a copy of pos and of the mask as float, else the midpoint of edge r - N
-__global__ __launch_bounds__(MT_BLOCK) void k_ts_verts(int N, long long E, const float* __restrict__ pos, const void* __restrict__ mask, int mask_type,
+__global__ __launch_bounds__(RUN_BLOCK) void k_ts_verts(int N, long long E, const float* __restrict__ pos, const void* __restrict__ mask, int mask_type,
                                                        const long long* __restrict__ edges, float* __restrict__ new_v, float* __restrict__ new_mask)
 {
 #pragma clang fp contract(off)
-    const long long r = (long long)blockIdx.x * MT_BLOCK + threadIdx.x, R = (long long)N + E;
+    const long long r = (long long)blockIdx.x * RUN_BLOCK + threadIdx.x, R = (long long)N + E;
     if (r >= R) return;
     const size_t b = blockIdx.y;
     const float* p = pos + 3 * b * (size_t)N;
@@ -251,18 +250,18 @@ __device__ __forceinline__ long long ts_mid(int N, long long E, const uint32_t* 
                                             long long x, long long y)
 {
     const long long a = x < y ? x : y, b = x < y ? y : x;
-    const long long lo = a ? run[a - 1] : 0, first = urun[a];
+    const long long lo = (long long)run_start(run, (size_t)a), first = urun[a];
     long long n = (long long)urun[a + 1] - first;
     if (first + n > E) n = E - first;
-    const long long at = mt_search_run(list, 1, lo, lo + n, b);
+    const long long at = run_search(list, 1, lo, lo + n, b);
     return at < 0 ? -1 : (long long)N + first + (at - lo);
 }
 template <typename Idx>
-__global__ __launch_bounds__(MT_BLOCK) void k_ts_tets(int N, int F, long long E, const Idx* __restrict__ tet, const uint32_t* __restrict__ run,
+__global__ __launch_bounds__(RUN_BLOCK) void k_ts_tets(int N, int F, long long E, const Idx* __restrict__ tet, const uint32_t* __restrict__ run,
                                                       const uint32_t* __restrict__ urun, const uint32_t* __restrict__ list, long long* __restrict__ new_tets,
                                                       long long* __restrict__ sub_to_parent)
 {
-    const size_t f = (size_t)blockIdx.x * MT_BLOCK + threadIdx.x;
+    const size_t f = (size_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
     if (f >= (size_t)F) return;
     long long t[4];
     mt_load_tet(tet, f, t);
@@ -308,11 +307,11 @@ int tgs_tet_compact_select(void* stream, int N, int F, const float* sdf, const v
         return hip_status("tgs_tet_compact_select");
     if (F == 0) return TGS_OK;
     long long* cnt = (long long*)counts;
-    if (tet_is_int64) hipLaunchKernelGGL(k_tg_select<long long>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, sdf, (const long long*)tet, keep, threshold, w.bits, w.kept, w.blk, cnt);
-    else              hipLaunchKernelGGL(k_tg_select<int>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, sdf, (const int*)tet, keep, threshold, w.bits, w.kept, w.blk, cnt);
-    mt_scan(st, w.blk, mt_blocks((size_t)F), w.scan, cnt + 0);
-    hipLaunchKernelGGL(k_tg_popc, mt_grid(words), dim3(MT_BLOCK), 0, st, words, (const unsigned long long*)w.bits, w.wpre);
-    mt_scan(st, w.wpre, words, w.scan, cnt + 1);
+    if (tet_is_int64) hipLaunchKernelGGL(k_tg_select<long long>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, sdf, (const long long*)tet, keep, threshold, w.bits, w.kept, w.blk, cnt);
+    else              hipLaunchKernelGGL(k_tg_select<int>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, sdf, (const int*)tet, keep, threshold, w.bits, w.kept, w.blk, cnt);
+    run_scan(st, w.blk, run_blocks((size_t)F), w.scan, cnt + 0);
+    hipLaunchKernelGGL(k_tg_popc, run_grid(words), dim3(RUN_BLOCK), 0, st, words, (const unsigned long long*)w.bits, w.wpre);
+    run_scan(st, w.wpre, words, w.scan, cnt + 1);
     return hip_status("tgs_tet_compact_select");
 }
 
@@ -335,17 +334,17 @@ int tgs_tet_compact_emit(void* stream, int N, int F, const void* tet, int tet_is
     if (member_workspace) tg_compact_carve(other, (char*)member_workspace, (size_t)N, (size_t)F);
     const long long Fk = n_tets, Nk = n_verts;
 #define TG_EMIT_TETS(I, O)                                                                                                                            \
-    hipLaunchKernelGGL((k_tg_emit_tets<I, O>), mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, Fk, (const I*)tet, (const uint8_t*)w.kept, (const uint32_t*)w.blk, \
+    hipLaunchKernelGGL((k_tg_emit_tets<I, O>), run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, Fk, (const I*)tet, (const uint8_t*)w.kept, (const uint32_t*)w.blk, \
                        (const unsigned long long*)w.bits, (const uint32_t*)w.wpre, (O*)new_tets, (O*)new_tet_idx_to_old)
     if (tet_is_int64) { if (out_is_int64) TG_EMIT_TETS(long long, long long); else TG_EMIT_TETS(long long, int); }
     else              { if (out_is_int64) TG_EMIT_TETS(int, long long); else TG_EMIT_TETS(int, int); }
 #undef TG_EMIT_TETS
     const int mbytes = tg_mask_bytes(mask_type);
     if (out_is_int64)
-        hipLaunchKernelGGL(k_tg_emit_verts<long long>, mt_grid((size_t)N), dim3(MT_BLOCK), 0, st, N, Nk, (const unsigned long long*)w.bits, (const uint32_t*)w.wpre, pos, sdf, mask, mbytes,
+        hipLaunchKernelGGL(k_tg_emit_verts<long long>, run_grid((size_t)N), dim3(RUN_BLOCK), 0, st, N, Nk, (const unsigned long long*)w.bits, (const uint32_t*)w.wpre, pos, sdf, mask, mbytes,
                            (const unsigned long long*)other.bits, (long long*)unique_vtx, new_pos, new_sdf, new_mask, (int*)member);
     else
-        hipLaunchKernelGGL(k_tg_emit_verts<int>, mt_grid((size_t)N), dim3(MT_BLOCK), 0, st, N, Nk, (const unsigned long long*)w.bits, (const uint32_t*)w.wpre, pos, sdf, mask, mbytes,
+        hipLaunchKernelGGL(k_tg_emit_verts<int>, run_grid((size_t)N), dim3(RUN_BLOCK), 0, st, N, Nk, (const unsigned long long*)w.bits, (const uint32_t*)w.wpre, pos, sdf, mask, mbytes,
                            (const unsigned long long*)other.bits, (int*)unique_vtx, new_pos, new_sdf, new_mask, (int*)member);
     return hip_status("tgs_tet_compact_emit");
 }
@@ -370,13 +369,13 @@ int tgs_tet_subdivide_edges(void* stream, int N, int F, const void* tet, int tet
         return hip_status("tgs_tet_subdivide_edges");
     if (F == 0) return TGS_OK;
     long long* cnt = (long long*)counts;
-    if (tet_is_int64) hipLaunchKernelGGL(k_ts_count<long long>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (const long long*)tet, w.run, cnt);
-    else              hipLaunchKernelGGL(k_ts_count<int>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (const int*)tet, w.run, cnt);
-    mt_scan(st, w.run, (size_t)N + 1, w.scan, (long long*)nullptr);
-    if (tet_is_int64) hipLaunchKernelGGL(k_ts_fill<long long>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (const long long*)tet, w.run, w.list);
-    else              hipLaunchKernelGGL(k_ts_fill<int>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (const int*)tet, w.run, w.list);
-    hipLaunchKernelGGL(k_ts_sort_unique, mt_grid((size_t)N + 1), dim3(MT_BLOCK), 0, st, N, F, (const uint32_t*)w.run, w.list, w.urun);
-    mt_scan(st, w.urun, (size_t)N + 1, w.scan, cnt + 0);
+    if (tet_is_int64) hipLaunchKernelGGL(k_ts_count<long long>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (const long long*)tet, w.run, cnt);
+    else              hipLaunchKernelGGL(k_ts_count<int>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (const int*)tet, w.run, cnt);
+    run_scan(st, w.run, (size_t)N + 1, w.scan, (long long*)nullptr);
+    if (tet_is_int64) hipLaunchKernelGGL(k_ts_fill<long long>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (const long long*)tet, w.run, w.list);
+    else              hipLaunchKernelGGL(k_ts_fill<int>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (const int*)tet, w.run, w.list);
+    hipLaunchKernelGGL(k_ts_sort_unique, run_grid((size_t)N + 1), dim3(RUN_BLOCK), 0, st, N, F, (const uint32_t*)w.run, w.list, w.urun);
+    run_scan(st, w.urun, (size_t)N + 1, w.scan, cnt + 0);
     return hip_status("tgs_tet_subdivide_edges");
 }
 
@@ -395,17 +394,17 @@ int tgs_tet_subdivide_emit(void* stream, int N, int F, int B, int64_t E, const f
     if (tg_subdiv_carve(w, (char*)workspace, (size_t)N, (size_t)F) > workspace_bytes)
         return set_error(TGS_ERR_INVALID, "tgs_tet_subdivide_emit: workspace smaller than tgs_tet_subdivide_workspace_bytes(N, F)");
     long long* ed = (long long*)edges;
-    hipLaunchKernelGGL(k_ts_edges, mt_grid((size_t)N), dim3(MT_BLOCK), 0, st, N, (long long)E, (const uint32_t*)w.run, (const uint32_t*)w.urun, (const uint32_t*)w.list, ed);
+    hipLaunchKernelGGL(k_ts_edges, run_grid((size_t)N), dim3(RUN_BLOCK), 0, st, N, (long long)E, (const uint32_t*)w.run, (const uint32_t*)w.urun, (const uint32_t*)w.list, ed);
     if (B > 0) {
-        dim3 grid = mt_grid((size_t)N + (size_t)E);
+        dim3 grid = run_grid((size_t)N + (size_t)E);
         grid.y = (unsigned)B;
-        hipLaunchKernelGGL(k_ts_verts, grid, dim3(MT_BLOCK), 0, st, N, (long long)E, pos, mask, mask_type, (const long long*)ed, new_v, new_mask);
+        hipLaunchKernelGGL(k_ts_verts, grid, dim3(RUN_BLOCK), 0, st, N, (long long)E, pos, mask, mask_type, (const long long*)ed, new_v, new_mask);
     }
     if (tet_is_int64)
-        hipLaunchKernelGGL(k_ts_tets<long long>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (long long)E, (const long long*)tet, (const uint32_t*)w.run, (const uint32_t*)w.urun,
+        hipLaunchKernelGGL(k_ts_tets<long long>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (long long)E, (const long long*)tet, (const uint32_t*)w.run, (const uint32_t*)w.urun,
                            (const uint32_t*)w.list, (long long*)new_tets, (long long*)sub_to_parent);
     else
-        hipLaunchKernelGGL(k_ts_tets<int>, mt_grid((size_t)F), dim3(MT_BLOCK), 0, st, N, F, (long long)E, (const int*)tet, (const uint32_t*)w.run, (const uint32_t*)w.urun,
+        hipLaunchKernelGGL(k_ts_tets<int>, run_grid((size_t)F), dim3(RUN_BLOCK), 0, st, N, F, (long long)E, (const int*)tet, (const uint32_t*)w.run, (const uint32_t*)w.urun,
                            (const uint32_t*)w.list, (long long*)new_tets, (long long*)sub_to_parent);
     return hip_status("tgs_tet_subdivide_emit");
 }

@@ -25,10 +25,9 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _mesh
-from .diff_gaussian_rasterization import _C as _rast_c
+from . import _host
+from ._host import _F, _I, _L, _P, _Z, guard as _guard, need_device as _need_device, ok as _ok, raw_stream as _raw_stream
 
-_P, _I, _L, _Z, _F = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
 _HEAD = [_P, _L, _I, _P, _P, _P, _I, _I, _I, _I]      # stream, N, n_input_dims, x, params, levels, n_levels, n_features, log2_hashmap_size, active_levels
 SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_raster.h declares them (every pointer is a c_void_p)
     "tgs_hashgrid_workspace_bytes": (_Z, [_L, _I, _I]),
@@ -39,14 +38,12 @@ SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_r
 }
 
 
-def declare(lib: C.CDLL) -> C.CDLL:
+def declare(lib):
     """applies ``SIGNATURES`` to a handle of the native library -> the handle"""
-    for name, (restype, argtypes) in SIGNATURES.items():
-        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
-    return lib
+    return _host.declare(lib, SIGNATURES)
 
 
-_lib = declare(_rast_c._lib)
+_lib = declare(_host.lib)
 MAX_POINTS = 1 << 25
 MAX_LEVELS = 16
 FUSED_WIDTHS = (16, 32, 64)
@@ -138,26 +135,6 @@ def _records(levels):
     return arr
 
 
-def _ok(r: int) -> None:
-    if r < 0:
-        raise _rast_c._err(r)
-
-
-def _guard(dev: torch.device):
-    return torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else _mesh._NO_GUARD
-
-
-def _need_device(**tensors) -> torch.device:
-    """checked last, behind everything that can be said about the arguments without a device -> the one device"""
-    for name, t in tensors.items():
-        if not t.is_cuda:
-            raise RuntimeError(f"youreditableavatar_amd.hashgrid has no CPU path: {name} must be on a HIP device")
-    devs = {t.device for t in tensors.values()}
-    if len(devs) != 1:
-        raise RuntimeError("all tensors must be on one device, got " + ", ".join(f"{n} on {t.device}" for n, t in tensors.items()))
-    return next(iter(devs))
-
-
 def _check_points(x) -> int:
     if not isinstance(x, torch.Tensor):
         raise RuntimeError("x must be a tensor")
@@ -184,14 +161,13 @@ def _check_active(active_levels, n_levels: int) -> int:
 
 
 def _workspace(n_params: int, hidden: int, n_out: int, dev: torch.device):
-    nbytes = int(_lib.tgs_hashgrid_workspace_bytes(n_params, hidden, n_out))
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+    return _host.workspace(_lib.tgs_hashgrid_workspace_bytes(n_params, hidden, n_out), dev)
 
 
 def _head(dev, N, x, params, levels, active):
     """the arguments every native call starts with; the record array is returned too, to keep it alive across the call"""
     recs = _records(levels)
-    return recs, (_mesh._raw_stream(dev.index), N, 3, x.data_ptr(), params.data_ptr(), recs, len(levels), 2, _log2_of(levels), active)
+    return recs, (_raw_stream(dev.index), N, 3, x.data_ptr(), params.data_ptr(), recs, len(levels), 2, _log2_of(levels), active)
 
 
 # ---- the encoding ----------------------------------------------------------------------------------------------------------------------
@@ -243,7 +219,7 @@ def hashgrid_encode(x: torch.Tensor, params: torch.Tensor, levels: Sequence[Leve
     n_entries = _check_levels(levels)
     _check_params(params, n_entries)
     active = _check_active(active_levels, len(levels))
-    dev = _need_device(x=x, params=params)
+    dev = _need_device("hashgrid", x=x, params=params)
     levels = tuple(levels)
     if torch.is_grad_enabled() and (x.requires_grad or params.requires_grad):
         return _Encode.apply(x, params, levels, active, N, dev)
@@ -358,7 +334,7 @@ def sdf_field(x: torch.Tensor, params: torch.Tensor, levels: Sequence[Level], W1
     H, D = _check_weights(W1, W2, 2 * len(levels))
     bbox = _check_bbox(bbox)
     bias = float(bias)
-    dev = _need_device(x=x, params=params, W1=W1, W2=W2)
+    dev = _need_device("hashgrid", x=x, params=params, W1=W1, W2=W2)
     levels = tuple(levels)
     if torch.is_grad_enabled() and (x.requires_grad or params.requires_grad or W1.requires_grad or W2.requires_grad):
         return _Field.apply(x, params, W1, W2, levels, active, bbox, bias, N, H, D, dev)

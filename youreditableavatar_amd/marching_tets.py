@@ -13,15 +13,13 @@ compare with.
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import torch
 
-from . import _mesh
-from .diff_gaussian_rasterization import _C as _rast_c
+from . import _host
+from ._host import _I, _L, _P, _Z, guard as _guard, index_error as _index_error, index_rows as _index_rows, ok as _ok, raw_stream as _raw_stream, workspace as _workspace
 
-_P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_raster.h declares them (every pointer is a c_void_p)
     "tgs_marching_tets_workspace_bytes": (_Z, [_I, _I]),
     "tgs_marching_tets_table_bytes": (_Z, [_L]),
@@ -33,70 +31,68 @@ SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_r
 }
 
 
-def declare(lib: C.CDLL) -> C.CDLL:
+def declare(lib):
     """applies ``SIGNATURES`` to a handle of the native library -> the handle"""
-    for name, (restype, argtypes) in SIGNATURES.items():
-        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
-    return lib
+    return _host.declare(lib, SIGNATURES)
 
 
-_lib = declare(_rast_c._lib)
+_lib = declare(_host.lib)
 MAX_ROWS = (1 << 31) - 1
+MASK_TYPES = {torch.int32: 0, torch.int64: 1, torch.float32: 2, torch.uint8: 3, torch.bool: 3}     # what a keep / edit mask of ``tet_grid`` may be stored as
 KEYS = ("verts", "faces", "face_to_tet_idx", "valid_tets", "interp_v")
+
+
+def check(module_name: str, named, N: Optional[int] = None, each: bool = False) -> torch.device:
+    """The argument check of the calls on a tetrahedral grid, here and in ``tet_grid``.  ``named``: (name, tensor, kind) with kind in pos / sdf / tet /
+    mask; ``N``: the rows sdf and mask must have.  Types, then shapes and dtypes with the row limit, then the device -> the one device of all of them.
+    ``each``: the row limit is said once for the first and the last tensor, behind every shape."""
+    for name, t, _ in named:
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{name} must be a tensor")
+    for name, t, kind in named:
+        got = f"got {t.dtype} {tuple(t.shape)}"
+        if kind == "pos" and (t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3):
+            raise RuntimeError(f"expected float32 {name} of shape [N,3], {got}")
+        if kind == "sdf" and (t.dtype != torch.float32 or tuple(t.shape) not in ((N,), (N, 1))):
+            raise RuntimeError(f"expected float32 {name} of shape [{N}] or [{N},1], {got}")
+        if kind == "tet" and (t.dtype not in (torch.int32, torch.int64) or t.dim() != 2 or t.shape[1] != 4):
+            raise RuntimeError(f"expected int32 or int64 {name} of shape [F,4], {got}")
+        if kind == "mask" and (t.dtype not in MASK_TYPES or tuple(t.shape) not in ((N,), (N, 1))):
+            raise RuntimeError(f"expected an int32, int64, float32 or one-byte {name} of shape [{N}] or [{N},1], {got}")
+        if not each and t.shape[0] > MAX_ROWS:
+            raise RuntimeError(f"{name} has {t.shape[0]} rows; at most 2^31 - 1")
+    (a, ta, _), (b, tb, _) = named[0], named[-1]
+    if each and (ta.shape[0] > MAX_ROWS or tb.shape[0] > MAX_ROWS):
+        raise RuntimeError(f"{a} has {ta.shape[0]} rows and {b} {tb.shape[0]}; at most 2^31 - 1 each")
+    return _host.need_device(module_name, **{name: t for name, t, _ in named})
 
 
 def _check(pos: torch.Tensor, sdf: torch.Tensor, tet: torch.Tensor) -> torch.device:
     """types, shapes and dtypes, then the device: everything that can be said before a native call -> the device"""
-    for name, t in (("pos", pos), ("sdf", sdf), ("tet", tet)):
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{name} must be a tensor")
-    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
-        raise RuntimeError(f"expected float32 pos of shape [N,3], got {pos.dtype} {tuple(pos.shape)}")
-    N = int(pos.shape[0])
-    if sdf.dtype != torch.float32 or tuple(sdf.shape) not in ((N,), (N, 1)):
-        raise RuntimeError(f"expected float32 sdf of shape [{N}] or [{N},1], got {sdf.dtype} {tuple(sdf.shape)}")
-    if tet.dtype not in (torch.int32, torch.int64) or tet.dim() != 2 or tet.shape[1] != 4:
-        raise RuntimeError(f"expected int32 or int64 tet of shape [F,4], got {tet.dtype} {tuple(tet.shape)}")
-    if N > MAX_ROWS or tet.shape[0] > MAX_ROWS:
-        raise RuntimeError(f"pos has {N} rows and tet {tet.shape[0]}; at most 2^31 - 1 each")
-    for name, t in (("pos", pos), ("sdf", sdf), ("tet", tet)):
-        if not t.is_cuda:
-            raise RuntimeError(f"youreditableavatar_amd.marching_tets has no CPU path: {name} must be on a HIP device")
-    if not (pos.device == sdf.device == tet.device):
-        raise RuntimeError(f"all tensors must be on one device, got pos on {pos.device}, sdf on {sdf.device}, tet on {tet.device}")
-    return pos.device
-
-
-def _ok(r: int) -> None:
-    if r < 0:
-        raise _rast_c._err(r)
+    return check("marching_tets", (("pos", pos, "pos"), ("sdf", sdf, "sdf"), ("tet", tet, "tet")), int(pos.shape[0]) if isinstance(pos, torch.Tensor) and pos.dim() else None, each=True)
 
 
 def _forward(pos: torch.Tensor, sdf: torch.Tensor, tet: torch.Tensor, dev: torch.device):
     """checked, detached inputs -> (verts, faces, face_to_tet_idx, valid_tets, interp_v); two read-backs"""
     N, F = int(pos.shape[0]), int(tet.shape[0])
-    pos, sdf, tet = pos.contiguous(), sdf.reshape(-1).contiguous(), tet.contiguous()
-    if tet.data_ptr() % 16:                                                     # (a view that starts inside a row's 16 bytes: the kernels load whole rows)
-        tet = tet.clone()
+    pos, sdf, tet = pos.contiguous(), sdf.reshape(-1).contiguous(), _index_rows(tet)
     is64 = int(tet.dtype == torch.int64)
     new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
     valid = new((F,), torch.bool)
     empty = lambda: (new((0, 3), torch.float32), new((0, 3), torch.int64), new((0,), torch.int64), valid, new((0, 2), torch.int64))
     if F == 0:
         return empty()
-    with torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else _mesh._NO_GUARD:
-        st = _mesh._raw_stream(dev.index)
+    with _guard(dev):
+        st = _raw_stream(dev.index)
         counts = new((4,), torch.int64)
-        nbytes = int(_lib.tgs_marching_tets_workspace_bytes(N, F))
-        ws = new((nbytes,), torch.uint8)
+        ws, nbytes = _workspace(_lib.tgs_marching_tets_workspace_bytes(N, F), dev)
         _ok(_lib.tgs_marching_tets_classify(st, N, F, sdf.data_ptr(), tet.data_ptr(), is64, valid.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes))
         n_one, n_two, bad, _ = counts.tolist()                                  # the first read-back
         if bad:
-            raise RuntimeError(f"tet holds a vertex index outside [0, {N}): pos has {N} rows (code -1)")
+            raise _index_error("tet", N, f"pos has {N} rows")
         if n_one + n_two == 0:
             return empty()
-        tbytes = int(_lib.tgs_marching_tets_table_bytes(3 * n_one + 4 * n_two))
-        table = new((tbytes,), torch.uint8)
+        table, tbytes = _workspace(_lib.tgs_marching_tets_table_bytes(3 * n_one + 4 * n_two), dev)
         _ok(_lib.tgs_marching_tets_edges(st, N, F, tet.data_ptr(), is64, n_one, n_two, counts.data_ptr(), ws.data_ptr(), nbytes, table.data_ptr(), tbytes))
         M = int(counts[3].item())                                               # the second read-back
         T = n_one + 2 * n_two
@@ -124,11 +120,10 @@ class _MarchingTets(torch.autograd.Function):
         dev, N, M = ctx.dev, int(pos.shape[0]), int(interp_v.shape[0])
         d_pos = torch.empty((N, 3), dtype=torch.float32, device=dev) if need_pos else None
         d_sdf = torch.empty((N,), dtype=torch.float32, device=dev) if need_sdf else None
-        with torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else _mesh._NO_GUARD:
-            nbytes = int(_lib.tgs_marching_tets_backward_workspace_bytes(N, M))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with _guard(dev):
+            ws, nbytes = _workspace(_lib.tgs_marching_tets_backward_workspace_bytes(N, M), dev)
             p, s, g = pos.detach().contiguous(), sdf.detach().reshape(-1).contiguous(), g_verts.contiguous()
-            _ok(_lib.tgs_marching_tets_backward(_mesh._raw_stream(dev.index), N, M, p.data_ptr(), s.data_ptr(), interp_v.data_ptr(), g.data_ptr(),
+            _ok(_lib.tgs_marching_tets_backward(_raw_stream(dev.index), N, M, p.data_ptr(), s.data_ptr(), interp_v.data_ptr(), g.data_ptr(),
                                                 d_pos.data_ptr() if need_pos else None, d_sdf.data_ptr() if need_sdf else None, ws.data_ptr(), nbytes))
         return d_pos, d_sdf.reshape(sdf.shape) if need_sdf else None, None
 

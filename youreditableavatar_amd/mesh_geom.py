@@ -13,15 +13,13 @@ atomics, so two runs give the same bits, forward and backward.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
 
-from . import _mesh
-from .diff_gaussian_rasterization import _C as _rast_c
+from . import _host
+from ._host import _I, _L, _P, _Z, guard as _guard, index_error as _index_error, need_device as _need_device, ok as _ok, raw_stream as _raw_stream
 
-_P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_raster.h declares them (every pointer is a c_void_p)
     "tgs_meshgeom_workspace_bytes": (_Z, [_I, _I]),
     "tgs_meshgeom_table_bytes": (_Z, [_I]),
@@ -37,25 +35,14 @@ SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_r
 }
 
 
-def declare(lib: C.CDLL) -> C.CDLL:
+def declare(lib):
     """applies ``SIGNATURES`` to a handle of the native library -> the handle"""
-    for name, (restype, argtypes) in SIGNATURES.items():
-        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
-    return lib
+    return _host.declare(lib, SIGNATURES)
 
 
-_lib = declare(_rast_c._lib)
+_lib = declare(_host.lib)
 MAX_VERTICES = (1 << 31) - 1
 MAX_FACES = ((1 << 32) - 1) // 3   # incidence entries 3 * face + corner and edge numbers are 32-bit
-
-
-def _ok(r: int) -> None:
-    if r < 0:
-        raise _rast_c._err(r)
-
-
-def _guard(dev: torch.device):
-    return torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else _mesh._NO_GUARD
 
 
 def _check_faces(faces) -> int:
@@ -78,17 +65,6 @@ def _check_rows(name: str, t) -> int:
     return int(t.shape[0])
 
 
-def _need_device(**tensors) -> torch.device:
-    """checked last, behind everything that can be said about the arguments without a device -> the one device"""
-    for name, t in tensors.items():
-        if not t.is_cuda:
-            raise RuntimeError(f"youreditableavatar_amd.mesh_geom has no CPU path: {name} must be on a HIP device")
-    devs = {t.device for t in tensors.values()}
-    if len(devs) != 1:
-        raise RuntimeError("all tensors must be on one device, got " + ", ".join(f"{n} on {t.device}" for n, t in tensors.items()))
-    return next(iter(devs))
-
-
 class MeshTopology:
     """What ``mesh_topology`` built for one ``faces`` array: ``edges`` [E,2] int64 (``None`` when built with ``edges=False``), and, for the kernels, the
     vertex -> (face, corner) incidence (``inc_end`` [V+1], ``inc`` [3F]: the runs' ends and the entries ``3 * face + corner``) and the edges' runs
@@ -108,8 +84,7 @@ class MeshTopology:
 
 
 def _workspace(V: int, F: int, dev: torch.device):
-    nbytes = int(_lib.tgs_meshgeom_workspace_bytes(V, F))
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+    return _host.workspace(_lib.tgs_meshgeom_workspace_bytes(V, F), dev)
 
 
 def _faces_arg(faces: torch.Tensor):
@@ -125,28 +100,27 @@ def mesh_topology(faces: torch.Tensor, num_vertices: int, edges: bool = True) ->
     if isinstance(num_vertices, bool) or not isinstance(num_vertices, int) or not 0 <= num_vertices <= MAX_VERTICES:
         raise RuntimeError(f"num_vertices must be an int in [0, 2^31 - 1], got {num_vertices!r}")
     V = num_vertices
-    dev = _need_device(faces=faces)
+    dev = _need_device("mesh_geom", faces=faces)
     words = lambda n, zero=False: (torch.zeros if zero else torch.empty)((n,), dtype=torch.int32, device=dev)
     if F and not V:
-        raise RuntimeError(f"faces holds a vertex index outside [0, {V}): the mesh has {V} vertices (code -1)")
+        raise _index_error("faces", V, f"the mesh has {V} vertices")
     if not F:
         return MeshTopology(V, F, 0, dev, words(V + 1, True), words(0), torch.empty((0, 2), dtype=torch.int64, device=dev) if edges else None,
                             words(V + 1, True), words(V + 1, True), words(0))
     faces, is64 = _faces_arg(faces)
     with _guard(dev):
-        st = _mesh._raw_stream(dev.index)
+        st = _raw_stream(dev.index)
         ws, nbytes = _workspace(V, F, dev)
         counts = torch.empty((4,), dtype=torch.int64, device=dev)
         inc_end, edge_end, max_end = words(V + 1), words(V + 1 if edges else 0), words(V + 1 if edges else 0)
         table, tbytes = None, 0
         if edges:
-            tbytes = int(_lib.tgs_meshgeom_table_bytes(F))
-            table = torch.empty(tbytes, dtype=torch.uint8, device=dev)
+            table, tbytes = _host.workspace(_lib.tgs_meshgeom_table_bytes(F), dev)
         _ok(_lib.tgs_meshgeom_topology_count(st, V, F, faces.data_ptr(), is64, inc_end.data_ptr(), edge_end.data_ptr() if edges else None,
                                               max_end.data_ptr() if edges else None, counts.data_ptr(), table.data_ptr() if edges else None, tbytes, ws.data_ptr(), nbytes))
         E, bad, _, _ = counts.tolist()                                          # the read-back
         if bad:
-            raise RuntimeError(f"faces holds a vertex index outside [0, {V}): the mesh has {V} vertices (code -1)")
+            raise _index_error("faces", V, f"the mesh has {V} vertices")
         inc, edge_rows, max_list = words(3 * F), torch.empty((E, 2), dtype=torch.int64, device=dev) if edges else None, words(E)
         _ok(_lib.tgs_meshgeom_topology_fill(st, V, F, faces.data_ptr(), is64, E, inc_end.data_ptr(), inc.data_ptr(), edge_end.data_ptr() if edges else None,
                                              max_end.data_ptr() if edges else None, edge_rows.data_ptr() if edges else None, max_list.data_ptr() if edges else None,
@@ -174,7 +148,7 @@ def _check_normals(v_pos, faces, topology):
     V, F = _check_rows("v_pos", v_pos), _check_faces(faces)
     if topology is not None:
         _is_topology(topology)
-    dev = _need_device(v_pos=v_pos, faces=faces)
+    dev = _need_device("mesh_geom", v_pos=v_pos, faces=faces)
     if topology is None:
         topology = mesh_topology(faces, V, edges=False)
     _check_topology(topology, V, F, dev, False)
@@ -191,7 +165,7 @@ def _normals_forward(v_pos, faces, topo, V, F, dev):
     v_pos = v_pos.contiguous()
     faces, is64 = _faces_arg(faces)
     with _guard(dev):
-        _ok(_lib.tgs_meshgeom_normals(_mesh._raw_stream(dev.index), V, F, v_pos.data_ptr(), faces.data_ptr(), is64, topo.inc_end.data_ptr(), topo.inc.data_ptr(), out.data_ptr()))
+        _ok(_lib.tgs_meshgeom_normals(_raw_stream(dev.index), V, F, v_pos.data_ptr(), faces.data_ptr(), is64, topo.inc_end.data_ptr(), topo.inc.data_ptr(), out.data_ptr()))
     return out
 
 
@@ -214,9 +188,8 @@ class _VertexNormals(torch.autograd.Function):
         p, g = v_pos.detach().contiguous(), g.contiguous()
         faces, is64 = _faces_arg(faces)
         with _guard(dev):
-            nbytes = int(_lib.tgs_meshgeom_normals_backward_workspace_bytes(V, F))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _ok(_lib.tgs_meshgeom_normals_backward(_mesh._raw_stream(dev.index), V, F, p.data_ptr(), faces.data_ptr(), is64, topo.inc_end.data_ptr(), topo.inc.data_ptr(),
+            ws, nbytes = _host.workspace(_lib.tgs_meshgeom_normals_backward_workspace_bytes(V, F), dev)
+            _ok(_lib.tgs_meshgeom_normals_backward(_raw_stream(dev.index), V, F, p.data_ptr(), faces.data_ptr(), is64, topo.inc_end.data_ptr(), topo.inc.data_ptr(),
                                                     g.data_ptr(), d_pos.data_ptr(), ws.data_ptr(), nbytes))
         return (d_pos,) + (None,) * 5
 
@@ -240,7 +213,7 @@ def _consistency_forward(v_nrm, topo, V, dev):
     v_nrm = v_nrm.contiguous()
     with _guard(dev):
         ws, nbytes = _workspace(V, topo.num_faces, dev)
-        _ok(_lib.tgs_meshgeom_consistency(_mesh._raw_stream(dev.index), V, E, v_nrm.data_ptr(), topo.edges.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes))
+        _ok(_lib.tgs_meshgeom_consistency(_raw_stream(dev.index), V, E, v_nrm.data_ptr(), topo.edges.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes))
     return out
 
 
@@ -262,7 +235,7 @@ class _Consistency(torch.autograd.Function):
         d_nrm = torch.empty((V, 3), dtype=torch.float32, device=dev)
         n, g = v_nrm.detach().contiguous(), g.to(torch.float32).contiguous()
         with _guard(dev):
-            _ok(_lib.tgs_meshgeom_consistency_backward(_mesh._raw_stream(dev.index), V, topo.num_edges, n.data_ptr(), topo.edges.data_ptr(), topo.edge_end.data_ptr(),
+            _ok(_lib.tgs_meshgeom_consistency_backward(_raw_stream(dev.index), V, topo.num_edges, n.data_ptr(), topo.edges.data_ptr(), topo.edge_end.data_ptr(),
                                                         topo.max_end.data_ptr(), topo.max_list.data_ptr(), g.data_ptr(), d_nrm.data_ptr()))
         return d_nrm, None, None, None
 
@@ -272,7 +245,7 @@ def normal_consistency(v_nrm: torch.Tensor, topology: MeshTopology) -> torch.Ten
     differentiable with respect to ``v_nrm``.  No edges: NaN, the mean of nothing."""
     V = _check_rows("v_nrm", v_nrm)
     _is_topology(topology)
-    dev = _need_device(v_nrm=v_nrm)
+    dev = _need_device("mesh_geom", v_nrm=v_nrm)
     _check_topology(topology, V, None, dev, True)
     if torch.is_grad_enabled() and v_nrm.requires_grad:
         return _Consistency.apply(v_nrm, topology, V, dev)
@@ -283,7 +256,7 @@ def mesh_normal_consistency(v_pos: torch.Tensor, faces: torch.Tensor, topology: 
     """``Mesh(v_pos, faces).normal_consistency()``: ``normal_consistency(vertex_normals(v_pos, faces, topology), topology)``"""
     if topology is None:
         _check_rows("v_pos", v_pos), _check_faces(faces)
-        _need_device(v_pos=v_pos, faces=faces)
+        _need_device("mesh_geom", v_pos=v_pos, faces=faces)
         topology = mesh_topology(faces, int(v_pos.shape[0]))
     return normal_consistency(vertex_normals(v_pos, faces, topology), topology)
 
@@ -300,7 +273,7 @@ def _laplacian_forward(v_pos, topo, V, dev, keep: bool):
     v_pos = v_pos.contiguous()
     with _guard(dev):
         ws, nbytes = _workspace(V, topo.num_faces, dev)
-        _ok(_lib.tgs_meshgeom_laplacian(_mesh._raw_stream(dev.index), V, topo.num_edges, v_pos.data_ptr(), topo.edges.data_ptr(), topo.edge_end.data_ptr(),
+        _ok(_lib.tgs_meshgeom_laplacian(_raw_stream(dev.index), V, topo.num_edges, v_pos.data_ptr(), topo.edges.data_ptr(), topo.edge_end.data_ptr(),
                                          topo.max_end.data_ptr(), topo.max_list.data_ptr(),
                                          unit.data_ptr() if keep else None, out.data_ptr(), ws.data_ptr(), nbytes))
     return out, unit
@@ -323,7 +296,7 @@ class _Laplacian(torch.autograd.Function):
         d_pos = torch.empty((V, 3), dtype=torch.float32, device=dev)
         g = g.to(torch.float32).contiguous()
         with _guard(dev):
-            _ok(_lib.tgs_meshgeom_laplacian_backward(_mesh._raw_stream(dev.index), V, topo.num_edges, topo.edges.data_ptr(), topo.edge_end.data_ptr(), topo.max_end.data_ptr(),
+            _ok(_lib.tgs_meshgeom_laplacian_backward(_raw_stream(dev.index), V, topo.num_edges, topo.edges.data_ptr(), topo.edge_end.data_ptr(), topo.max_end.data_ptr(),
                                                       topo.max_list.data_ptr(), unit.data_ptr(), g.data_ptr(), d_pos.data_ptr()))
         return d_pos, None, None, None
 
@@ -334,7 +307,7 @@ def laplacian(v_pos: torch.Tensor, topology: MeshTopology) -> torch.Tensor:
     zero subgradient.  No vertices: NaN, the mean of nothing."""
     V = _check_rows("v_pos", v_pos)
     _is_topology(topology)
-    dev = _need_device(v_pos=v_pos)
+    dev = _need_device("mesh_geom", v_pos=v_pos)
     _check_topology(topology, V, None, dev, True)
     if torch.is_grad_enabled() and v_pos.requires_grad:
         return _Laplacian.apply(v_pos, topology, V, dev)

@@ -13,16 +13,14 @@ topology, bit copies and exact halvings, so the outputs equal the reference's el
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import torch
 
-from . import _mesh
-from .diff_gaussian_rasterization import _C as _rast_c
-from .marching_tets import marching_tets
+from . import _host
+from ._host import _F, _I, _L, _P, _Z, guard as _guard, index_error as _index_error, index_rows as _rows, ok as _ok, ptr as _ptr, raw_stream as _raw_stream, workspace as _workspace
+from .marching_tets import MASK_TYPES, MAX_ROWS, check, marching_tets
 
-_P, _I, _L, _Z, _F = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
 SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_raster.h declares them (every pointer is a c_void_p)
     "tgs_tet_compact_workspace_bytes": (_Z, [_I, _I]),
     "tgs_tet_compact_select": (_I, [_P, _I, _I, _P, _P, _I, _P, _F, _P, _P, _Z]),
@@ -33,62 +31,19 @@ SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_r
 }
 
 
-def declare(lib: C.CDLL) -> C.CDLL:
+def declare(lib):
     """applies ``SIGNATURES`` to a handle of the native library -> the handle"""
-    for name, (restype, argtypes) in SIGNATURES.items():
-        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
-    return lib
+    return _host.declare(lib, SIGNATURES)
 
 
-_lib = declare(_rast_c._lib)
-MAX_ROWS = (1 << 31) - 1
+_lib = declare(_host.lib)
 MAX_SUBDIV_TETS = MAX_ROWS // 8                                                 # new_tets has 8 F rows
-MASK_TYPES = {torch.int32: 0, torch.int64: 1, torch.float32: 2, torch.uint8: 3, torch.bool: 3}
 MARK_KEYS = ("keep_verts_indices", "keep_pos", "keep_sdf", "keep_tets", "keep_tet_idx", "unique_grid_vtx", "new_pos", "new_sdf", "new_tets", "mask_keep_part_in_new_pos")
 
 
-def _ok(r: int) -> None:
-    if r < 0:
-        raise _rast_c._err(r)
-
-
 def _check(named, N: Optional[int] = None) -> torch.device:
-    """``named``: (name, tensor, kind) with kind in pos / sdf / tet / mask / keep -> the one device of all of them"""
-    for name, t, _ in named:
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{name} must be a tensor")
-    for name, t, kind in named:
-        got = f"got {t.dtype} {tuple(t.shape)}"
-        if kind == "pos" and (t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3):
-            raise RuntimeError(f"expected float32 {name} of shape [N,3], {got}")
-        if kind == "sdf" and (t.dtype != torch.float32 or tuple(t.shape) not in ((N,), (N, 1))):
-            raise RuntimeError(f"expected float32 {name} of shape [{N}] or [{N},1], {got}")
-        if kind == "tet" and (t.dtype not in (torch.int32, torch.int64) or t.dim() != 2 or t.shape[1] != 4):
-            raise RuntimeError(f"expected int32 or int64 {name} of shape [F,4], {got}")
-        if kind == "mask" and (t.dtype not in MASK_TYPES or tuple(t.shape) not in ((N,), (N, 1))):
-            raise RuntimeError(f"expected an int32, int64, float32 or one-byte {name} of shape [{N}] or [{N},1], {got}")
-        if t.shape[0] > MAX_ROWS:
-            raise RuntimeError(f"{name} has {t.shape[0]} rows; at most 2^31 - 1")
-    for name, t, _ in named:
-        if not t.is_cuda:
-            raise RuntimeError(f"youreditableavatar_amd.tet_grid has no CPU path: {name} must be on a HIP device")
-    dev = named[0][1].device
-    if any(t.device != dev for _, t, _ in named):
-        raise RuntimeError("all tensors must be on one device, got " + ", ".join(f"{name} on {t.device}" for name, t, _ in named))
-    return dev
-
-
-def _rows(tet: torch.Tensor) -> torch.Tensor:
-    tet = tet.contiguous()
-    return tet.clone() if tet.data_ptr() % 16 else tet                           # (a view that starts inside a row's 16 bytes: the kernels load whole rows)
-
-
-def _guard(dev: torch.device):
-    return torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else _mesh._NO_GUARD
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+    """``named``: (name, tensor, kind) with kind in pos / sdf / tet / mask -> the one device of all of them (``marching_tets.check`` has the rules)"""
+    return check("tet_grid", named, N)
 
 
 class _Selection:
@@ -97,17 +52,16 @@ class _Selection:
     def __init__(self, dev, N, F, tet, sdf=None, keep=None, threshold=0.0):
         self.dev, self.N, self.F, self.tet = dev, N, F, tet
         self.n_tets = self.n_verts = 0
-        self.nbytes = int(_lib.tgs_tet_compact_workspace_bytes(N, F))
-        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self.ws, self.nbytes = _workspace(_lib.tgs_tet_compact_workspace_bytes(N, F), dev)
         if F == 0:
             return
         counts = torch.empty(4, dtype=torch.int64, device=dev)
         with _guard(dev):
-            _ok(_lib.tgs_tet_compact_select(_mesh._raw_stream(dev.index), N, F, _ptr(sdf), tet.data_ptr(), int(tet.dtype == torch.int64), _ptr(keep), float(threshold),
+            _ok(_lib.tgs_tet_compact_select(_raw_stream(dev.index), N, F, _ptr(sdf), tet.data_ptr(), int(tet.dtype == torch.int64), _ptr(keep), float(threshold),
                                             counts.data_ptr(), self.ws.data_ptr(), self.nbytes))
         self.n_tets, self.n_verts, bad, _ = counts.tolist()                      # the read-back
         if bad:
-            raise RuntimeError(f"tet holds a vertex index outside [0, {N}): pos has {N} rows (code -1)")
+            raise _index_error("tet", N, f"pos has {N} rows")
 
     def emit(self, index_dtype, pos=None, sdf=None, mask=None, member_of: Optional["_Selection"] = None):
         """-> (new_tets, new_tet_idx_to_old, unique_vtx, new_pos, new_sdf [N'], new_mask [N'], member [N'] int32), None for what was not given"""
@@ -118,7 +72,7 @@ class _Selection:
         if Fk == 0:
             return out
         with _guard(dev):
-            _ok(_lib.tgs_tet_compact_emit(_mesh._raw_stream(dev.index), self.N, self.F, self.tet.data_ptr(), int(self.tet.dtype == torch.int64), Fk, Nk, _ptr(pos), _ptr(sdf),
+            _ok(_lib.tgs_tet_compact_emit(_raw_stream(dev.index), self.N, self.F, self.tet.data_ptr(), int(self.tet.dtype == torch.int64), Fk, Nk, _ptr(pos), _ptr(sdf),
                                           _ptr(mask), MASK_TYPES[mask.dtype] if mask is not None else 0, None if member_of is None else member_of.ws.data_ptr(),
                                           int(index_dtype == torch.int64), *(_ptr(t) for t in out), self.ws.data_ptr(), self.nbytes))
         return out
@@ -161,14 +115,14 @@ def _subdivide(pos: torch.Tensor, tet: torch.Tensor, mask: Optional[torch.Tensor
     p, t = pos.detach().contiguous(), _rows(tet)
     m = None if mask is None else mask.detach().contiguous()
     with _guard(dev):
-        st = _mesh._raw_stream(dev.index)
-        nbytes = int(_lib.tgs_tet_subdivide_workspace_bytes(N, F))
-        ws, counts = new((nbytes,), torch.uint8), new((4,), torch.int64)
+        st = _raw_stream(dev.index)
+        ws, nbytes = _workspace(_lib.tgs_tet_subdivide_workspace_bytes(N, F), dev)
+        counts = new((4,), torch.int64)
         is64 = int(t.dtype == torch.int64)
         _ok(_lib.tgs_tet_subdivide_edges(st, N, F, t.data_ptr(), is64, counts.data_ptr(), ws.data_ptr(), nbytes))
         E, bad, _, _ = counts.tolist()                                           # the read-back
         if bad:
-            raise RuntimeError(f"tet holds a vertex index outside [0, {N}): pos has {N} rows (code -1)")
+            raise _index_error("tet", N, f"pos has {N} rows")
         if N + E > MAX_ROWS:
             raise RuntimeError(f"{N} vertices and {E} edges: new_v would have more than 2^31 - 1 rows")
         new_v, new_tets, sub, edges = new((B, N + E, 3), torch.float32), new((8 * F, 4), torch.int64), new((8 * F,), torch.int64), new((E, 2), torch.int64)
