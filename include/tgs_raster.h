@@ -859,6 +859,64 @@ int tgs_tet_subdivide_edges(void* stream, int N, int F, const void* tet, int tet
 int tgs_tet_subdivide_emit(void* stream, int N, int F, int B, int64_t E, const float* pos, const void* tet, int tet_is_int64, const void* mask, int mask_type,
                            float* new_v, int64_t* new_tets, float* new_mask, int64_t* sub_to_parent, int64_t* edges, void* workspace, size_t workspace_bytes);
 
+/* ---- mesh signed distance ----
+ * The signed distance from N query points to a triangle mesh: the target of the geometry stage's shape initialisation
+ * (tetgs_spatial/models/geometry/implicit_sdf.py :231-239: pysdf.SDF(vertices, faces)(points), a CPU k-d tree behind a copy to the host and a copy
+ * back per iteration).  vertices [V,3] float32, all finite; faces [F,3] int32 or int64 (faces_is_int64) with indices in [0, V), 1 <= F <=
+ * tgs_meshsdf_max_faces() = 2^28 - 1; points [N,3] float32.  All arithmetic is in double on the float32 inputs; the per-pair functions
+ * (csrc/tgs_mesh_sdf.hpp) are compiled without contraction, so the host build, the device build and the restatement (tests/mesh_sdf_ref.py)
+ * evaluate the same expressions.
+ *
+ * Distance.  d(p) = min over the faces of the exact point-to-triangle distance: the closest point lies on the face, on an edge or at a vertex.  A
+ * face whose cross product is exactly zero takes part as its three segments (ab, bc, ca; the first of the nearest).  Distances are compared as the
+ * squared distances |p - c|^2 of the computed closest points c.  face(p) is the lowest face index among the faces whose computed distance equals
+ * the minimum; closest(p) is that face's closest point, each coordinate rounded to float32; |sdf| is the square root of the minimum, rounded once
+ * to float32.
+ *
+ * Inside.  A point is inside when at least two of the three ray parities along +x, +y and +z are odd.  The parity along axis k, with (a, b) the
+ * other two axes in cyclic order, counts the faces whose projection onto (a, b) contains (p_a, p_b) and whose height over that point is > p_k.
+ * Containment is decided by the three edge values E = (V_a - U_a)(p_b - U_b) - (V_b - U_b)(p_a - U_a), each evaluated on the edge in its canonical
+ * direction -- U is the vertex with the lower index -- and its sign flipped for the face that runs the edge the other way, so two faces that share
+ * an edge see the same number.  Contained: the three oriented values have the same strict sign.  An E that is exactly zero takes the sign of
+ * -(V_b - U_b), and if that is zero too the sign of (V_a - U_a): the top-left rule, an infinitesimal shift of the point that is the same for every
+ * face, so a ray through a shared edge or through a vertex of a closed fan is counted once.  A face whose three values sum to zero (edge-on to the
+ * ray) is not counted; nor is a face that names a vertex twice.  The height is the combination of the three k coordinates with the edge values as
+ * weights (the value of the edge opposite a vertex weighs that vertex), divided by their sum.  Parity does not depend on the faces' orientation.
+ * The majority of three serves meshes that are not closed (a hole turns the parity of the rays that leave through it; two of three rays seldom
+ * do).  Where two solids overlap, parity makes the overlap outside: that is the stated behaviour.
+ *
+ * Result.  sdf = +|sdf| inside, -|sdf| outside (pysdf's sign; the reference negates it).  d == 0: sdf = +0.0 and inside.  A non-finite query point:
+ * sdf and closest NaN, face -1, inside 0; nothing faults and nothing loops.  Each output pointer may be NULL; without out_sdf and out_inside the
+ * parities are not computed.
+ *
+ * The tree.  tgs_meshsdf_build runs on the host and makes no device call: `vertices`, `faces` and `tree` are HOST pointers there.  It writes
+ * tgs_meshsdf_tree_bytes(F) bytes (64 + 128 F): a header, at most 2 F nodes of 32 bytes in depth-first order -- the box rounded outward and padded
+ * by 2^-20 of the mesh's largest |coordinate|, `skip` = the node that follows the node's subtree, so the left child of node i is i + 1 and the
+ * right child is skip[i + 1] -- and the F faces permuted leaf by leaf as records of 64 bytes (the vertices, their indices, the face's number).  A
+ * leaf holds at most 4 faces, in ascending order.  Median splits of the centroids along the longest axis, ties by face number: the depth is at
+ * most 32 by construction and the bound is checked; the build is deterministic, two builds give the same bytes.  The caller copies the bytes to
+ * the device as they are.
+ *
+ * The query.  tgs_meshsdf_query takes DEVICE pointers and enqueues one kernel on `stream`, one lane per point; it allocates nothing and reads
+ * nothing back (no read-back at all: the tree's header is checked by the lanes, and a tree that was not built for this F gives the outputs of a
+ * non-finite point).  mode 0 walks the tree without a stack: down to the leaf behind the nearer box for a starting bound, then the nodes in
+ * depth-first order, into a box unless its lower bound is strictly greater than the best so far (ties are visited) and past its subtree
+ * otherwise; then one more walk for the three parities, into a box whose (a, b) extent contains the point and whose upper k bound is > p_k.
+ * Every loop ends by construction: the node index only grows and is bounded by the node count.  mode 1 visits every face in the caller's order:
+ * the on-device cross-check and the path for tiny meshes.  mode 0 returns the same bits and the same face as mode 1.  No atomics, no scratch
+ * memory; a lane writes its own outputs: determinism, two runs give the same bits.
+ *
+ * Refused with TGS_ERR_INVALID and a message, before any device call: a NULL vertices / faces / tree (or points with N > 0), V < 1, F == 0, F
+ * above the limit, faces_is_int64 outside {0, 1}, a tree buffer smaller than tgs_meshsdf_tree_bytes(F), a mode other than 0 or 1, N < 0; and by
+ * the build: a vertex index outside [0, V), a non-finite vertex.  N == 0 returns without a launch.  tgs_meshsdf_tree_bytes gives 0 for an F
+ * outside the limits.  The host twin of the query, tgs_meshsdf_query_host, is declared in tgs_mesh_sdf_testing.h, which
+ * tgs_raster_testing.h includes. */
+size_t tgs_meshsdf_tree_bytes(int F);
+int tgs_meshsdf_max_faces(void);
+int tgs_meshsdf_build(int V, int F, const float* vertices, const void* faces, int faces_is_int64, void* tree, size_t tree_bytes);
+int tgs_meshsdf_query(void* stream, const void* tree, size_t tree_bytes, int V, int F, const float* vertices, const void* faces, int faces_is_int64, int64_t N,
+                      const float* points, int mode, float* out_sdf, int32_t* out_face, float* out_closest, uint8_t* out_inside);
+
 /* ---- Batched backward (multi-view steps) ----
  * Rasterizer::backward runs its per-Gaussian half (computeCov2DCUDA + preprocessCUDA of backward.cu) once per view; with
  * in-place accumulation that is 192 B of SH read plus 192 B of dL_dsh read AND written per Gaussian per view.  A batch

@@ -9,6 +9,7 @@
 #define TGS_RASTER_TESTING_H
 
 #include <stdint.h>
+#include "tgs_mesh_sdf_testing.h"   /* the host twin of the mesh signed distance query: a header of its own, what is declared HERE is the set of shims above */
 
 #ifdef __cplusplus
 extern "C" {
