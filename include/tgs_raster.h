@@ -917,6 +917,85 @@ int tgs_meshsdf_build(int V, int F, const float* vertices, const void* faces, in
 int tgs_meshsdf_query(void* stream, const void* tree, size_t tree_bytes, int V, int F, const float* vertices, const void* faces, int faces_is_int64, int64_t N,
                       const float* points, int mode, float* out_sdf, int32_t* out_face, float* out_closest, uint8_t* out_inside);
 
+/* ---- mask morphology and blur ----
+ * The image operations of the painting stage between the mesh rasterizer's calls: cv2.erode, cv2.dilate and cv2.GaussianBlur as prepare_mask_proj
+ * (tetgs_inpainter/mask_mesh_0822.py :153-207) and normal_based_inpaint (inpaint_utils.py :27-39) call them, on the device, on `stream`.
+ * An image is [H,W,C] in cv2's layout, 1 <= C <= 4; the source is read through its strides (stride_y, stride_x, stride_c, in elements), dst is
+ * contiguous [H,W,C].  Channels are independent.
+ *
+ * tgs_maskops_morph: op 0 erodes, op 1 dilates; dtype 0 is uint8 (a bool image is one), 1 is float32.  The structuring element is the full
+ * kh x kw rectangle, 1 <= kh, kw <= 64.  The rule is OpenCV's documented one with the default anchor and the default border: the anchor is
+ * a = k / 2 (integer division) per axis, and
+ *     dst(y, x) = min (erode) or max (dilate) of src(y + dy, x + dx) over dy in [-a_h, kh - 1 - a_h], dx in [-a_w, kw - 1 - a_w];
+ * positions outside the image take no part.  So a 2 x 2 dilation of one set pixel at (y, x) sets (y .. y + 1, x .. x + 1), a 5 x 5 one
+ * x - 2 .. x + 2, a 20 x 20 one x - 9 .. x + 10; an erosion does the same with the zeros; k = 1 is the identity; a rectangle larger than the
+ * image is legal.  Exact min / max: no arithmetic.  A float NaN: not defined.  Two launches, a row pass then a column pass, each through LDS;
+ * the workspace is one image.
+ *
+ * tgs_maskops_blur: float32 only.  kw and kh are odd and <= 31, and each dimension of the image must exceed k / 2.  weights_x[kw] and
+ * weights_y[kh] are HOST pointers to the double coefficients (OpenCV's getGaussianKernel: for sigma <= 0 the fixed tables of k = 1, 3, 5, 7, else
+ * sigma = 0.3 ((k - 1) 0.5 - 1) + 0.8; w_i = exp(-(i - k / 2)^2 / (2 sigma^2)), normalised to sum 1, in double); they travel as kernel
+ * arguments.  The border is BORDER_REFLECT_101: index -1 reads 1, index n reads n - 2.  Both passes accumulate in double, tap 0 first; the row
+ * pass keeps doubles in the workspace (one double per element); the value is rounded to float once.  OpenCV rounds the coefficients to float
+ * and sums in float, so it is further from the real-number value than this.
+ *
+ * No atomics; an element is written by one lane: determinism, two runs give the same bits.  The calls allocate nothing, synchronise nothing
+ * and read nothing back.  workspace: tgs_maskops_workspace_bytes(H, W, C, elem_bytes) with elem_bytes 1 (uint8), 4 (float32) or 8 (the blur);
+ * 0 for what is refused.  Refused with TGS_ERR_INVALID and a message, before any launch: an op or dtype outside {0, 1}, C outside [1, 4], a k
+ * outside its limits, an even k for the blur, an image no larger than k / 2 for the blur, W * C above 2^31 - 256 or H above 65535, a NULL
+ * pointer with H * W > 0, a workspace that is too small.  H * W == 0 returns without a launch. */
+size_t tgs_maskops_workspace_bytes(int H, int W, int C, int elem_bytes);
+int tgs_maskops_morph(void* stream, int op, int dtype, int H, int W, int C, const void* src, int64_t stride_y, int64_t stride_x, int64_t stride_c, int kh, int kw,
+                      void* dst, void* workspace, size_t workspace_bytes);
+int tgs_maskops_blur(void* stream, int H, int W, int C, const float* src, int64_t stride_y, int64_t stride_x, int64_t stride_c, int kw, int kh,
+                     const double* weights_x, const double* weights_y, float* dst, void* workspace, size_t workspace_bytes);
+
+/* ---- mesh regions ----
+ * Face selections on a triangle mesh: what refine_region and gen_editing_region_mask (mesh_localization.py :34-67, :133-148) take from MeshLab.
+ * faces[F,3] int32 and the selections (one byte per face, nonzero = selected) are DEVICE pointers; V is the vertex count.  A degenerate face is an
+ * ordinary face.  A face with an index outside [0, V) is never selected and touches no vertex: the kernels check the bounds and never read
+ * through such an index.
+ *
+ * tgs_meshregion_morph runs dilate_iter dilations, then erode_iter erosions, on a copy of sel_in, and writes sel_out[F] and, if vertex_mask is
+ * not NULL, vertex_mask[V]: the vertices some face of sel_out references.
+ *   dilation   MeshLab's apply_selection_dilatation (VertexFromFaceLoose, then FaceFromVertexLoose), the loose rule: a vertex is marked iff
+ *              some incident face is selected; a face is selected iff any of its three vertices is marked.
+ *   erosion    apply_selection_erosion (VertexFromFaceStrict, then FaceFromVertexStrict), the strict rule: a vertex is marked iff it has at
+ *              least one selected incident face and no unselected one; a face stays selected iff all three of its vertices are marked.  A
+ *              boundary vertex whose incident faces are all selected stays marked.
+ * The flags are one word per vertex and rule that holds the number of the iteration that wrote it: plain stores of a single value, cleared
+ * once per call.  The iterations are queued back to back with no read-back.  workspace: tgs_meshregion_workspace_bytes(V, F).
+ *
+ * Components.  Two selected faces are adjacent iff they share an undirected edge: the same unordered pair of distinct vertex indices.  Faces
+ * around a non-manifold edge are all adjacent; sharing only a vertex does not connect.  label[f] is the smallest face index of f's component
+ * and size[f] its face count; an unselected face gets -1 and 0.  The caller keeps a face iff size >= min_faces (the reference deletes the
+ * components strictly smaller).  Duplicate faces count as faces: the reference's remove_duplicate_faces / remove_null_faces are not done.
+ *   tgs_meshregion_components_begin   the edges of the selected faces into the table of csrc/tgs_edge_set.hpp (integer CAS), label[f] = f
+ *   tgs_meshregion_components_rounds  `rounds` rounds: every face pushes its label to its three edge slots (atomicMin), pulls the least,
+ *                                     passes it to the face its old label names, and label[f] = label[label[f]] twice.  A label only falls
+ *                                     and is always a face of the same component, so the fixed point, all labels equal to the least index,
+ *                                     does not depend on the order of the lanes.  *changed (a device int32) becomes 1 iff a label fell in the call's
+ *                                     LAST round, else 0: a whole round in which no label fell is the fixed point.  1 <= rounds <= 16.
+ *                                     rounds_done is the number of rounds of the earlier calls.
+ *   tgs_meshregion_components_finish  size[f] = count[label[f]], the counts by integer atomicAdd
+ * The read-back: the caller reads `changed` back once per call of _rounds (8 rounds per call in youreditableavatar_amd.mesh_region) and stops
+ * at 0; nothing else is read back.  The hard cap: plain propagation alone lowers a label per round along every edge, so F rounds and one
+ * quiet round always suffice, and with the caller's block of at most 16 rounds the count stays below F + 16
+ * (tgs_meshregion_components_max_rounds); a call with rounds_done at the cap returns TGS_ERR_INVALID: the loop never spins.
+ * workspace: tgs_meshregion_components_workspace_bytes(F), the same buffer for the three calls (the table has the power of two >= 4 F slots).
+ *
+ * Integer atomics and plain stores only, no float anywhere: determinism, two runs give the same bits.  F <= 2^28 - 1, iterations <= 2^20.
+ * Refused with TGS_ERR_INVALID and a message: V < 0, F outside the limit, a NULL pointer with F > 0, sel_out == sel_in, an iteration count
+ * outside the limit, rounds outside [1, 16], a workspace that is too small. */
+size_t tgs_meshregion_workspace_bytes(int V, int F);
+int tgs_meshregion_morph(void* stream, int V, int F, const int32_t* faces, const uint8_t* sel_in, int dilate_iter, int erode_iter, uint8_t* sel_out, uint8_t* vertex_mask,
+                         void* workspace, size_t workspace_bytes);
+size_t tgs_meshregion_components_workspace_bytes(int F);
+int tgs_meshregion_components_max_rounds(int F);
+int tgs_meshregion_components_begin(void* stream, int V, int F, const int32_t* faces, const uint8_t* sel, int32_t* label, void* workspace, size_t workspace_bytes);
+int tgs_meshregion_components_rounds(void* stream, int F, int32_t* label, int rounds_done, int rounds, int32_t* changed, void* workspace, size_t workspace_bytes);
+int tgs_meshregion_components_finish(void* stream, int F, const int32_t* label, int32_t* size, void* workspace, size_t workspace_bytes);
+
 /* ---- Batched backward (multi-view steps) ----
  * Rasterizer::backward runs its per-Gaussian half (computeCov2DCUDA + preprocessCUDA of backward.cu) once per view; with
  * in-place accumulation that is 192 B of SH read plus 192 B of dL_dsh read AND written per Gaussian per view.  A batch
