@@ -996,6 +996,67 @@ int tgs_meshregion_components_begin(void* stream, int V, int F, const int32_t* f
 int tgs_meshregion_components_rounds(void* stream, int F, int32_t* label, int rounds_done, int rounds, int32_t* changed, void* workspace, size_t workspace_bytes);
 int tgs_meshregion_components_finish(void* stream, int F, const int32_t* label, int32_t* size, void* workspace, size_t workspace_bytes);
 
+/* ---- mesh ray casting ----
+ * N rays against a triangle mesh: open3d's RaycastingScene.cast_rays as the editing pipeline calls it (mesh_localization.py :150-167 and :89-131,
+ * tetgs_inpainter/mask_mesh_0822.py :209-237), on the tree of the mesh signed distance above: the same bytes serve both queries, and a mesh that
+ * has an SDF needs no second build.  vertices, faces, tree and the limits are tgs_meshsdf_build's.  The per-pair functions (csrc/tgs_mesh_rays.hpp)
+ * are compiled without contraction, so the host build, the device build and the restatement (tests/mesh_rays_ref.py) evaluate the same expressions.
+ *
+ * Ray validity.  A ray is six float32: origin o, direction d.  d is not normalised and t is in units of |d|, as open3d has it.  A ray with a
+ * non-finite component, or with d == (0, 0, 0), is a miss; nothing faults and nothing loops.
+ *
+ * Arithmetic setup.  All arithmetic is in double on the float32 inputs.  kz is the axis of the largest |d_k| (the lowest axis on a tie); kx, ky
+ * are the next two axes in cyclic order, swapped when d[kz] < 0.  Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].  For a vertex P:
+ * A = P - o, Ax = A[kx] - Sx * A[kz], Ay = A[ky] - Sy * A[kz], Az = Sz * A[kz]: a function of the vertex and the ray alone, not of the face (Woop,
+ * Benthin and Wald's watertight construction).
+ *
+ * Hit test.  For a face (A, B, C): U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax.  Two faces that share an edge compute the
+ * same two products for it, so their values for that edge are exact negatives: a ray cannot pass between them.  The face is a candidate unless
+ * one of U, V, W is < 0 and another is > 0; exact zeros belong to both sides.  det = (U + V) + W; a face with det == 0 is no hit (edge-on faces,
+ * faces that name a vertex twice).  t = ((U * Az + V * Bz) + W * Cz) / det; it is a hit when t >= 0 and t is finite.  Both sides of a face are hit.
+ * One rule more than det == 0: a face whose cross product (v1 - v0) x (v2 - v0), in double, is exactly zero is no hit.  Three distinct collinear
+ * vertices give a det that is zero in real numbers and need not round to zero, and such a face has no normal to return: with this rule zero-area
+ * faces never hit.
+ *
+ * Choosing the answer.  The hit of least t, and among equal t the lowest face index: a total order, so the visiting order does not matter.
+ *
+ * Outputs, each pointer may be NULL.  out_t float32 [N]: t, rounded once.  out_face int32 [N]: the face's number in the caller's array.
+ * out_geometry int32 [N]: 0 on a hit.  out_uv float32 [N,2]: (V / det, W / det), so that the point is (1 - u - v) v0 + u v1 + v v2 (embree's
+ * convention, which open3d passes on).  out_normal float32 [N,3]: (v1 - v0) x (v2 - v0), normalised in double and rounded.  On a miss: t = +inf,
+ * both ids -1 (the bits of open3d's INVALID_ID 0xFFFFFFFF), uvs and normals 0.  out_hit_faces uint8 [F]: a lane stores 1 at its hit face with a
+ * plain store; several lanes may store the same value, so the result does not depend on their order.  The caller zeroes the array, or passes the
+ * previous camera's array to accumulate the OR: the fused route for the reference's Python set of primitive_ids.
+ *
+ * The walks.  mode 1 visits every face in the caller's order.  mode 0 walks the tree in depth-first order with the skip links, without a stack, the
+ * children in layout order.  At each node the slab test against the node's box, in double: an axis with d_k == 0 requires lo_k <= o_k <= hi_k and
+ * contributes no interval; otherwise it contributes (lo_k - o_k) / d_k and (hi_k - o_k) / d_k, ordered.  The box is entered when
+ * max(0, entries) <= min(best t so far, exits); ties are entered.  Every loop is bounded by the node count: the node index only grows.  mode 0
+ * returns the bits of mode 1.  The lanes check the tree's header: a tree that was not built for this F gives miss rows.
+ *
+ * Why the rounded slab test is conservative.  The boxes are padded by p = 2^-20 of the mesh's largest |coordinate| m.  A face that mode 1 accepts
+ * at t has U, V, W of one sign as computed; each carries an error of at most 2^-52 (|p1| + |p2|) <= 2^-49 r^2, r the distance from the origin to
+ * the face's farthest vertex (the sheared coordinates are at most 2 r), so in real numbers the ray passes the face's triangle within
+ * delta <= 2^-49 r^2 / s in the plane across kz, s the face's shortest edge as projected along the ray, at a parameter within 2^-50 r / |d[kz]|
+ * of t.  The slab bounds are computed with an error of 2^-52 (|o_k| + m) / |d_k|.  With origins |o_k| <= 64 m, so r <= 2^7 m, and s >= 2^-14 m:
+ * delta <= 2^-21 m = p / 2, and the other two errors stay below 2^-40 m: the ray, in real numbers, is inside the padded box at a parameter that the
+ * rounded bounds still contain.  That is the range for which the argument holds: origins within 64 times the mesh's largest |coordinate|, faces
+ * whose shortest projected edge is at least 2^-14 of it (or, for shorter edges, origins nearer in proportion: delta scales with r^2 / s).  Outside
+ * it mode 0 may skip a face that mode 1 accepts within rounding of its edge; nothing faults.
+ *
+ * tgs_meshrays_occluded: out_occluded uint8 [N] is 1 when some face has a hit with tnear <= t <= tfar.  The walk stops at the first such face (the
+ * answer does not depend on which face it was); mode 0 enters a box when max(0, entries) <= min(tfar, exits).
+ *
+ * One lane per ray, no atomics, no LDS, no per-lane array and no scratch memory (the axis permutation is selects).  The calls take DEVICE pointers,
+ * enqueue one kernel on `stream`, allocate nothing and read nothing back: two runs give the same bits.  Refused with TGS_ERR_INVALID and a message,
+ * before any device call: a NULL tree / vertices / faces (or rays with N > 0, or out_occluded with N > 0), V < 1, F outside [1, 2^28 - 1], N < 0,
+ * faces_is_int64 outside {0, 1}, a tree buffer smaller than tgs_meshsdf_tree_bytes(F), a mode other than 0 or 1, tnear > tfar or a NaN bound.
+ * N == 0 returns without a launch.  The host twins, tgs_meshrays_cast_host and tgs_meshrays_occluded_host, are declared in
+ * tgs_mesh_rays_testing.h, which tgs_raster_testing.h includes. */
+int tgs_meshrays_cast(void* stream, const void* tree, size_t tree_bytes, int V, int F, const float* vertices, const void* faces, int faces_is_int64, int64_t N, const float* rays,
+                      int mode, float* out_t, int32_t* out_face, int32_t* out_geometry, float* out_uv, float* out_normal, uint8_t* out_hit_faces);
+int tgs_meshrays_occluded(void* stream, const void* tree, size_t tree_bytes, int V, int F, const float* vertices, const void* faces, int faces_is_int64, int64_t N, const float* rays,
+                          float tnear, float tfar, int mode, uint8_t* out_occluded);
+
 /* ---- Batched backward (multi-view steps) ----
  * Rasterizer::backward runs its per-Gaussian half (computeCov2DCUDA + preprocessCUDA of backward.cu) once per view; with
  * in-place accumulation that is 192 B of SH read plus 192 B of dL_dsh read AND written per Gaussian per view.  A batch

@@ -10,6 +10,7 @@
 
 #include <stdint.h>
 #include "tgs_mesh_sdf_testing.h"   /* the host twin of the mesh signed distance query: a header of its own, what is declared HERE is the set of shims above */
+#include "tgs_mesh_rays_testing.h"  /* the host twins of the mesh ray casting, likewise */
 
 #ifdef __cplusplus
 extern "C" {

@@ -17,7 +17,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, os.environ.get("TGS_LIB_NAME", "libtgs_raster.so"))       # TGS_LIB_NAME: build a variant next to the default one
 SOURCES = ["tgs_forward.hip", "tgs_backward.hip", "tgs_api.hip", "tgs_shcolor.hip", "tgs_knn.hip", "tgs_loss.hip", "tgs_bind.hip", "tgs_optim.hip", "tgs_reg.hip", "tgs_depth.hip",
            "tgs_feature.hip", "tgs_median.hip", "tgs_mesh.hip", "tgs_mesh_aa.hip", "tgs_mesh_grad.hip", "tgs_marching_tets.hip", "tgs_mesh_geom.hip", "tgs_hashgrid.hip", "tgs_tet_grid.hip", "tgs_mesh_sdf.hip",
-           "tgs_mask_ops.hip", "tgs_mesh_region.hip"]
+           "tgs_mask_ops.hip", "tgs_mesh_region.hip", "tgs_mesh_rays.hip"]
 ARCH = "gfx950"
 # -fno-slp-vectorize: the SLP vectoriser pairs scalar f32 operations into v_pk_fma_f32 / v_pk_mul_f32, which on gfx950 issue no faster than
 # the two scalar instructions (MI355X_MICROARCH.md: packed f32 VALU is an anti-lever) while the pairing costs registers and moves:
@@ -26,8 +26,8 @@ ARCH = "gfx950"
 # 2.04 -> 1.97 ms, the drop-in frame 0.386 -> 0.376 ms.
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function"]
 # Per-source flags.  tgs_mesh_sdf.hip: no fused multiply-add, so that the host build, the device build and the float64 restatement of the
-# per-pair functions evaluate the same expressions (the file carries the pragma as well).
-EXTRA_FLAGS = {"tgs_mesh_sdf.hip": ["-ffp-contract=off"]}
+# per-pair functions evaluate the same expressions (the file carries the pragma as well).  tgs_mesh_rays.hip: the same, for the ray functions.
+EXTRA_FLAGS = {"tgs_mesh_sdf.hip": ["-ffp-contract=off"], "tgs_mesh_rays.hip": ["-ffp-contract=off"]}
 # experiment knobs, e.g. TGS_LIB_NAME=libtgs_raster_x.so TGS_DEFINES="-DTGS_STAMPS=1" python -m youreditableavatar_amd.build --force.  They apply
 # to a NAMED variant only: TGS_DEFINES left in the environment of an ordinary import must not change what the default library is built from
 # (or make a fresh one look stale).
@@ -59,7 +59,7 @@ def source_hash() -> str:
     files = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".cpp"))) 
     for f in files:
         h.update(f.encode()); h.update(open(os.path.join(CSRC, f), "rb").read())
-    for hname in ("tgs_raster.h", "tgs_raster_testing.h", "tgs_mesh_sdf_testing.h"):
+    for hname in ("tgs_raster.h", "tgs_raster_testing.h", "tgs_mesh_sdf_testing.h", "tgs_mesh_rays_testing.h"):
         hp = os.path.join(HERE, "..", "include", hname)
         if os.path.exists(hp):
             h.update(open(hp, "rb").read())
