@@ -1,5 +1,6 @@
 """NumPy restatement of the rules of include/tgs_raster.h, "mesh regions": naive loops over the faces and the edges, components by a plain union-find.
-The yardstick of youreditableavatar_amd.mesh_region; checked itself in tests/test_mesh_region_ref.py on hand meshes."""
+The yardstick of youreditableavatar_amd.mesh_region; checked itself in tests/test_mesh_region_ref.py on hand meshes.  For the launch shapes of
+tests/test_gpu_mesh_region_launch.py: ``face_components_fast``, the same components without the loops, and the named cases ``LAUNCH_CASES``."""
 import numpy as np
 
 
@@ -113,6 +114,53 @@ def keep_large_components(face_mask, faces, V, min_faces):
     return (label >= 0) & (size >= min_faces)
 
 
+def _edges(sel, faces, V):
+    """the sides (u, w), u != w, of the selected faces -> (face [n], edge id [n], number of distinct unordered pairs)"""
+    f = np.nonzero(sel)[0]
+    u, w = faces[f][:, [0, 1, 2]].ravel(), faces[f][:, [1, 2, 0]].ravel()
+    f = np.repeat(f, 3)
+    side = u != w
+    _, edge = np.unique(np.minimum(u, w)[side] * max(V, 1) + np.maximum(u, w)[side], return_inverse=True)
+    return f[side], edge.reshape(-1), int(edge.max()) + 1 if edge.size else 0
+
+
+def face_components_fast(face_mask, faces, V):
+    """``face_components`` without its loops, for the launch shapes: the graph of the faces and their edges (a face is joined to each of its distinct
+    unordered pairs), scipy's components, the least face index per component by np.minimum.at and the sizes by np.bincount -> the same (label, size)"""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    sel, faces = _start(face_mask, faces, V)
+    F = len(faces)
+    f, edge, n_edges = _edges(sel, faces, V)
+    graph = coo_matrix((np.ones(len(f), np.int8), (f, F + edge)), shape=(F + n_edges, F + n_edges))
+    comp = connected_components(graph, directed=False)[1][:F]
+    least = np.full(F + n_edges, F, np.int64)
+    np.minimum.at(least, comp[sel], np.nonzero(sel)[0])
+    count = np.bincount(comp[sel], minlength=F + n_edges)
+    label, size = np.full(F, -1, np.int32), np.zeros(F, np.int32)
+    label[sel], size[sel] = least[comp[sel]], count[comp[sel]]
+    return label, size
+
+
+def table_capacity(F):
+    """the components' edge table: a power of two >= max(64, 4 F)"""
+    cap = 64
+    while cap < 4 * F:
+        cap *= 2
+    return cap
+
+
+def case_properties(V, faces, sel):
+    """what a launch case is named for, counted: the distinct edges of the selected faces (the table's keys), the table's load, the faces on the busiest
+    edge, the sizes of the components in falling order, and the largest |face index - least face index of its component|"""
+    sel, faces = _start(sel, faces, V)
+    _, edge, keys = _edges(sel, faces, V)
+    label, size = face_components_fast(sel, faces, V)
+    on = np.nonzero(sel)[0]
+    return {"keys": keys, "capacity": table_capacity(len(faces)), "load": keys / table_capacity(len(faces)), "busiest": int(np.bincount(edge).max()) if keys else 0,
+            "sizes": sorted((int(size[r]) for r in np.unique(label[on])), reverse=True), "reach": int((on - label[on]).max()) if len(on) else 0}
+
+
 # ---- hand meshes ----
 def strip(n=6):
     """a triangle strip of n faces over n + 2 vertices"""
@@ -137,3 +185,85 @@ def grid(nx=9, ny=7):
         for x in range(nx):
             f += [[idx(x, y), idx(x + 1, y), idx(x + 1, y + 1)], [idx(x, y), idx(x + 1, y + 1), idx(x, y + 1)]]
     return (nx + 1) * (ny + 1), np.array(f, np.int32)
+
+
+# ---- launch cases: (V, faces int32 [F,3], selection bool [F]) by name; tests/test_mesh_region_ref.py counts what each is named for ----
+def _rows(n, order):
+    """a row order of n faces: where the face at row r comes from"""
+    if order == "reversed":
+        return np.arange(n)[::-1].copy()
+    if order == "evens_first":
+        return np.concatenate([np.arange(0, n, 2), np.arange(1, n, 2)])
+    assert order == "random"
+    return np.random.default_rng(n).permutation(n)
+
+
+def strip_permuted(n, order, selection="all"):
+    """strip(n) with its rows permuted; "runs_of_96": every 97th face of the strip (not of the rows) is left out, which cuts it into runs of 96"""
+    V, f = strip(n)
+    rows = _rows(n, order)
+    keep = np.ones(n, bool) if selection == "all" else np.arange(n) % 97 != 96
+    return V, f[rows], keep[rows]
+
+
+def isolated(n, selection="all"):
+    """n triangles over 3 n vertices: no two share a vertex"""
+    sel = np.ones(n, bool) if selection == "all" else np.random.default_rng(n).random(n) < 0.5
+    return 3 * n, np.arange(3 * n, dtype=np.int32).reshape(n, 3), sel
+
+
+def pairs(n=16384):
+    """n / 2 pairs of triangles (4p, 4p+1, 4p+2), (4p+1, 4p, 4p+3) that share the edge (4p, 4p+1) and nothing else, in a seeded row order"""
+    p = 4 * np.arange(n // 2, dtype=np.int32)
+    f = np.concatenate([np.stack([p, p + 1, p + 2], 1), np.stack([p + 1, p, p + 3], 1)])
+    return 2 * n, f[_rows(n, "random")], np.ones(n, bool)
+
+
+def book(n=1000):
+    """n faces (0, 1, k + 2) around the one edge (0, 1), in a seeded row order"""
+    k = np.arange(n, dtype=np.int32)
+    f = np.stack([np.zeros(n, np.int32), np.ones(n, np.int32), k + 2], 1)
+    return n + 2, f[_rows(n, "random")], np.ones(n, bool)
+
+
+def spheres(copies=64, selection="random"):
+    """disjoint copies of icosphere(2) (320 faces, 162 vertices each), the rows of all copies permuted together; "random": 70 % of the faces"""
+    from youreditableavatar_amd import scenes
+    v, f = scenes.icosphere(2)
+    f = np.concatenate([f + i * len(v) for i in range(copies)]).astype(np.int32)
+    n = len(f)
+    sel = np.ones(n, bool) if selection == "all" else np.random.default_rng(copies).random(n) < 0.7
+    return copies * len(v), f[_rows(n, "random")], sel
+
+
+def grid_selected(nx, ny, selection):
+    """grid(nx, ny) with the middle face, a seeded 0.1 % of the faces, or everything but the middle face.  (The seed: of 0 .. 11 at 200 x 170, most leave
+    nothing or one small patch after 8 dilations and 10 erosions; this one leaves three patches of 16, 8 and 4 faces for the components.)"""
+    V, f = grid(nx, ny)
+    n = len(f)
+    if selection == "seeded":
+        return V, f, np.random.default_rng(3).random(n) < 0.001
+    middle = np.arange(n) == n // 2
+    return V, f, middle if selection == "middle" else ~middle
+
+
+LAUNCH_CASES = {                   # name: (builder, its arguments, the selections)
+    "strip_4099_reversed": (strip_permuted, (4099, "reversed"), ("all", "runs_of_96")),
+    "strip_4099_random": (strip_permuted, (4099, "random"), ("all", "runs_of_96")),
+    "strip_4099_evens_first": (strip_permuted, (4099, "evens_first"), ("all", "runs_of_96")),
+    "strip_20000_random": (strip_permuted, (20000, "random"), ("all", "runs_of_96")),
+    "isolated_4096": (isolated, (4096,), ("all", "half")),
+    "isolated_16384": (isolated, (16384,), ("all", "half")),
+    "isolated_16385": (isolated, (16385,), ("all", "half")),
+    "pairs_16384": (pairs, (16384,), (None,)),
+    "book_1000": (book, (1000,), (None,)),
+    "spheres_64": (spheres, (64,), ("random",)),
+    "grid_200x170": (grid_selected, (200, 170), ("middle", "seeded", "all_but_middle")),
+    "grid_40x30_saturated": (grid_selected, (40, 30), ("middle",)),
+}
+
+
+def launch_case(name, selection=None):
+    builder, args, selections = LAUNCH_CASES[name]
+    assert selection in selections, (name, selection)
+    return builder(*args) if selection is None else builder(*args, selection)

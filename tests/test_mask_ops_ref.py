@@ -82,3 +82,43 @@ def test_blur_support_of_an_impulse():
     m = (np.random.default_rng(3).random((50, 60)) < 0.02).astype(np.float64)
     support = R.gaussian_blur(R.dilate(m, 20), (21, 21)) > 0
     assert np.array_equal(support, R.morph(m, None, np.maximum, range(-20, 20), range(-20, 20)) > 0)       # offsets [-20, +19] in both axes
+
+
+# ---- what the cases of tests/test_gpu_mask_ops_launch.py rest on ----
+def test_sigma_above_zero_never_takes_the_table():
+    from youreditableavatar_amd import mask_ops
+    for k in (3, 5, 7, 31):
+        mine, ref = mask_ops.gaussian_kernel(k, 1.5), R.gaussian_kernel(k, 1.5)
+        assert mine.dtype == np.float64 and np.array_equal(mine, ref) and abs(mine.sum() - 1) < 1e-15
+        exact = np.exp(-(np.arange(k) - k // 2) ** 2 / 4.5)
+        assert np.allclose(mine, exact / exact.sum(), rtol=1e-14, atol=0)
+        if k in R.SMALL_GAUSSIAN:
+            assert not np.array_equal(mine, R.SMALL_GAUSSIAN[k]) and np.array_equal(mask_ops.gaussian_kernel(k, 0.0), R.SMALL_GAUSSIAN[k])
+    assert np.array_equal(mask_ops.gaussian_kernel(9), R.gaussian_kernel(9)) and np.array_equal(mask_ops.gaussian_kernel(31), R.gaussian_kernel(31))
+    w = R.gaussian_kernel(31)                                                   # sigma = 0.3 * (15 - 1) + 0.8 = 5
+    assert np.allclose(w, np.exp(-(np.arange(31) - 15.0) ** 2 / 50) / np.exp(-(np.arange(31) - 15.0) ** 2 / 50).sum(), rtol=1e-14, atol=0)
+
+
+@pytest.mark.parametrize("ksize,sigma", [((31, 31), 0.0), ((31, 1), 0.0), ((1, 31), 0.0), ((9, 9), 0.0), ((7, 7), 1.5), ((31, 31), 1.5)])
+def test_blur_of_the_smallest_image_and_of_two_and_four_channels_against_scipy(ksize, sigma):
+    ndi = pytest.importorskip("scipy.ndimage")
+    rng = np.random.default_rng(4)
+    for shape in ((16, 16), (16, 16, 2), (16, 300, 4), (130, 65, 2)):           # 16: the smallest legal line at k = 31, folded at both ends
+        img = rng.random(shape)
+        rows = ndi.correlate1d(img, R.gaussian_kernel(ksize[0], sigma), axis=1, mode="mirror")
+        want = ndi.correlate1d(rows, R.gaussian_kernel(ksize[1], sigma), axis=0, mode="mirror")
+        assert np.allclose(R.gaussian_blur(img, ksize, sigma), want, rtol=1e-13, atol=0)
+
+
+def test_min_and_max_of_subnormals_and_infinities_are_exact():
+    pytest.importorskip("torch")
+    from tests.test_gpu_mask_ops_launch import special_floats
+    values = special_floats("all")
+    assert len(values) == 20 and len(set(values.view(np.int32).tolist())) == 20 and not (values == 0).any()
+    img = values[np.random.default_rng(5).integers(0, 20, (9, 11))]
+    for k, ref, pick in ((3, R.erode, min), (2, R.dilate, max)):
+        got = ref(img, k)
+        for y in range(9):
+            for x in range(11):                                                 # Python floats: every float32 exactly, compared exactly
+                window = [float(img[yy, xx]) for yy in range(max(0, y - k // 2), min(9, y + k - k // 2)) for xx in range(max(0, x - k // 2), min(11, x + k - k // 2))]
+                assert float(got[y, x]) == pick(window) and got[y, x].view(np.int32) in img.view(np.int32)
