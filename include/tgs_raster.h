@@ -608,6 +608,52 @@ int tgs_mesh_antialias_backward(void* stream, int V, int F, int C, const float* 
                                 const float* rast, const float* color, const float* dL_dout, float* dL_dcolor, float* dL_dpos,
                                 float pos_gradient_boost, void* workspace, size_t workspace_bytes);
 
+/* ---- mesh shading ----
+ * The renderer's body between interpolate and antialias (models/renderers/part_nvdiff_rasterizer.py :112-148, the same lines in
+ * models/geometry/implicit_sdf.py :291-317) as one forward and one backward call: the packed map out[n_pixels,C] of one image, C = 4 (mask,
+ * normal) when zattr is NULL and C = 5 (mask, normal, depth) when it is given.  rast[n_pixels,4] and tri[F,3] are the rasterizer's, vn[V,3] the
+ * vertex normals, zattr[V] the clip-space z column, camera = 1 / 0 the mode (camera / world), rot[9] the image's c2w[:3,:3], row-major fp32 on
+ * the device (read in camera mode only), flip = 1 / 0.  One lane per pixel; the arithmetic is in double from the fp32 inputs, rounded once on
+ * store.  Nothing is read back and nothing is allocated.
+ * The rules, forward.  A pixel is covered when interpolate's decode accepts it: ID in [1, F] and the face's three indices in [0, V).
+ *   covered      face rast.w - 1 with vertex rows a0, a1, a2: m = u a0 + v a1 + (1 - u - v) a2.  Channel 0 is 1.
+ *   world        n = m / max(|m|, 1e-12), stored in channel order (n.y, n.z, n.x).
+ *   camera       m' = R^-1 m with R^-1 the inverse of rot, found per image in double by adjugate over determinant inside the kernel; if flip
+ *                and m'.z < 0 then m' = -m'; n = m' / max(|m'|, 1e-12), stored (n.x, n.y, n.z).
+ *   channels 1..3  the stored value is (n + 1) / 2 in both modes.
+ *   channel 4    z = u z0 + v z1 + (1 - u - v) z2, d = 1 / (z + 1e-7), stored as (d - dmin) / (dmax - dmin + 1e-7) with dmin and dmax the
+ *                extremes of d over the image's covered pixels.  They are found in a first pass with integer atomic max on an
+ *                order-preserving image of the double (its complement for the minimum): the result does not depend on the order of arrival.
+ *                They stay in the workspace and are never read back.
+ *   uncovered    exact zeros in every channel.
+ * Two departures from the reference's lines, because this path reads nothing back: a determinant of rot that is zero or not finite makes
+ * that image's normals NaN (the framework's matrix inverse raises there); an image with no covered pixel gets an all-zero depth channel and no error (the
+ * reference fails on the max of an empty tensor).
+ * The rules, backward, from the upstream g[n_pixels,C].  Channel 0 of g is ignored: the mask has no gradient of its own.
+ *   normal       g_n = g / 2 (the inverse channel permutation in world mode); through normalize as F.normalize differentiates it:
+ *                (g_n - n (n . g_n)) / |m'| where |m'| >= 1e-12, and g_n / 1e-12 below that; then the flip's sign; then R^-T in camera mode.
+ *                The result is g_m, the gradient of the interpolated normal.
+ *   depth        with r = dmax - dmin + 1e-7, dL/dd_p = g_p / r; the pixels that attain dmax share -S2 / r^2 evenly and the pixels that
+ *                attain dmin share -S1 / r + S2 / r^2 evenly (the framework's max / min over a whole tensor), S1 = sum g_q and S2 = sum g_q (d_q -
+ *                dmin) over the covered pixels.  S1, S2 and the two tie counts are reduced in a fixed order: per-workgroup partial sums in
+ *                double, added in ascending workgroup order.  Then dL/dz = -dL/dd d^2.
+ *   interpolate  from g_m and dL/dz the rules are those of "mesh rasterizer: gradients": u, v and 1 - u - v times the gradient go to the
+ *                three vertex rows of dL_dvn[V,3] and dL_dzattr[V]; dL_drast[n_pixels,4] gets sum_c g_c (a0_c - a2_c) and sum_c g_c (a1_c -
+ *                a2_c) in channels 0 and 1 (normal and depth added), channels 2 and 3 exact zeros.
+ * The two vertex scatters are the fixed-point scheme of "mesh rasterizer: gradients", one shared header: a bound per gradient found on the
+ * device by a measuring pass, llrint(c 2^(34 - e)), runs of equal destination pre-reduced in the wave, one no-return 64-bit integer atomic per
+ * run and element, a converting pass.  There are no float atomics and two runs give the same bits.  A NaN or an infinity in a contribution
+ * makes every element of that gradient tensor NaN.  Each of dL_dvn, dL_dzattr (needs zattr) and dL_drast is optional: NULL launches nothing
+ * for it.  F == 0, V == 0 or no covered pixel: zeros.
+ * workspace: device scratch of tgs_meshshade_workspace_bytes(V, C, n_pixels) bytes (0 for sizes that are refused: V < 0, C not 4 or 5,
+ * n_pixels outside [0, 8192^2]). */
+size_t tgs_meshshade_workspace_bytes(int V, int C, int64_t n_pixels);
+int tgs_meshshade(void* stream, int V, int F, const int32_t* tri, const float* vn, const float* zattr, int camera, const float* rot, int flip,
+                   int64_t n_pixels, const float* rast, float* out, void* workspace, size_t workspace_bytes);
+int tgs_meshshade_backward(void* stream, int V, int F, const int32_t* tri, const float* vn, const float* zattr, int camera, const float* rot, int flip,
+                            int64_t n_pixels, const float* rast, const float* dL_dout, float* dL_dvn, float* dL_dzattr, float* dL_drast,
+                            void* workspace, size_t workspace_bytes);
+
 /* ---- marching tetrahedra ----
  * The step in front of the mesh rasterizer in the geometry stage: MarchingTetrahedraHelper._forward (tetgs_spatial/models/isosurface.py :112-184,
  * called from forward, _isosurface and _isosurface_subdiv) and the call shape of the two marching_tetrahedra calls of models/geometry/base.py

@@ -1,7 +1,7 @@
-"""The host layer under ``mesh_raster``, ``mesh_raster_aa`` and ``mesh_raster_grad`` (private: those three are what callers import).
+"""The host layer under ``mesh_raster``, ``mesh_raster_aa``, ``mesh_raster_grad`` and ``mesh_shade`` (private: those four are what callers import).
 
-The pieces every geometry module shares (``declare``, the guard, the raw stream, the device check) are ``_host``'s.  Written once here: the ctypes signatures of the eleven ``tgs_mesh_*`` entry points (``SIGNATURES``, ``declare``); the argument checks of the four calls
-(``rasterize``, ``interpolate``, ``antialias``, ``topology``: types, shapes and dtypes, then ``tri``, the gradient refusal, resolution or extent, the device
+The pieces every geometry module shares (``declare``, the guard, the raw stream, the device check) are ``_host``'s.  Written once here: the ctypes signatures of the eleven ``tgs_mesh_*`` and the three ``tgs_meshshade*`` entry points (``SIGNATURES``, ``SHADE_SIGNATURES``, ``declare``); the argument checks of the five calls
+(``rasterize``, ``interpolate``, ``antialias``, ``topology``, ``shade``: types, shapes and dtypes, then ``tri``, the gradient refusal, resolution or extent, the device
 last), each returning the ``Call`` record forward and backward work from; the broadcast rule (``image_of``); N images through one native function
 (``run_images``); where a topology comes from (``topology_of``); the order of ``sum_images``.
 """
@@ -32,11 +32,16 @@ SIGNATURES = {                     # name: (restype, argtypes), as include/tgs_r
     "tgs_mesh_rasterize_backward": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _Z]),
     "tgs_mesh_antialias_backward": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _F, _P, _Z]),
 }
+SHADE_SIGNATURES = {               # the "mesh shading" block of the header: its own prefix, as the other geometry blocks have theirs
+    "tgs_meshshade_workspace_bytes": (_Z, [_I, _I, _L]),
+    "tgs_meshshade": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _L, _P, _P, _P, _Z]),
+    "tgs_meshshade_backward": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _L, _P, _P, _P, _P, _P, _P, _Z]),
+}
 
 
 def declare(lib):
-    """applies ``SIGNATURES`` to a handle of the native library -> the handle"""
-    return _host.declare(lib, SIGNATURES)
+    """applies ``SIGNATURES`` and ``SHADE_SIGNATURES`` to a handle of the native library -> the handle"""
+    return _host.declare(_host.declare(lib, SIGNATURES), SHADE_SIGNATURES)
 
 
 _lib = declare(_host.lib)                                                       # once: the three modules work on this handle
@@ -127,6 +132,58 @@ def topology(tri: torch.Tensor, num_vertices: Optional[int]) -> Call:
     if V < 0:
         raise RuntimeError(f"num_vertices must be >= 0, got {num_vertices}")
     return Call(1, 0, 0, V, 0, int(tri.shape[0]), _need_device("mesh_raster", tri=tri))
+
+
+NORMAL_TYPES = ("camera", "world")
+
+
+def shade(rast: torch.Tensor, tri: torch.Tensor, vn: torch.Tensor, normal_type: str, c2w: Optional[torch.Tensor], flip, pos_clip: Optional[torch.Tensor]) -> Call:
+    """the packed map's call: C = 4, or 5 with ``pos_clip``; ``per_image`` is ``vn``'s (``per_image_of`` says it for ``pos_clip``)"""
+    if not isinstance(rast, torch.Tensor) or not isinstance(vn, torch.Tensor):
+        raise RuntimeError("rast and vn must be tensors")
+    N, H, W = _check_rast(rast)
+    if vn.dtype != torch.float32 or vn.dim() not in (2, 3) or vn.shape[-1] != 3 or (vn.dim() == 3 and vn.shape[0] not in (1, N)):
+        raise RuntimeError(f"expected float32 vn of shape [{N},V,3], [1,V,3] or [V,3], got {vn.dtype} {tuple(vn.shape)}")
+    V = int(vn.shape[-2])
+    if normal_type not in NORMAL_TYPES:
+        raise ValueError(f"Unknown normal type: {normal_type} (expected 'camera' or 'world')")
+    if normal_type == "world" and c2w is not None:
+        raise RuntimeError("normal_type='world' reads no camera: c2w must be None")
+    if normal_type == "camera":
+        if not isinstance(c2w, torch.Tensor):
+            raise RuntimeError("normal_type='camera' needs c2w, the camera-to-world matrix of every image")
+        k = c2w.shape[-1] if c2w.dim() else 0
+        if c2w.dtype != torch.float32 or c2w.dim() not in (2, 3) or k not in (3, 4) or c2w.shape[-2] != k or (c2w.dim() == 3 and c2w.shape[0] not in (1, N)):
+            raise RuntimeError(f"expected float32 c2w of shape [{N},4,4], [1,4,4], [4,4] or the same with 3, got {c2w.dtype} {tuple(c2w.shape)}")
+    if not isinstance(flip, (bool, int)):
+        raise RuntimeError(f"flip must be True or False, got {type(flip).__name__}")
+    if pos_clip is not None:
+        if not isinstance(pos_clip, torch.Tensor):
+            raise RuntimeError("pos_clip must be a tensor or None")
+        if pos_clip.dtype != torch.float32 or pos_clip.dim() not in (2, 3) or tuple(pos_clip.shape[-2:]) != (V, 4) or (pos_clip.dim() == 3 and pos_clip.shape[0] not in (1, N)):
+            raise RuntimeError(f"expected float32 pos_clip of shape [{N},{V},4], [1,{V},4] or [{V},4] (vn has {V} rows), got {pos_clip.dtype} {tuple(pos_clip.shape)}")
+    _check_tri(tri)
+    if N * H * W and H * W > MAX_RESOLUTION * MAX_RESOLUTION:
+        raise RuntimeError(f"rast must have at most {MAX_RESOLUTION}^2 pixels per image, got {tuple(rast.shape)}")
+    tensors = dict(rast=rast, tri=tri, vn=vn)
+    if normal_type == "camera":
+        tensors["c2w"] = c2w
+    if pos_clip is not None:
+        tensors["pos_clip"] = pos_clip
+    dev = _need_device("mesh_shade", **tensors)
+    return Call(N, H, W, V, 4 if pos_clip is None else 5, int(tri.shape[0]), dev, per_image_of(vn, N))
+
+
+def per_image_of(t: torch.Tensor, N: int) -> bool:
+    """the input has a row per image (its gradient is stacked, not summed)"""
+    return t.dim() == 3 and t.shape[0] == N and N != 1
+
+
+def shade_workspace_bytes(call: Call) -> int:
+    nbytes = int(_lib.tgs_meshshade_workspace_bytes(call.V, call.C, call.H * call.W))
+    if nbytes == 0:
+        raise RuntimeError(f"no shading workspace for V = {call.V}, C = {call.C}, {call.H * call.W} pixels")
+    return nbytes
 
 
 def image_of(t: torch.Tensor, n: int, N: int) -> torch.Tensor:

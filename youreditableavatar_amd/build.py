@@ -17,7 +17,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, os.environ.get("TGS_LIB_NAME", "libtgs_raster.so"))       # TGS_LIB_NAME: build a variant next to the default one
 SOURCES = ["tgs_forward.hip", "tgs_backward.hip", "tgs_api.hip", "tgs_shcolor.hip", "tgs_knn.hip", "tgs_loss.hip", "tgs_bind.hip", "tgs_optim.hip", "tgs_reg.hip", "tgs_depth.hip",
            "tgs_feature.hip", "tgs_median.hip", "tgs_mesh.hip", "tgs_mesh_aa.hip", "tgs_mesh_grad.hip", "tgs_marching_tets.hip", "tgs_mesh_geom.hip", "tgs_hashgrid.hip", "tgs_tet_grid.hip", "tgs_mesh_sdf.hip",
-           "tgs_mask_ops.hip", "tgs_mesh_region.hip", "tgs_mesh_rays.hip"]
+           "tgs_mask_ops.hip", "tgs_mesh_region.hip", "tgs_mesh_rays.hip", "tgs_mesh_shade.hip"]
 ARCH = "gfx950"
 # -fno-slp-vectorize: the SLP vectoriser pairs scalar f32 operations into v_pk_fma_f32 / v_pk_mul_f32, which on gfx950 issue no faster than
 # the two scalar instructions (MI355X_MICROARCH.md: packed f32 VALU is an anti-lever) while the pairing costs registers and moves:

@@ -1,7 +1,7 @@
-// tgs_grad_fixed.hpp -- the fixed-point scatter of a gradient, shared by tgs_mesh_grad.hip and tgs_hashgrid.hip: one exponent per call from a
+// tgs_grad_fixed.hpp -- the fixed-point scatter of a gradient, shared by tgs_mesh_grad.hip, tgs_hashgrid.hip and tgs_mesh_shade.hip: one exponent per call from a
 // device-side bound that is never read back, contributions as 64-bit integers, the lanes of a wave pre-reduced over runs of equal
 // destination, one no-return integer atomic per run and element, one convert pass with one rounding.  No float atomics.  (The heads of the
-// two sources and include/tgs_raster.h have the reasons and the resolution.)
+// sources and include/tgs_raster.h have the reasons and the resolution.)
 #pragma once
 #include "tgs_device.hpp"
 
